@@ -12,8 +12,14 @@ as interleaved 8x8 tiles (tile t -> rank t % N); total work is fixed, so the
 scaling is strong.  value = closest-hit queries of all ranks / max-over-ranks
 wall time (Mray/s).
 
-Roofline: `achieved` = the MEASURED HBM bytes of the frame's kernels (rocprofv3
-PMC passes of this build and workload, run by this bench in child processes:
+A plain run sets up, warms up, times --steps frames, writes the last step's
+outputs if --dump-outputs DIR is given, and prints the headline line.
+Everything below -- the counting render behind the bytes model, the roofline
+passes, the other pipeline, the C4 / SAH / C5 lines, the CPU baseline -- runs
+only with --full, after the timed steps.
+
+Roofline (--full): `achieved` = the MEASURED HBM bytes of the frame's kernels
+(rocprofv3 PMC passes of this build and workload, run by this bench in child processes:
 FETCH_SIZE x2 + WRITE_SIZE) / their HIP-event duration; the traversal (path
 kernel / wavefront extend) is bound by VALU issue and latency, reported under
 roofline.valu (issue and lane fractions from the same passes); SURVEY.md
@@ -26,7 +32,7 @@ configs[0] (C1: 512x512, 16 spp, whole frame, one thread) on the CPU oracle,
 plus the same oracle on all of this process's cores over whole frames of the
 workload at a few samples per pixel.
 
-Launch:  python bench.py [--gpus 1 --steps 3 --warmup 1]
+Launch:  python bench.py [--gpus 1 --steps 3 --warmup 1] [--full] [--dump-outputs DIR]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
              --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
          python bench.py --gpus N ...   (no launcher: starts the line above as a
@@ -387,7 +393,7 @@ def child_line(args, scene: str, spp: int, steps: int, warmup: int, tag: str, ex
     roofline passes) in a child process of this bench (its own GPU context;
     this process's workspace stays allocated beside it)."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--scene", scene, "--no-extra", "--no-alt",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--scene", scene, "--no-extra", "--no-alt",
            "--no-cpu-baseline", "--steps", str(steps), "--warmup", str(warmup),
            "--width", str(args.width), "--height", str(args.height), "--spp", str(spp),
            "--spp-chunk", str(args.spp_chunk), "--pipeline", args.pipeline] + (["--no-pmc"] if args.no_pmc else []) + \
@@ -445,6 +451,27 @@ def c5_sorted_line(args) -> dict:
     return line
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d: str, image, rays_per_step: int) -> None:
+    """--dump-outputs: what the last timed step handed its caller, as .npy files
+    in `d`: image.npy, the (H, W, 4) float32 framebuffer (a larger frame than
+    DUMP_LIMIT_BYTES: a fixed, seeded sample of its pixels, (n, 4), with their
+    flat indices in image_index.npy), and rays.npy, the closest-hit queries of
+    one step as a float64 (exact: they stay far below 2^53)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    if image.nbytes > DUMP_LIMIT_BYTES:
+        flat = image.reshape(-1, image.shape[-1])
+        n = (DUMP_LIMIT_BYTES // 2) // (flat.shape[1] * 4)
+        idx = np.sort(np.random.default_rng(12345).choice(flat.shape[0], size=n, replace=False))
+        np.save(os.path.join(d, "image_index.npy"), idx.astype(np.float64))
+        image = flat[idx]
+    np.save(os.path.join(d, "image.npy"), np.ascontiguousarray(image, dtype=np.float32))
+    np.save(os.path.join(d, "rays.npy"), np.array([rays_per_step], dtype=np.float64))
+
+
 def launch_ranks(args, argv: list) -> int:
     """`--gpus N > 1` started without a launcher (no WORLD_SIZE): run N ranks
     as the driver would -- `torch.distributed.run --nproc-per-node N` on this
@@ -495,6 +522,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else this bench measures: the counting render "
+                         "behind the bytes model, the rocprofv3 PMC roofline passes, the copy-bandwidth "
+                         "microbenchmark, the other pipeline's timing, the C4 / SAH / C5 lines and the CPU baseline "
+                         "(each still has its own --no-... switch).  Without it a run sets up, warms up, times "
+                         "--steps frames and prints the headline line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed into DIR: image.npy, the (gathered) "
+                         "(H, W, 4) float32 framebuffer, and rays.npy, its closest-hit query count (float64)")
     ap.add_argument("--scene", default="scene01")
     ap.add_argument("--layout", choices=["auto", "global"], default="auto",
                     help="scene image placement (mcpt_scene_options::layout): LDS when it fits, or global memory "
@@ -545,6 +581,8 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 PMC passes (HBM bytes, VALU issue)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # one render under rocprofv3
     args = ap.parse_args()
+    if not args.full:   # the plain run: the timed steps and the headline line only
+        args.no_alt = args.no_pmc = args.no_cpu_baseline = args.no_extra = True
     if args.no_extra:
         args.no_c4 = args.no_c5 = args.no_sah = True
     if args.gpus < 1:
@@ -634,10 +672,12 @@ def main():
         if gatherer is not None:
             gatherer.gather(fb)   # RCCL gather of the packed tile buffers + unpermute on rank 0
 
-    scene.stats()
-    scene.render_device(p_count, fb.data_ptr(), stream.cuda_stream)   # untimed counting render
-    torch.cuda.synchronize(dev)
-    counts = scene.stats()
+    # --full: the node/leaf/triangle counts of the bytes model and the roofline
+    if args.full:
+        scene.stats()
+        scene.render_device(p_count, fb.data_ptr(), stream.cuda_stream)   # untimed counting render
+        torch.cuda.synchronize(dev)
+        counts = scene.stats()
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
@@ -662,10 +702,13 @@ def main():
 
     # the other pipeline on the same frame, for comparison (N = 1; same image, bit for bit)
     alt = None
-    if args.dump_image and rank == 0:   # before the comparison renders reuse fb
+    last_image = None
+    if (args.dump_image or args.dump_outputs) and rank == 0:   # before the comparison renders reuse fb
         import numpy as np
         img = gatherer.image if gatherer is not None else fb
-        np.save(args.dump_image, img.view(args.height, args.width, 4).cpu().numpy())
+        last_image = img.view(args.height, args.width, 4).cpu().numpy()
+        if args.dump_image:
+            np.save(args.dump_image, last_image)
     if n_gpus == 1 and not args.no_alt:
         other = "megakernel" if args.pipeline == "wavefront" else "wavefront"
         pa = dataclasses.replace(p, pipeline=other)
@@ -686,11 +729,14 @@ def main():
 
     # per-render node/leaf/triangle counts: the counting render's (identical for a lean one)
     renders = max(st["renders"], 1)
-    for k in ("paths", "inner_visits", "leaf_visits", "leaf_refs", "tri_tests", "shades", "stack_spills"):
-        if lean:
-            st[k] = counts[k] * renders
-    counts_match = counts["rays"] * renders == st["rays"]
-    count_keys = ("rays", "paths", "inner_visits", "leaf_visits", "leaf_refs", "tri_tests", "shades", "stack_spills")
+    count_keys = ("rays",)
+    if args.full:
+        for k in ("paths", "inner_visits", "leaf_visits", "leaf_refs", "tri_tests", "shades", "stack_spills"):
+            if lean:
+                st[k] = counts[k] * renders
+        counts_match = counts["rays"] * renders == st["rays"]
+        count_keys = ("rays", "paths", "inner_visits", "leaf_visits", "leaf_refs", "tri_tests", "shades",
+                      "stack_spills")
     kern_ms = st["kernel_ms"] / renders
     if world > 1:
         # whole-job counts (every rank's shard) and the slowest rank's time
@@ -703,14 +749,48 @@ def main():
             st[k] = int(agg[i].item())
     rays = st["rays"]
 
-    if rank == 0:
+    def headline() -> dict:
+        """The result line of a plain run: the timed steps' figures and the configuration."""
+        workload = f"cornell_{args.width}x{args.height}_{args.spp}spp" + \
+            ("" if args.scene == "scene01" else f"_{args.scene}") + \
+            ("" if args.kd_build == "reference" else f"_kd_{args.kd_build}")
+        if args.pipeline == "wavefront":
+            sched = {k: plan[k] for k in ("wf_streams", "wf_batch", "wf_batch_default", "wf_refill", "wf_group_shift")}
+        else:
+            sched = {k: plan[k] for k in ("ready_thresh", "tail_units")}
+        sched["workspace_GB"] = round(plan["workspace_bytes"] / 1e9, 2)
+        if n_gpus > 1:
+            par = (f"pixel-tiles x{n_gpus} + " + (f"{'rccl' if backend == 'nccl' else backend} gather" if world > 1
+                                                  else f"{'peer-copy' if args.gather == 'peer' else 'rccl'} gather "
+                                                       f"(one process, mcpt_init({devices}))"))
+        else:
+            par = "pixel-tiles x1"
+        return {
+            "metric": METRIC, "value": round(rays / elapsed / 1e6, 3), "unit": "Mray/s", "n_gpus": n_gpus,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+            "data": f"bundled reference scene {args.scene}.obj (Cornell Box), synthetic camera/seed",
+            "config": {"workload": workload, "scene": args.scene,
+                       "width": args.width, "height": args.height, "spp": args.spp, "max_depth": 7,
+                       "spp_chunk": args.spp_chunk, "parallelism": par, "pipeline": args.pipeline,
+                       "wf_sort": bool(args.wf_sort), "kd_build": args.kd_build,
+                       "kd_nodes": scene.info()["n_nodes"],
+                       "kernel_variant": st["variant"], "schedule": sched},
+            "rays_per_step": rays // args.steps,
+            "timed_kernel": (f"lean {'megakernel' if args.pipeline == 'megakernel' else 'wavefront extend'} "
+                             "(traversal counters compiled out)") if lean else "counting",
+            "kernel_ms_avg": round(kern_ms, 3),
+            "gpu_ms_per_step_event": round(ev0.elapsed_time(ev1) / args.steps, 3),
+        }
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_image, rays // args.steps)
+    if rank == 0 and not args.full:
+        print(json.dumps(headline()), flush=True)
+    elif rank == 0:
         per_launch = {k: st[k] / renders for k in count_keys}
         ab = algorithmic_bytes(per_launch, args.width * args.height)
         algo_gbs = ab["survey"] / (kern_ms * 1e-3) / 1e9
-        mray = rays / elapsed / 1e6
-        workload = f"cornell_{args.width}x{args.height}_{args.spp}spp" + ("" if args.scene == "scene01" else
-                                                                            f"_{args.scene}") + \
-            ("" if args.kd_build == "reference" else f"_kd_{args.kd_build}")
         cus = torch.cuda.get_device_properties(dev).multi_processor_count
         # the PMC passes profile one device's share: rank 0's shard (N > 1) or the whole frame
         shard = (n_gpus, 0) if n_gpus > 1 else (1, 0)
@@ -812,42 +892,18 @@ def main():
                                "own_layout_GBps": round(ab["own"] / (kern_ms * 1e-3) / 1e9, 1),
                                "per_ray": {k: round(per_launch[k] / max(per_launch["rays"], 1), 3) for k in
                                            ("inner_visits", "leaf_visits", "leaf_refs", "tri_tests", "shades")}}
-        sched = {k: plan[k] for k in ("wf_streams", "wf_batch", "wf_batch_default", "wf_refill", "wf_group_shift")
-                 if args.pipeline == "wavefront"} if args.pipeline == "wavefront" else \
-            {k: plan[k] for k in ("ready_thresh", "tail_units")}
-        sched["workspace_GB"] = round(plan["workspace_bytes"] / 1e9, 2)
-        if n_gpus > 1:
-            par = (f"pixel-tiles x{n_gpus} + " + (f"{'rccl' if backend == 'nccl' else backend} gather" if world > 1
-                                                  else f"{'peer-copy' if args.gather == 'peer' else 'rccl'} gather "
-                                                       f"(one process, mcpt_init({devices}))"))
-        else:
-            par = "pixel-tiles x1"
-        line = {
-            "metric": METRIC, "value": round(mray, 3), "unit": "Mray/s", "n_gpus": n_gpus, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-            "data": f"bundled reference scene {args.scene}.obj (Cornell Box), synthetic camera/seed",
-            "config": {"workload": workload, "scene": args.scene,
-                       "width": args.width, "height": args.height, "spp": args.spp, "max_depth": 7,
-                       "spp_chunk": args.spp_chunk, "parallelism": par, "pipeline": args.pipeline,
-                       "wf_sort": bool(args.wf_sort), "kd_build": args.kd_build,
-                       "kd_nodes": scene.info()["n_nodes"],
-                       "kernel_variant": st["variant"], "schedule": sched},
-            "rays_per_step": rays // args.steps,
+        line = headline()
+        line.update({
             "paths_per_step": st["paths"] // args.steps,
             "mpath_s": round(st["paths"] / elapsed / 1e6, 3),
             "rays_per_path": round(st["rays"] / max(st["paths"], 1), 4),
             "stack_spills_per_ray": round(st["stack_spills"] / max(st["rays"], 1), 4),
-            "timed_kernel": (f"lean {'megakernel' if args.pipeline == 'megakernel' else 'wavefront extend'} "
-                             "(traversal counters compiled out)") if lean else "counting",
             "counts_source": ("untimed counting render of the same frame; its rays equal the timed "
                               f"renders': {counts_match}") if lean else "timed renders",
-            "kernel_ms_avg": round(kern_ms, 3),
-            "gpu_ms_per_step_event": round(ev0.elapsed_time(ev1) / args.steps, 3),
             "roofline": roof,
             "cpu_baseline": None,
             "other_pipeline": alt,
-        }
+        })
         if n_gpus == 1 and args.scene == "scene01":
             extra = {}
             if not args.no_c4:

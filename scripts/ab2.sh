@@ -9,7 +9,7 @@ if [ -z "$NOTEST" ]; then
   MCPT_LIB_PATH=$PWD/montecarlopathtracer_amd/lib/$first timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > gpurun_out/ab2/tests.log 2>&1 || { echo "tests FAILED"; tail -40 gpurun_out/ab2/tests.log; exit 1; }
   tail -1 gpurun_out/ab2/tests.log
 fi
-alt="--no-alt"; [ -z "$NOALT" ] && alt=""
+alt="--full --no-alt"; [ -z "$NOALT" ] && alt="--full"   # --full: the megakernel and the C4 line beside it
 for round in $(seq 1 ${ROUNDS:-2}); do
 for lib in $LIBS; do
   MCPT_LIB_PATH=$PWD/montecarlopathtracer_amd/lib/$lib timeout -k 10 300 python bench.py $alt --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline --no-pmc --no-c5 $ARGS > gpurun_out/ab2/b_${lib}_$round.log 2>&1

@@ -21,7 +21,7 @@ PY
 done
 done
 if [ -z "$NOPMC" ]; then
-  timeout -k 10 400 python bench.py --scene cornell_bunny70k --no-alt --steps 1 --warmup 1 --no-cpu-baseline --keep-pmc $O/pmc > $O/pmc_line.jsonl 2> $O/pmc_line.err
+  timeout -k 10 400 python bench.py --scene cornell_bunny70k --no-alt --steps 1 --warmup 1 --full --no-cpu-baseline --keep-pmc $O/pmc > $O/pmc_line.jsonl 2> $O/pmc_line.err
   python3 - $O/pmc_line.jsonl <<'PY'
 import json, sys
 ln = [json.loads(x) for x in open(sys.argv[1]) if x.startswith("{")][-1]

@@ -6,7 +6,7 @@ set -e
 O=gpurun_out/lines
 mkdir -p $O
 B="python bench.py --no-cpu-baseline --no-pmc"
-BW="python bench.py --no-cpu-baseline"
+BW="python bench.py --full --no-cpu-baseline"
 timeout -k 10 300 $B --pipeline megakernel --no-alt --steps 3 --warmup 1 > $O/c2_megakernel.jsonl 2> $O/c2_megakernel.err
 timeout -k 10 300 $B --pipeline megakernel --no-alt --scene cornell_bunny70k --spp 1024 --steps 2 --warmup 1 > $O/c4_megakernel.jsonl 2> $O/c4_megakernel.err
 timeout -k 10 400 $BW --scene cornell_bunny70k --spp 1024 --pipeline wavefront --no-alt --steps 2 --warmup 1 > $O/c4_wavefront.jsonl 2> $O/c4_wavefront.err

@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU suite + the default bench line (with its PMC csv kept) on one box.
+# GPU suite + the bench line of a --full run (with its PMC csv kept) on one box.
 #   OUT=gpurun_out/r05 [BENCH_ARGS=...] [NOTEST=1] bash scripts/gpu_check.sh
 set -e
 O=${OUT:-gpurun_out/check}
@@ -8,7 +8,7 @@ if [ -z "$NOTEST" ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $O/gputest.log 2>&1 || { echo "tests FAILED"; tail -40 $O/gputest.log; exit 1; }
   tail -1 $O/gputest.log
 fi
-timeout -k 10 600 python bench.py --steps ${STEPS:-10} --warmup 2 --keep-pmc $O/pmc_wf $BENCH_ARGS > $O/bench.jsonl 2> $O/bench.err
+timeout -k 10 600 python bench.py --full --steps ${STEPS:-10} --warmup 2 --keep-pmc $O/pmc_wf $BENCH_ARGS > $O/bench.jsonl 2> $O/bench.err
 python3 - $O/bench.jsonl <<'PY'
 import json, sys
 ln = [json.loads(x) for x in open(sys.argv[1]) if x.startswith("{")][-1]

@@ -7,7 +7,7 @@ R=$PWD
 O=$R/gpurun_out/r04
 mkdir -p $O
 export TMPDIR=/tmp
-timeout -k 10 600 python3 bench.py --keep-pmc $O/pmc_wf > $O/bench.jsonl 2> $O/bench.err
+timeout -k 10 600 python3 bench.py --full --keep-pmc $O/pmc_wf > $O/bench.jsonl 2> $O/bench.err
 tail -c 300 $O/bench.jsonl
 for sc in scene01 cornell_bunny70k; do
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$sc -o run -- \

@@ -10,7 +10,7 @@ mkdir -p $O
 O=$(cd $O && pwd)
 export TMPDIR=/tmp
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 && tail -2 $O/smoke.log
-timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 --keep-pmc $O/pmc_wf > $O/bench.jsonl 2> $O/bench.err
+timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full --keep-pmc $O/pmc_wf > $O/bench.jsonl 2> $O/bench.err
 python3 - $O/bench.jsonl <<'PY'
 import json, sys
 ln = [json.loads(x) for x in open(sys.argv[1]) if x.startswith("{")][-1]

@@ -10,7 +10,7 @@ tail -1 $O/gputest.log
 LIBS="libmcpt.so libmcpt_sah_ci10.so libmcpt_sah_ci12.so libmcpt_sah_ci25.so" ROUNDS=2 STEPS=10 NOTEST=1 NOALT=1 \
   ARGS="--kd-build sah --no-c4" bash scripts/ab2.sh
 mkdir -p $O/ab_sah && cp gpurun_out/ab2/b_*.log $O/ab_sah/
-timeout -k 10 600 python bench.py > $O/default_bench.jsonl 2> $O/default_bench.err
+timeout -k 10 600 python bench.py --full > $O/default_bench.jsonl 2> $O/default_bench.err
 python3 - $O/default_bench.jsonl <<'PY'
 import json, sys
 ln = [json.loads(x) for x in open(sys.argv[1]) if x.startswith("{")][-1]

@@ -11,7 +11,7 @@ rm -rf gpurun_out/ab2
 LIBS="libmcpt.so libmcpt_sah_np.so libmcpt_sah_p25.so libmcpt_sah_p15.so" ROUNDS=2 STEPS=10 NOTEST=1 NOALT=1 \
   ARGS="--kd-build sah --no-c4" bash scripts/ab2.sh
 mkdir -p $O/ab_sah && cp gpurun_out/ab2/b_*.log $O/ab_sah/
-timeout -k 10 600 python bench.py > $O/default_bench.jsonl 2> $O/default_bench.err
+timeout -k 10 600 python bench.py --full > $O/default_bench.jsonl 2> $O/default_bench.err
 python3 - $O/default_bench.jsonl <<'PY'
 import json, sys
 ln = [json.loads(x) for x in open(sys.argv[1]) if x.startswith("{")][-1]

@@ -9,11 +9,11 @@ set -e
 mkdir -p gpurun_out/rehearse
 for n in ${NS:-4 8}; do
   if [ -n "$SELF" ]; then
-    MCPT_DIST_BACKEND=gloo timeout -k 10 500 python bench.py --gpus $n --steps 2 --warmup 1 \
+    MCPT_DIST_BACKEND=gloo timeout -k 10 500 python bench.py --gpus $n --steps 2 --warmup 1 --full \
       --no-cpu-baseline --dump-image gpurun_out/rehearse/img_n$n.npy > gpurun_out/rehearse/n$n.log 2>&1
   else
     MCPT_DIST_BACKEND=gloo MASTER_ADDR=127.0.0.1 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 \
-      --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --gpus $n --steps 2 --warmup 1 \
+      --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --gpus $n --steps 2 --warmup 1 --full \
       --no-cpu-baseline --dump-image gpurun_out/rehearse/img_n$n.npy > gpurun_out/rehearse/n$n.log 2>&1
   fi
   grep '^{' gpurun_out/rehearse/n$n.log > gpurun_out/rehearse/n$n.jsonl

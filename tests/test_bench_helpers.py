@@ -149,3 +149,60 @@ def test_pmc_child_replays_the_line_s_scene_options():
     w = bench._workload_args(a, (2, 1))
     assert w[w.index("--kd-build") + 1] == "sah" and "--wf-sort" in w
     assert w[w.index("--pmc-shard") + 1] == "2,1"
+
+
+def test_dump_outputs_writes_the_frame_and_its_ray_count(tmp_path):
+    """--dump-outputs: image.npy is the framebuffer as float32, rays.npy the
+    step's ray count as float64; a second dump of the same frame is identical."""
+    import numpy as np
+    bench = _bench()
+    img = np.arange(6 * 5 * 4, dtype=np.float32).reshape(6, 5, 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), img, 12345678901)
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+    rays = np.load(tmp_path / "a" / "rays.npy")
+    assert rays.dtype == np.float64 and rays.tolist() == [12345678901.0]
+    assert sorted(os.listdir(tmp_path / "a")) == ["image.npy", "rays.npy"]
+    assert np.array_equal(np.load(tmp_path / "b" / "image.npy"), got)
+
+
+def test_dump_outputs_samples_a_frame_over_the_limit(tmp_path, monkeypatch):
+    """A frame larger than the dump limit is written as a fixed, seeded sample
+    of its pixels: the same pixels on every run, their flat indices beside
+    them, and the files together within the limit."""
+    import numpy as np
+    bench = _bench()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1024)
+    img = np.random.default_rng(1).random((16, 9, 4), dtype=np.float32)   # 2304 B
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), img, 7)
+    idx = np.load(tmp_path / "a" / "image_index.npy")
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert idx.dtype == np.float64 and got.dtype == np.float32
+    assert got.shape == (32, 4) and idx.shape == (32,)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 16 * 9
+    assert np.array_equal(got, img.reshape(-1, 4)[idx.astype(np.int64)])
+    assert got.nbytes + idx.nbytes + 8 <= 1024
+    assert np.array_equal(np.load(tmp_path / "b" / "image_index.npy"), idx)
+    assert np.array_equal(np.load(tmp_path / "b" / "image.npy"), got)
+
+
+def test_child_lines_are_full_runs(monkeypatch):
+    """The C4 / SAH / C5 lines carry a PMC roofline of their own: their child
+    processes run bench.py --full (a plain run stops after the timed steps)."""
+    import argparse
+    import subprocess
+    bench = _bench()
+    seen = {}
+
+    def fake_run(cmd, **kw):
+        seen["cmd"] = cmd
+        return subprocess.CompletedProcess(cmd, 0, stdout='{"value": 1.0}\n', stderr="")
+
+    monkeypatch.setattr(subprocess, "run", fake_run)
+    a = argparse.Namespace(width=64, height=48, spp=4, spp_chunk=2, pipeline="wavefront", no_pmc=False, keep_pmc="",
+                           steps=2, warmup=1)
+    assert bench.c4_line(a) == {"value": 1.0}
+    assert "--full" in seen["cmd"] and "--no-extra" in seen["cmd"]
+    assert seen["cmd"][seen["cmd"].index("--scene") + 1] == "cornell_bunny70k"

@@ -61,7 +61,7 @@ def test_bench_rank_path_gloo(mcpt, tmp_path, world, w, h, pmc):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--width", str(w), "--height", str(h),
-           "--spp", str(SPP), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--dump-image", out]
+           "--spp", str(SPP), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--dump-image", out]
     if not pmc:
         cmd.append("--no-pmc")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
