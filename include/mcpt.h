@@ -344,6 +344,58 @@ int mcpt_scene_reserve(mcpt_scene* s, const mcpt_render_params* p);
  * captured render is held to the scene's reservation, mcpt_scene_reserve).  */
 int mcpt_plan_query(mcpt_scene* s, const mcpt_render_params* p, mcpt_plan_info* out);
 
+/* ---- first-hit feature buffers (AOVs) and the denoiser --------------------- */
+/* Per-pixel features of the render's own primary rays: for the samples
+ * spp_offset .. spp_offset + spp - 1 of p, the ray the render of p traces
+ * first (same RNG stream, jitter and camera) and its closest hit through the
+ * renders' traversal.  Two row-major buffers, 4 floats per pixel, each channel
+ * the plain fp32 mean over the samples (a miss counts as zeros):
+ *   albedo_cov   = r g b coverage: the factor the first scatter multiplies into
+ *                  the throughput -- (1,1,1) on an emitter; Tr > 0: Kd if
+ *                  fresnel_kd (CVMCTracer mode only) else (1,1,1); Ns > 1: Ks;
+ *                  else Kd -- and 1 for a hit
+ *   normal_depth = nx ny nz t: the shading normal as the scatter forms it
+ *                  (interpolated, normalized, not flipped) and the hit's t
+ * prev_count > 0: each channel becomes (old * prev_count + mean) / (prev_count + 1),
+ * the linear running mean in both modes (the buffers are read).
+ * The call takes its own spp -- features converge with far fewer samples than
+ * radiance (1 to 16 is plenty) -- and ignores spp_chunk, max_depth, pipeline
+ * and the scheduling fields.  shard_count > 1 or packed: MCPT_E_UNSUPPORTED.
+ * A multi-device scene computes them on devices[0].  The scene's render stats
+ * are not touched.  The workspace is the scene's (the stack spill area a
+ * render of the same scene uses): after mcpt_scene_reserve(p) or a first call
+ * nothing is allocated.  Run it on the stream of the scene's renders, or
+ * synchronize: they share that workspace.                                   */
+int mcpt_render_aov(mcpt_scene* s, const mcpt_render_params* p, float* albedo_cov, float* normal_depth);
+/* The same on device buffers (4 floats per pixel each), asynchronous on hip_stream. */
+int mcpt_render_aov_device(mcpt_scene* s, const mcpt_render_params* p, float* d_albedo_cov, float* d_normal_depth,
+                           void* hip_stream);
+
+/* Edge-avoiding a-trous denoiser (Dammertz et al., HPG 2010) on
+ * albedo-demodulated colour, guided by the two feature buffers; fp32, a fixed
+ * operation order.  0 in a field = its default. */
+typedef struct {
+    int32_t width, height;
+    int32_t iterations;         /* a-trous passes, step 2^i; 0 = 5, at most 8 */
+    int32_t normal_power_log2;  /* normal weight = clamp(n.n', 0, 1)^(2^k); 0 = 7 (power 128), at most 10 */
+    float sigma_z;              /* relative depth tolerance; 0 = 0.1 */
+    float albedo_floor;         /* demodulation divides by max(albedo, floor); 0 = 0.01 */
+    int32_t gamma_space;        /* 1: colour is gamma-2.2 encoded (a QuinEngine-mode framebuffer):
+                                   decoded before, encoded after */
+} mcpt_denoise_params;
+/* the defaults spelled out (5, 7, 0.1, 0.01, linear colour); width and height 0 */
+void mcpt_denoise_params_default(mcpt_denoise_params* p);
+/* Host buffers, synchronous, on the current device: colour in and out 3 floats
+ * per pixel, features 4.  out_rgb may not overlap an input.                   */
+int mcpt_denoise(const mcpt_denoise_params* p, const float* color_rgb, const float* albedo_cov,
+                 const float* normal_depth, float* out_rgb);
+/* Device buffers of 4 floats per pixel, asynchronous on hip_stream, no
+ * allocation: d_color_rgba is only read (alpha ignored), d_out_rgba receives
+ * the result (alpha 0), d_scratch_rgba is a work buffer of the same size;
+ * neither may overlap another buffer of the call.                           */
+int mcpt_denoise_device(const mcpt_denoise_params* p, const float* d_color_rgba, const float* d_albedo_cov,
+                        const float* d_normal_depth, float* d_out_rgba, float* d_scratch_rgba, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,10 +11,12 @@ from ._capi import McptError, lib  # noqa: F401  (loads libmcpt.so, raises if mi
 from .imageio import read_pfm, read_png, write_pfm, write_png
 from .scenes import scene_path
 from .tracer import (ILLUM, IMG_HEIGHT, IMG_WIDTH, NUM_KERNELS, NUM_SAMPLES_PER_KERNEL, CreateGeometry,
-                     DestroyGeometry, Initialize, ObjModel, RenderParams, RenderScene, Scene, Tracer, encode_8bit)
+                     DestroyGeometry, Initialize, ObjModel, RenderParams, RenderScene, Scene, Tracer, denoise,
+                     denoise_device, denoise_params, encode_8bit)
 
 lib()
 
 __all__ = ["McptError", "ObjModel", "RenderParams", "Scene", "Tracer", "Initialize", "CreateGeometry",
            "DestroyGeometry", "RenderScene", "encode_8bit", "scene_path", "IMG_WIDTH", "IMG_HEIGHT",
-           "NUM_KERNELS", "NUM_SAMPLES_PER_KERNEL", "ILLUM", "write_png", "read_png", "write_pfm", "read_pfm"]
+           "NUM_KERNELS", "NUM_SAMPLES_PER_KERNEL", "ILLUM", "write_png", "read_png", "write_pfm", "read_pfm",
+           "denoise", "denoise_device", "denoise_params"]

@@ -91,6 +91,12 @@ class SceneOptions(C.Structure):
                 ("kd_build", C.c_int32)]
 
 
+class DenoiseParamsC(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32),
+                ("normal_power_log2", C.c_int32), ("sigma_z", C.c_float), ("albedo_floor", C.c_float),
+                ("gamma_space", C.c_int32)]
+
+
 OBJ_CVMCTRACER = 0
 OBJ_TINYOBJ = 1
 LAYOUT_AUTO = 0
@@ -148,6 +154,12 @@ _SIGS = {
     "mcpt_shard_pixels": (C.c_int, [C.POINTER(RenderParamsC), C.POINTER(C.c_int32)]),
     "mcpt_scene_reserve": (C.c_int, [_vp, C.POINTER(RenderParamsC)]),
     "mcpt_plan_query": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(PlanInfo)]),
+    "mcpt_render_aov": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mcpt_render_aov_device": (C.c_int, [_vp, C.POINTER(RenderParamsC), _vp, _vp, _vp]),
+    "mcpt_denoise_params_default": (None, [C.POINTER(DenoiseParamsC)]),
+    "mcpt_denoise": (C.c_int, [C.POINTER(DenoiseParamsC), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                               C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mcpt_denoise_device": (C.c_int, [C.POINTER(DenoiseParamsC), _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/mcpt.h"
+#include "aov_launch.hpp"
 #include "half_box.hpp"
 #include "host_model.hpp"
 #include "render_launch.hpp"
@@ -1054,6 +1055,62 @@ void upload(mcpt_scene& s, int device, const std::vector<unsigned char>& image, 
     s.gpu.normals = static_cast<const float4*>(s.d_normals);
 }
 
+// First-hit feature buffers (aov.hip) of p's frame into two device buffers of
+// 4 floats per pixel.  The only workspace is the scene's stack spill area,
+// sized by lanes exactly as a render's (prepare_workspace), so after a render,
+// a reserve or a first call nothing is allocated; no counter, event or stats
+// record of the scene is touched.
+void aov_async(mcpt_scene& s, const mcpt_render_params* p, float* d_ac, float* d_nd, hipStream_t st) {
+    if (!p) throw mcpt::Error{MCPT_E_INVALID, "params is NULL"};
+    if (!d_ac || !d_nd) throw mcpt::Error{MCPT_E_INVALID, "NULL feature buffer"};
+    if (d_ac == d_nd) throw mcpt::Error{MCPT_E_INVALID, "albedo_cov and normal_depth are the same buffer"};
+    if (p->width <= 0 || p->height <= 0) throw mcpt::Error{MCPT_E_INVALID, "width/height must be positive"};
+    if (p->spp == 0) throw mcpt::Error{MCPT_E_INVALID, "spp must be > 0"};
+    if (!s.on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
+    if (p->shard_count > 1 || p->packed)
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "feature buffers are not sharded: shard_count <= 1, packed = 0"};
+    set_device(s);                        // (a multi-device scene: devices[0], the primary)
+    mcpt_render_params q = *p;
+    q.spp_chunk = 0;                      // plain sums in sample order
+    q.tile = 8;                           // one wave per 8x8 tile
+    q.shard_count = 1; q.shard_index = 0;
+    q.pipeline = MCPT_PIPELINE_MEGAKERNEL;
+    q.max_depth = 0;
+    Plan pl = make_plan(s, &q);
+    pl.capturing = stream_capturing(st);
+    const size_t lanes = static_cast<size_t>(mcpt::total_lanes_for(s.gpu.image_bytes, s.cus));
+    grow_ws(s, s.ws.spill, s.ws.spill_bytes, 32 * lanes * 16, pl.capturing);
+    pl.kp.spill = static_cast<uint4*>(s.ws.spill);
+    pl.kp.total_lanes = static_cast<uint32_t>(lanes);
+    HIP_TRY(mcpt::launch_aov(pl.kp, reinterpret_cast<float4*>(d_ac), reinterpret_cast<float4*>(d_nd), st));
+}
+
+// mcpt_denoise_params with its zeros replaced by the defaults; throws on a bad field
+mcpt::DenoiseParams denoise_resolve(const mcpt_denoise_params* p) {
+    if (!p) throw mcpt::Error{MCPT_E_INVALID, "params is NULL"};
+    if (p->width <= 0 || p->height <= 0) throw mcpt::Error{MCPT_E_INVALID, "width/height must be positive"};
+    if (p->iterations < 0 || p->iterations > 8) throw mcpt::Error{MCPT_E_INVALID, "iterations must be 0 (default 5) or 1..8"};
+    if (p->normal_power_log2 < 0 || p->normal_power_log2 > 10)
+        throw mcpt::Error{MCPT_E_INVALID, "normal_power_log2 must be 0 (default 7) or 1..10"};
+    if (!(p->sigma_z >= 0.0f) || !std::isfinite(p->sigma_z) || !(p->albedo_floor >= 0.0f) || !std::isfinite(p->albedo_floor))
+        throw mcpt::Error{MCPT_E_INVALID, "sigma_z / albedo_floor must be finite and >= 0 (0 = default)"};
+    if (p->gamma_space != 0 && p->gamma_space != 1) throw mcpt::Error{MCPT_E_INVALID, "gamma_space must be 0 or 1"};
+    mcpt::DenoiseParams d;
+    d.width = p->width; d.height = p->height;
+    d.iterations = p->iterations ? p->iterations : 5;
+    d.normal_power_log2 = p->normal_power_log2 ? p->normal_power_log2 : 7;
+    d.sigma_z = p->sigma_z != 0.0f ? p->sigma_z : 0.1f;
+    d.albedo_floor = p->albedo_floor != 0.0f ? p->albedo_floor : 0.01f;
+    d.gamma_space = p->gamma_space;
+    return d;
+}
+
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + nb && y < x + na;
+}
+
+
 }  // namespace
 
 extern "C" {
@@ -1604,6 +1661,103 @@ int mcpt_plan_query(mcpt_scene* s, const mcpt_render_params* p, mcpt_plan_info* 
         r.devices = multi ? q.shard_count : 1;
         r.peer_access = s->peer_access ? 1 : 0;
         *out = r;
+        return MCPT_OK;
+    });
+}
+
+int mcpt_render_aov_device(mcpt_scene* s, const mcpt_render_params* p, float* d_albedo_cov, float* d_normal_depth,
+                           void* hip_stream) {
+    return guarded([&]() -> int {
+        if (!s) return fail(MCPT_E_INVALID, "NULL scene");
+        aov_async(*s, p, d_albedo_cov, d_normal_depth, static_cast<hipStream_t>(hip_stream));
+        return MCPT_OK;
+    });
+}
+
+int mcpt_render_aov(mcpt_scene* s, const mcpt_render_params* p, float* albedo_cov, float* normal_depth) {
+    return guarded([&]() -> int {
+        if (!s || !p || !albedo_cov || !normal_depth) return fail(MCPT_E_INVALID, "NULL argument");
+        if (albedo_cov == normal_depth) return fail(MCPT_E_INVALID, "albedo_cov and normal_depth are the same buffer");
+        if (p->width <= 0 || p->height <= 0) return fail(MCPT_E_INVALID, "width/height must be positive");
+        if (p->spp == 0) return fail(MCPT_E_INVALID, "spp must be > 0");
+        if (!s->on_device) return fail(MCPT_E_INVALID, "scene was created host-only");
+        if (p->shard_count > 1 || p->packed)
+            return fail(MCPT_E_UNSUPPORTED, "feature buffers are not sharded: shard_count <= 1, packed = 0");
+        set_device(*s);
+        // staging: both buffers in the scene's host-render framebuffer
+        const size_t bytes = size_t(p->width) * size_t(p->height) * 16;
+        ensure_buf(s->ws.fb, s->ws.fb_bytes, 2 * bytes);
+        float* d_ac = static_cast<float*>(s->ws.fb);
+        float* d_nd = d_ac + bytes / 4;
+        if (p->prev_count > 0) {
+            HIP_TRY(hipMemcpy(d_ac, albedo_cov, bytes, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_nd, normal_depth, bytes, hipMemcpyHostToDevice));
+        }
+        aov_async(*s, p, d_ac, d_nd, nullptr);
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        HIP_TRY(hipMemcpy(albedo_cov, d_ac, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(normal_depth, d_nd, bytes, hipMemcpyDeviceToHost));
+        return MCPT_OK;
+    });
+}
+
+void mcpt_denoise_params_default(mcpt_denoise_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof *p);
+    p->iterations = 5;
+    p->normal_power_log2 = 7;
+    p->sigma_z = 0.1f;
+    p->albedo_floor = 0.01f;
+}
+
+int mcpt_denoise_device(const mcpt_denoise_params* p, const float* d_color_rgba, const float* d_albedo_cov,
+                        const float* d_normal_depth, float* d_out_rgba, float* d_scratch_rgba, void* hip_stream) {
+    return guarded([&]() -> int {
+        if (!p || !d_color_rgba || !d_albedo_cov || !d_normal_depth || !d_out_rgba || !d_scratch_rgba)
+            return fail(MCPT_E_INVALID, "NULL argument");
+        const mcpt::DenoiseParams d = denoise_resolve(p);
+        const size_t bytes = size_t(d.width) * size_t(d.height) * 16;
+        const void* bufs[5] = {d_color_rgba, d_albedo_cov, d_normal_depth, d_out_rgba, d_scratch_rgba};
+        for (int i = 0; i < 5; ++i)
+            for (int j = std::max(i + 1, 3); j < 5; ++j)   // out and scratch against every other buffer
+                if (ranges_overlap(bufs[i], bytes, bufs[j], bytes))
+                    return fail(MCPT_E_INVALID, "the out / scratch buffer overlaps another buffer of the call");
+        HIP_TRY(mcpt::launch_denoise(d, reinterpret_cast<const float4*>(d_color_rgba),
+                                     reinterpret_cast<const float4*>(d_albedo_cov),
+                                     reinterpret_cast<const float4*>(d_normal_depth),
+                                     reinterpret_cast<float4*>(d_out_rgba), reinterpret_cast<float4*>(d_scratch_rgba),
+                                     static_cast<hipStream_t>(hip_stream)));
+        return MCPT_OK;
+    });
+}
+
+int mcpt_denoise(const mcpt_denoise_params* p, const float* color_rgb, const float* albedo_cov,
+                 const float* normal_depth, float* out_rgb) {
+    return guarded([&]() -> int {
+        if (!p || !color_rgb || !albedo_cov || !normal_depth || !out_rgb) return fail(MCPT_E_INVALID, "NULL argument");
+        const mcpt::DenoiseParams d = denoise_resolve(p);
+        const size_t npx = size_t(d.width) * size_t(d.height), bytes = npx * 16;
+        if (ranges_overlap(out_rgb, npx * 12, color_rgb, npx * 12) || ranges_overlap(out_rgb, npx * 12, albedo_cov, bytes) ||
+            ranges_overlap(out_rgb, npx * 12, normal_depth, bytes))
+            return fail(MCPT_E_INVALID, "out_rgb overlaps an input");
+        // one allocation: colour, albedo_cov, normal_depth, out, scratch
+        char* buf = nullptr;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), 5 * bytes));
+        struct Free { char* p; ~Free() { (void)hipFree(p); } } guard{buf};
+        std::vector<float> rgba(npx * 4, 0.0f);
+        for (size_t i = 0; i < npx; ++i)
+            for (int c = 0; c < 3; ++c) rgba[4 * i + c] = color_rgb[3 * i + c];
+        HIP_TRY(hipMemcpy(buf, rgba.data(), bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(buf + bytes, albedo_cov, bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(buf + 2 * bytes, normal_depth, bytes, hipMemcpyHostToDevice));
+        HIP_TRY(mcpt::launch_denoise(d, reinterpret_cast<const float4*>(buf), reinterpret_cast<const float4*>(buf + bytes),
+                                     reinterpret_cast<const float4*>(buf + 2 * bytes),
+                                     reinterpret_cast<float4*>(buf + 3 * bytes), reinterpret_cast<float4*>(buf + 4 * bytes),
+                                     nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        HIP_TRY(hipMemcpy(rgba.data(), buf + 3 * bytes, bytes, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < npx; ++i)
+            for (int c = 0; c < 3; ++c) out_rgb[3 * i + c] = rgba[4 * i + c];
         return MCPT_OK;
     });
 }

@@ -357,6 +357,28 @@ class Scene:
         check(lib().mcpt_render_device(self.handle, C.byref(params.to_c()), C.c_void_p(d_fb_rgba_ptr),
                                        C.c_void_p(stream_ptr)))
 
+    def render_aov(self, params: RenderParams, albedo_cov: Optional[np.ndarray] = None,
+                   normal_depth: Optional[np.ndarray] = None):
+        """First-hit feature buffers of the render's own primary rays (mcpt_render_aov):
+        (albedo_cov, normal_depth), float32 (H, W, 4) each -- r g b coverage and
+        nx ny nz t, means over ``params.spp`` samples (a few are plenty).  With
+        ``prev_count > 0`` the given buffers are blended in by the linear running mean."""
+        shape = (int(params.height), int(params.width), 4)
+        bufs = []
+        for a in (albedo_cov, normal_depth):
+            if a is None:
+                a = np.zeros(shape, np.float32)
+            if a.dtype != np.float32 or not a.flags.c_contiguous or a.size != shape[0] * shape[1] * 4:
+                raise McptError(-1, "feature buffers must be C-contiguous float32 arrays with 4 floats per pixel")
+            bufs.append(a)
+        check(lib().mcpt_render_aov(self.handle, C.byref(params.to_c()), _fptr(bufs[0]), _fptr(bufs[1])))
+        return bufs[0], bufs[1]
+
+    def render_aov_device(self, params: RenderParams, albedo_ptr: int, nd_ptr: int, stream_ptr: int = 0):
+        """Asynchronous feature buffers into two device RGBA float buffers (mcpt_render_aov_device)."""
+        check(lib().mcpt_render_aov_device(self.handle, C.byref(params.to_c()), C.c_void_p(albedo_ptr),
+                                           C.c_void_p(nd_ptr), C.c_void_p(stream_ptr)))
+
     def reserve(self, params: RenderParams):
         check(lib().mcpt_scene_reserve(self.handle, C.byref(params.to_c())))
 
@@ -371,6 +393,39 @@ class Scene:
         st = RenderStats()
         check(lib().mcpt_render_stats_read(self.handle, C.byref(st)))
         return st.as_dict()
+
+
+def denoise_params(width: int, height: int, iterations: int = 0, normal_power_log2: int = 0, sigma_z: float = 0.0,
+                   albedo_floor: float = 0.0, gamma_space: bool = False) -> "_capi.DenoiseParamsC":
+    """mcpt_denoise_params; 0 = the default (5 iterations, normal power 2^7, sigma_z 0.1, floor 0.01)."""
+    return _capi.DenoiseParamsC(int(width), int(height), int(iterations), int(normal_power_log2), float(sigma_z),
+                                float(albedo_floor), 1 if gamma_space else 0)
+
+
+def denoise(color: np.ndarray, albedo_cov: np.ndarray, normal_depth: np.ndarray, **params) -> np.ndarray:
+    """Edge-avoiding a-trous denoise of a host image on the current device (mcpt_denoise):
+    color (H, W, 3) float32, the two feature buffers (H, W, 4) of Scene.render_aov;
+    returns the filtered (H, W, 3) image.  params: the fields of denoise_params."""
+    color = np.ascontiguousarray(color, np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise McptError(-1, "color must be (H, W, 3)")
+    H, W = color.shape[:2]
+    a = np.ascontiguousarray(albedo_cov, np.float32)
+    n = np.ascontiguousarray(normal_depth, np.float32)
+    if a.size != H * W * 4 or n.size != H * W * 4:
+        raise McptError(-1, "feature buffers must hold 4 floats per pixel of color")
+    out = np.zeros((H, W, 3), np.float32)
+    check(lib().mcpt_denoise(C.byref(denoise_params(W, H, **params)), _fptr(color), _fptr(a), _fptr(n), _fptr(out)))
+    return out
+
+
+def denoise_device(width: int, height: int, color_ptr: int, albedo_ptr: int, nd_ptr: int, out_ptr: int,
+                   scratch_ptr: int, stream_ptr: int = 0, **params) -> None:
+    """Asynchronous denoise of device RGBA float buffers (mcpt_denoise_device): color is only
+    read, out receives the result, scratch is a work buffer of the same size."""
+    check(lib().mcpt_denoise_device(C.byref(denoise_params(width, height, **params)), C.c_void_p(color_ptr),
+                                    C.c_void_p(albedo_ptr), C.c_void_p(nd_ptr), C.c_void_p(out_ptr),
+                                    C.c_void_p(scratch_ptr), C.c_void_p(stream_ptr)))
 
 
 class Tracer:
