@@ -396,6 +396,49 @@ int mcpt_denoise(const mcpt_denoise_params* p, const float* color_rgb, const flo
 int mcpt_denoise_device(const mcpt_denoise_params* p, const float* d_color_rgba, const float* d_albedo_cov,
                         const float* d_normal_depth, float* d_out_rgba, float* d_scratch_rgba, void* hip_stream);
 
+/* ---- per-pixel variance and the variance-guided denoiser ------------------- */
+/* mcpt_render plus the variance of this call's pixel mean: the render of p
+ * (framebuffer, stats and counters bit-identical to mcpt_render's) followed by
+ * one kernel on the same stream that reads the per-chunk partial sums the
+ * render wrote.  var_rgba is row-major, 4 floats per pixel (var_r var_g var_b 0),
+ * linear radiance squared in both modes (the QuinEngine gamma applies to the
+ * framebuffer only).  A batch-means estimate over the K = ceil(spp / spp_chunk)
+ * chunks, fp32 in a fixed operation order:
+ *   mean = (P_0 + ... + P_K-1) / spp          P_c: chunk c's sum, n_c samples
+ *   var  = sum_c n_c (P_c / n_c - mean)^2 / (spp (K - 1))
+ * prev_count > 0: var = (old prev_count^2 + var) / (prev_count + 1)^2, the
+ * variance of the render's equal-weight running mean (the buffer is read).
+ * K < 2 (spp_chunk = 0 is one chunk): MCPT_E_INVALID.  shard_count > 1,
+ * packed, a multi-device scene or gather = RCCL: MCPT_E_UNSUPPORTED.  The
+ * variance step allocates nothing: after mcpt_scene_reserve(p) neither does
+ * mcpt_render_var_device.                                                   */
+int mcpt_render_var(mcpt_scene* s, const mcpt_render_params* p, float* fb_rgb, float* var_rgba,
+                    mcpt_render_stats* stats);
+/* The same on device buffers (4 floats per pixel each, not overlapping),
+ * asynchronous on hip_stream as mcpt_render_device.                          */
+int mcpt_render_var_device(mcpt_scene* s, const mcpt_render_params* p, float* d_fb_rgba, float* d_var_rgba,
+                           void* hip_stream);
+
+/* mcpt_denoise with an SVGF-style luminance edge-stopping weight (Schied et
+ * al., HPG 2017) driven by that variance, which is filtered along with the
+ * colour: a tap's weight is also multiplied by max(1 - |l_p - l_q| /
+ * (sigma_l sqrt(g_p) + 1e-6), 0)^2, l the luminance of the demodulated colour
+ * and g_p the 3x3-prefiltered luminance variance.     */
+typedef struct {
+    mcpt_denoise_params base;
+    float sigma_l;              /* luminance tolerance in standard deviations; 0 = 4 */
+} mcpt_denoise_var_params;
+/* mcpt_denoise_params_default for base, sigma_l 4 */
+void mcpt_denoise_var_params_default(mcpt_denoise_var_params* p);
+/* Buffers, overlap rules and checks as mcpt_denoise; var_rgba (4 floats per
+ * pixel, of mcpt_render_var, always linear) is one more read-only input.    */
+int mcpt_denoise_var(const mcpt_denoise_var_params* p, const float* color_rgb, const float* var_rgba,
+                     const float* albedo_cov, const float* normal_depth, float* out_rgb);
+/* As mcpt_denoise_device, with d_var_rgba one more read-only input.         */
+int mcpt_denoise_var_device(const mcpt_denoise_var_params* p, const float* d_color_rgba, const float* d_var_rgba,
+                            const float* d_albedo_cov, const float* d_normal_depth, float* d_out_rgba,
+                            float* d_scratch_rgba, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

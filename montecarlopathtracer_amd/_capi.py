@@ -97,6 +97,10 @@ class DenoiseParamsC(C.Structure):
                 ("gamma_space", C.c_int32)]
 
 
+class DenoiseVarParamsC(C.Structure):
+    _fields_ = [("base", DenoiseParamsC), ("sigma_l", C.c_float)]
+
+
 OBJ_CVMCTRACER = 0
 OBJ_TINYOBJ = 1
 LAYOUT_AUTO = 0
@@ -160,6 +164,13 @@ _SIGS = {
     "mcpt_denoise": (C.c_int, [C.POINTER(DenoiseParamsC), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mcpt_denoise_device": (C.c_int, [C.POINTER(DenoiseParamsC), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcpt_render_var": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                  C.POINTER(RenderStats)]),
+    "mcpt_render_var_device": (C.c_int, [_vp, C.POINTER(RenderParamsC), _vp, _vp, _vp]),
+    "mcpt_denoise_var_params_default": (None, [C.POINTER(DenoiseVarParamsC)]),
+    "mcpt_denoise_var": (C.c_int, [C.POINTER(DenoiseVarParamsC), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                   C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mcpt_denoise_var_device": (C.c_int, [C.POINTER(DenoiseVarParamsC), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

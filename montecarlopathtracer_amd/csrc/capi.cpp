@@ -24,6 +24,7 @@
 #include "half_box.hpp"
 #include "host_model.hpp"
 #include "render_launch.hpp"
+#include "variance_launch.hpp"
 
 struct mcpt_model {
     mcpt::ObjModel m;
@@ -817,8 +818,10 @@ void ensure_capture_timing(mcpt_scene& s) {
     s.has_capture_timing = true;
 }
 
+// d_var: also the per-pixel variance of this call's pixel mean (variance.hip),
+// from the partial sums the render's kernels wrote, behind them on st
 void render_async(mcpt_scene& s, const mcpt_render_params* p, float* d_fb, hipStream_t st,
-                  uint32_t* d_unit_counters = nullptr, bool raw_mean = false) {
+                  uint32_t* d_unit_counters = nullptr, bool raw_mean = false, float* d_var = nullptr) {
     if (!s.on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
     if (!d_fb) throw mcpt::Error{MCPT_E_INVALID, "framebuffer is NULL"};
     if (multi_device(s, p, d_unit_counters)) {
@@ -864,6 +867,7 @@ void render_async(mcpt_scene& s, const mcpt_render_params* p, float* d_fb, hipSt
         HIP_TRY(mcpt::launch_render(pl.kp, s.cus, st, t.e[0], t.e[1], t.e[2], reinterpret_cast<float4*>(d_fb),
                                     &s.last_variant));
     }
+    if (d_var) HIP_TRY(mcpt::launch_variance(pl.kp, reinterpret_cast<float4*>(d_var), st));
     if (pl.capturing) return;   // timed and counted when replayed, not now
     s.pending.push_back(t);
     s.renders++;
@@ -1108,6 +1112,34 @@ mcpt::DenoiseParams denoise_resolve(const mcpt_denoise_params* p) {
 bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return x < y + nb && y < x + na;
+}
+
+// What mcpt_render_var[_device] asks of a render beyond mcpt_render's own
+// checks; throws before anything is launched.  The variance is a batch-means
+// estimate over the render's chunks, so it needs at least two of them.
+void check_var_render(const mcpt_scene& s, const mcpt_render_params* p) {
+    if (!p) throw mcpt::Error{MCPT_E_INVALID, "params is NULL"};
+    if (p->width <= 0 || p->height <= 0) throw mcpt::Error{MCPT_E_INVALID, "width/height must be positive"};
+    if (p->spp == 0) throw mcpt::Error{MCPT_E_INVALID, "spp must be > 0"};
+    if (p->spp_chunk == 0 || p->spp_chunk >= p->spp)
+        throw mcpt::Error{MCPT_E_INVALID, "the variance needs at least two chunks: set spp_chunk to 1 .. spp - 1 "
+                                          "(spp_chunk = 0 is one chunk)"};
+    if (p->shard_count > 1 || p->packed)
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "the variance is not sharded: shard_count <= 1, packed = 0"};
+    if (!s.replicas.empty() || p->gather == MCPT_GATHER_RCCL)
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "the variance needs a one-device scene and the peer gather"};
+    if (!s.on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
+}
+
+// mcpt_denoise_var_params resolved as denoise_resolve does; sigma_l 0 = 4
+mcpt::DenoiseVarParams denoise_var_resolve(const mcpt_denoise_var_params* p) {
+    if (!p) throw mcpt::Error{MCPT_E_INVALID, "params is NULL"};
+    mcpt::DenoiseVarParams d;
+    d.base = denoise_resolve(&p->base);
+    if (!(p->sigma_l >= 0.0f) || !std::isfinite(p->sigma_l))
+        throw mcpt::Error{MCPT_E_INVALID, "sigma_l must be finite and >= 0 (0 = default)"};
+    d.sigma_l = p->sigma_l != 0.0f ? p->sigma_l : 4.0f;
+    return d;
 }
 
 
@@ -1444,15 +1476,20 @@ int mcpt_render_stats_read(mcpt_scene* s, mcpt_render_stats* out) {
     });
 }
 
+// var_rgba: mcpt_render_var -- the variance buffer (4 floats per pixel) is
+// staged behind the framebuffer in the scene's host-render buffer
 static int render_sync(mcpt_scene* s, const mcpt_render_params* p, float* fb_rgb, mcpt_render_stats* stats,
-                       uint32_t* unit_counters) {
+                       uint32_t* unit_counters, float* var_rgba = nullptr) {
     return guarded([&]() -> int {
         if (!s || !fb_rgb) return fail(MCPT_E_INVALID, "NULL argument");
+        if (var_rgba) check_var_render(*s, p);
         if (!s->on_device) return fail(MCPT_E_INVALID, "scene was created host-only");
         set_device(*s);
         Plan pl = make_plan(*s, p);
         const size_t npx = pl.out_pixels;
-        ensure_buf(s->ws.fb, s->ws.fb_bytes, npx * 16);
+        ensure_buf(s->ws.fb, s->ws.fb_bytes, npx * (var_rgba ? 32 : 16));
+        float* d_var = var_rgba ? static_cast<float*>(s->ws.fb) + npx * 4 : nullptr;
+        if (var_rgba && p->prev_count > 0) HIP_TRY(hipMemcpy(d_var, var_rgba, npx * 16, hipMemcpyHostToDevice));
         std::vector<float> rgba(npx * 4, 0.0f);
         if (p->prev_count > 0) {
             for (size_t i = 0; i < npx; ++i)
@@ -1468,8 +1505,9 @@ static int render_sync(mcpt_scene* s, const mcpt_render_params* p, float* fb_rgb
             HIP_TRY(hipMalloc(&d_uc, uc_bytes ? uc_bytes : 16));
             HIP_TRY(hipMemset(d_uc, 0, uc_bytes ? uc_bytes : 16));
         }
-        render_async(*s, p, static_cast<float*>(s->ws.fb), nullptr, static_cast<uint32_t*>(d_uc));
+        render_async(*s, p, static_cast<float*>(s->ws.fb), nullptr, static_cast<uint32_t*>(d_uc), false, d_var);
         HIP_TRY(hipStreamSynchronize(nullptr));
+        if (var_rgba) HIP_TRY(hipMemcpy(var_rgba, d_var, npx * 16, hipMemcpyDeviceToHost));
         if (unit_counters) {
             HIP_TRY(hipMemcpy(unit_counters, d_uc, uc_bytes, hipMemcpyDeviceToHost));
             HIP_TRY(hipFree(d_uc));
@@ -1756,6 +1794,92 @@ int mcpt_denoise(const mcpt_denoise_params* p, const float* color_rgb, const flo
                                      nullptr));
         HIP_TRY(hipStreamSynchronize(nullptr));
         HIP_TRY(hipMemcpy(rgba.data(), buf + 3 * bytes, bytes, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < npx; ++i)
+            for (int c = 0; c < 3; ++c) out_rgb[3 * i + c] = rgba[4 * i + c];
+        return MCPT_OK;
+    });
+}
+
+int mcpt_render_var_device(mcpt_scene* s, const mcpt_render_params* p, float* d_fb_rgba, float* d_var_rgba,
+                           void* hip_stream) {
+    return guarded([&]() -> int {
+        if (!s) return fail(MCPT_E_INVALID, "NULL scene");
+        if (!d_fb_rgba || !d_var_rgba) return fail(MCPT_E_INVALID, "NULL framebuffer or variance buffer");
+        if (p && p->width > 0 && p->height > 0) {
+            const size_t bytes = size_t(p->width) * size_t(p->height) * 16;
+            if (ranges_overlap(d_fb_rgba, bytes, d_var_rgba, bytes))
+                return fail(MCPT_E_INVALID, "the framebuffer and the variance buffer overlap");
+        }
+        check_var_render(*s, p);
+        render_async(*s, p, d_fb_rgba, static_cast<hipStream_t>(hip_stream), nullptr, false, d_var_rgba);
+        return MCPT_OK;
+    });
+}
+
+int mcpt_render_var(mcpt_scene* s, const mcpt_render_params* p, float* fb_rgb, float* var_rgba,
+                    mcpt_render_stats* stats) {
+    if (!var_rgba) return fail(MCPT_E_INVALID, "NULL argument");
+    return render_sync(s, p, fb_rgb, stats, nullptr, var_rgba);
+}
+
+void mcpt_denoise_var_params_default(mcpt_denoise_var_params* p) {
+    if (!p) return;
+    mcpt_denoise_params_default(&p->base);
+    p->sigma_l = 4.0f;
+}
+
+int mcpt_denoise_var_device(const mcpt_denoise_var_params* p, const float* d_color_rgba, const float* d_var_rgba,
+                            const float* d_albedo_cov, const float* d_normal_depth, float* d_out_rgba,
+                            float* d_scratch_rgba, void* hip_stream) {
+    return guarded([&]() -> int {
+        if (!p || !d_color_rgba || !d_var_rgba || !d_albedo_cov || !d_normal_depth || !d_out_rgba || !d_scratch_rgba)
+            return fail(MCPT_E_INVALID, "NULL argument");
+        const mcpt::DenoiseVarParams d = denoise_var_resolve(p);
+        const size_t bytes = size_t(d.base.width) * size_t(d.base.height) * 16;
+        const void* bufs[6] = {d_color_rgba, d_var_rgba, d_albedo_cov, d_normal_depth, d_out_rgba, d_scratch_rgba};
+        for (int i = 0; i < 6; ++i)
+            for (int j = std::max(i + 1, 4); j < 6; ++j)   // out and scratch against every other buffer
+                if (ranges_overlap(bufs[i], bytes, bufs[j], bytes))
+                    return fail(MCPT_E_INVALID, "the out / scratch buffer overlaps another buffer of the call");
+        HIP_TRY(mcpt::launch_denoise_var(d, reinterpret_cast<const float4*>(d_color_rgba),
+                                         reinterpret_cast<const float4*>(d_var_rgba),
+                                         reinterpret_cast<const float4*>(d_albedo_cov),
+                                         reinterpret_cast<const float4*>(d_normal_depth),
+                                         reinterpret_cast<float4*>(d_out_rgba),
+                                         reinterpret_cast<float4*>(d_scratch_rgba), static_cast<hipStream_t>(hip_stream)));
+        return MCPT_OK;
+    });
+}
+
+int mcpt_denoise_var(const mcpt_denoise_var_params* p, const float* color_rgb, const float* var_rgba,
+                     const float* albedo_cov, const float* normal_depth, float* out_rgb) {
+    return guarded([&]() -> int {
+        if (!p || !color_rgb || !var_rgba || !albedo_cov || !normal_depth || !out_rgb)
+            return fail(MCPT_E_INVALID, "NULL argument");
+        const mcpt::DenoiseVarParams d = denoise_var_resolve(p);
+        const size_t npx = size_t(d.base.width) * size_t(d.base.height), bytes = npx * 16;
+        if (ranges_overlap(out_rgb, npx * 12, color_rgb, npx * 12) || ranges_overlap(out_rgb, npx * 12, var_rgba, bytes) ||
+            ranges_overlap(out_rgb, npx * 12, albedo_cov, bytes) || ranges_overlap(out_rgb, npx * 12, normal_depth, bytes))
+            return fail(MCPT_E_INVALID, "out_rgb overlaps an input");
+        // one allocation: colour, variance, albedo_cov, normal_depth, out, scratch
+        char* buf = nullptr;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), 6 * bytes));
+        struct Free { char* p; ~Free() { (void)hipFree(p); } } guard{buf};
+        std::vector<float> rgba(npx * 4, 0.0f);
+        for (size_t i = 0; i < npx; ++i)
+            for (int c = 0; c < 3; ++c) rgba[4 * i + c] = color_rgb[3 * i + c];
+        HIP_TRY(hipMemcpy(buf, rgba.data(), bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(buf + bytes, var_rgba, bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(buf + 2 * bytes, albedo_cov, bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(buf + 3 * bytes, normal_depth, bytes, hipMemcpyHostToDevice));
+        HIP_TRY(mcpt::launch_denoise_var(d, reinterpret_cast<const float4*>(buf),
+                                         reinterpret_cast<const float4*>(buf + bytes),
+                                         reinterpret_cast<const float4*>(buf + 2 * bytes),
+                                         reinterpret_cast<const float4*>(buf + 3 * bytes),
+                                         reinterpret_cast<float4*>(buf + 4 * bytes),
+                                         reinterpret_cast<float4*>(buf + 5 * bytes), nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        HIP_TRY(hipMemcpy(rgba.data(), buf + 4 * bytes, bytes, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < npx; ++i)
             for (int c = 0; c < 3; ++c) out_rgb[3 * i + c] = rgba[4 * i + c];
         return MCPT_OK;

@@ -379,6 +379,29 @@ class Scene:
         check(lib().mcpt_render_aov_device(self.handle, C.byref(params.to_c()), C.c_void_p(albedo_ptr),
                                            C.c_void_p(nd_ptr), C.c_void_p(stream_ptr)))
 
+    def render_var(self, params: RenderParams, fb: Optional[np.ndarray] = None, var: Optional[np.ndarray] = None):
+        """``render`` plus the per-pixel variance of this call's pixel mean (mcpt_render_var):
+        (fb (H, W, 3), var (H, W, 4) = var_r var_g var_b 0, stats).  A batch-means estimate
+        over the render's chunks, so ``spp_chunk`` must cut ``spp`` into at least two; linear
+        radiance squared in both modes.  With ``prev_count > 0`` the given buffers are blended in."""
+        H, W = int(params.height), int(params.width)
+        if fb is None:
+            fb = np.zeros((H, W, 3), np.float32)
+        if var is None:
+            var = np.zeros((H, W, 4), np.float32)
+        if fb.dtype != np.float32 or not fb.flags.c_contiguous or fb.size != 3 * H * W:
+            raise McptError(-1, "fb must be a C-contiguous float32 array with 3 floats per pixel")
+        if var.dtype != np.float32 or not var.flags.c_contiguous or var.size != 4 * H * W:
+            raise McptError(-1, "var must be a C-contiguous float32 array with 4 floats per pixel")
+        st = RenderStats()
+        check(lib().mcpt_render_var(self.handle, C.byref(params.to_c()), _fptr(fb), _fptr(var), C.byref(st)))
+        return fb, var, st.as_dict()
+
+    def render_var_device(self, params: RenderParams, d_fb_rgba_ptr: int, d_var_rgba_ptr: int, stream_ptr: int = 0):
+        """Asynchronous render and variance into two device RGBA float buffers (mcpt_render_var_device)."""
+        check(lib().mcpt_render_var_device(self.handle, C.byref(params.to_c()), C.c_void_p(d_fb_rgba_ptr),
+                                           C.c_void_p(d_var_rgba_ptr), C.c_void_p(stream_ptr)))
+
     def reserve(self, params: RenderParams):
         check(lib().mcpt_scene_reserve(self.handle, C.byref(params.to_c())))
 
@@ -426,6 +449,41 @@ def denoise_device(width: int, height: int, color_ptr: int, albedo_ptr: int, nd_
     check(lib().mcpt_denoise_device(C.byref(denoise_params(width, height, **params)), C.c_void_p(color_ptr),
                                     C.c_void_p(albedo_ptr), C.c_void_p(nd_ptr), C.c_void_p(out_ptr),
                                     C.c_void_p(scratch_ptr), C.c_void_p(stream_ptr)))
+
+
+def denoise_var_params(width: int, height: int, sigma_l: float = 0.0, **params) -> "_capi.DenoiseVarParamsC":
+    """mcpt_denoise_var_params: the fields of denoise_params and sigma_l (0 = the default, 4)."""
+    return _capi.DenoiseVarParamsC(denoise_params(width, height, **params), float(sigma_l))
+
+
+def denoise_var(color: np.ndarray, variance: np.ndarray, albedo_cov: np.ndarray, normal_depth: np.ndarray,
+                **params) -> np.ndarray:
+    """Variance-guided a-trous denoise of a host image on the current device (mcpt_denoise_var):
+    color (H, W, 3) float32, variance (H, W, 4) of Scene.render_var, the two feature buffers
+    (H, W, 4) of Scene.render_aov; returns the filtered (H, W, 3) image.  params: the fields of
+    denoise_var_params."""
+    color = np.ascontiguousarray(color, np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise McptError(-1, "color must be (H, W, 3)")
+    H, W = color.shape[:2]
+    v = np.ascontiguousarray(variance, np.float32)
+    a = np.ascontiguousarray(albedo_cov, np.float32)
+    n = np.ascontiguousarray(normal_depth, np.float32)
+    if v.size != H * W * 4 or a.size != H * W * 4 or n.size != H * W * 4:
+        raise McptError(-1, "the variance and feature buffers must hold 4 floats per pixel of color")
+    out = np.zeros((H, W, 3), np.float32)
+    check(lib().mcpt_denoise_var(C.byref(denoise_var_params(W, H, **params)), _fptr(color), _fptr(v), _fptr(a),
+                                 _fptr(n), _fptr(out)))
+    return out
+
+
+def denoise_var_device(width: int, height: int, color_ptr: int, var_ptr: int, albedo_ptr: int, nd_ptr: int,
+                       out_ptr: int, scratch_ptr: int, stream_ptr: int = 0, **params) -> None:
+    """Asynchronous variance-guided denoise of device RGBA float buffers (mcpt_denoise_var_device):
+    color and variance are only read, out receives the result, scratch is a work buffer of the same size."""
+    check(lib().mcpt_denoise_var_device(C.byref(denoise_var_params(width, height, **params)), C.c_void_p(color_ptr),
+                                        C.c_void_p(var_ptr), C.c_void_p(albedo_ptr), C.c_void_p(nd_ptr),
+                                        C.c_void_p(out_ptr), C.c_void_p(scratch_ptr), C.c_void_p(stream_ptr)))
 
 
 class Tracer:
