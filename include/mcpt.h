@@ -439,6 +439,53 @@ int mcpt_denoise_var_device(const mcpt_denoise_var_params* p, const float* d_col
                             const float* d_albedo_cov, const float* d_normal_depth, float* d_out_rgba,
                             float* d_scratch_rgba, void* hip_stream);
 
+/* ---- variance-driven adaptive sampling -------------------------------------- */
+/* Passes of p->spp samples, each pass only over the pixels that are still
+ * noisy.  Pass 0 is mcpt_render_var of p for every pixel.  Before pass j >= 1
+ * every pixel gets, from the current framebuffer and variance (fp32, one
+ * rounding per operation; k = (0.2126, 0.7152, 0.0722)),
+ *   sd_c = sqrt(max(var_c, 0))
+ *   s    = (k.x sd_r + k.y sd_g) + k.z sd_b
+ *   l    = (k.x fb_r + k.y fb_g) + k.z fb_b
+ *   over = s > threshold (l + lum_floor)
+ * and pass j renders the pixels that were active in pass j - 1 and have an
+ * `over` pixel in their (2r+1)^2 window (clipped to the image); for
+ * j < min_passes, and as the predecessor of pass min_passes, every pixel is
+ * active.  A pixel that stopped never restarts; an empty set ends the render.
+ * The active pixels are rendered as a uniform mcpt_render_var with
+ * spp_offset + j spp and prev_count = j renders them (same chunks, partial
+ * sums, running mean and variance merge), so a pixel with pass_count m holds,
+ * bit for bit, what m chained uniform mcpt_render_var calls leave in it, and
+ * the counters are the sums over the pixels rendered.
+ * The pixel list is built on the device (selection, per-block ballot counts,
+ * scan, scatter in tile-major order); the host reads its length once per pass. */
+typedef struct {
+    int32_t max_passes;   /* passes of p->spp samples a pixel can get; 0 = 8; 1..4096 */
+    int32_t min_passes;   /* passes every pixel gets before selection starts; 0 = 1; <= max_passes */
+    float   threshold;    /* stop a pixel when the standard error of its luminance <= threshold * (luminance + lum_floor); 0 = 0.2; >= 0 */
+    float   lum_floor;    /* 0 = 0.01; >= 0 */
+    int32_t dilate;       /* radius r of the (2r+1)^2 window over which "still noisy" spreads; 0 = 1; < 0 = none; at most 4 */
+    int32_t force_list;   /* 1: full-frame passes after pass 0 also run through the pixel list (measures the list's overhead; same result) */
+} mcpt_adaptive_params;
+/* max_passes 8, min_passes 1, threshold 0.2, lum_floor 0.01, dilate 1, force_list 0 */
+void mcpt_adaptive_params_default(mcpt_adaptive_params*);
+/* fb_rgb: 3 floats per pixel; var_rgba: 4; pass_count: one uint32 per pixel
+ * (all row-major, written only).  stats: counters summed over the passes,
+ * renders = passes run.  a may be NULL (the defaults).  MCPT_E_INVALID:
+ * whatever mcpt_render_var rejects, prev_count != 0, spp_offset +
+ * max_passes * spp past 2^32, an adaptive field out of range.
+ * MCPT_E_UNSUPPORTED: whatever mcpt_render_var refuses, the wavefront
+ * pipeline, QuinEngine mode, a capturing stream (the host reads the list's
+ * length each pass).  All checks come before any launch.                     */
+int mcpt_render_adaptive(mcpt_scene*, const mcpt_render_params*, const mcpt_adaptive_params*,
+                         float* fb_rgb, float* var_rgba, uint32_t* pass_count, mcpt_render_stats* stats);
+/* The same on device buffers (4 floats per pixel for d_fb_rgba and d_var_rgba,
+ * none overlapping).  The call waits for hip_stream once per selecting pass;
+ * the last pass is left running on it.  After mcpt_scene_reserve(p) and one
+ * call a further call allocates nothing.                                      */
+int mcpt_render_adaptive_device(mcpt_scene*, const mcpt_render_params*, const mcpt_adaptive_params*,
+                                float* d_fb_rgba, float* d_var_rgba, uint32_t* d_pass_count, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,8 @@ from ._capi import McptError, lib  # noqa: F401  (loads libmcpt.so, raises if mi
 from .imageio import read_pfm, read_png, write_pfm, write_png
 from .scenes import scene_path
 from .tracer import (ILLUM, IMG_HEIGHT, IMG_WIDTH, NUM_KERNELS, NUM_SAMPLES_PER_KERNEL, CreateGeometry,
-                     DestroyGeometry, Initialize, ObjModel, RenderParams, RenderScene, Scene, Tracer, denoise,
+                     DestroyGeometry, Initialize, ObjModel, RenderParams, RenderScene, Scene, Tracer,
+                     adaptive_params, denoise,
                      denoise_device, denoise_params, denoise_var, denoise_var_device, denoise_var_params,
                      encode_8bit)
 
@@ -20,4 +21,5 @@ lib()
 __all__ = ["McptError", "ObjModel", "RenderParams", "Scene", "Tracer", "Initialize", "CreateGeometry",
            "DestroyGeometry", "RenderScene", "encode_8bit", "scene_path", "IMG_WIDTH", "IMG_HEIGHT",
            "NUM_KERNELS", "NUM_SAMPLES_PER_KERNEL", "ILLUM", "write_png", "read_png", "write_pfm", "read_pfm",
-           "denoise", "denoise_device", "denoise_params", "denoise_var", "denoise_var_device", "denoise_var_params"]
+           "denoise", "denoise_device", "denoise_params", "denoise_var", "denoise_var_device", "denoise_var_params",
+           "adaptive_params"]

@@ -101,6 +101,11 @@ class DenoiseVarParamsC(C.Structure):
     _fields_ = [("base", DenoiseParamsC), ("sigma_l", C.c_float)]
 
 
+class AdaptiveParamsC(C.Structure):
+    _fields_ = [("max_passes", C.c_int32), ("min_passes", C.c_int32), ("threshold", C.c_float),
+                ("lum_floor", C.c_float), ("dilate", C.c_int32), ("force_list", C.c_int32)]
+
+
 OBJ_CVMCTRACER = 0
 OBJ_TINYOBJ = 1
 LAYOUT_AUTO = 0
@@ -171,6 +176,12 @@ _SIGS = {
     "mcpt_denoise_var": (C.c_int, [C.POINTER(DenoiseVarParamsC), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                    C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mcpt_denoise_var_device": (C.c_int, [C.POINTER(DenoiseVarParamsC), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcpt_adaptive_params_default": (None, [C.POINTER(AdaptiveParamsC)]),
+    "mcpt_render_adaptive": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(AdaptiveParamsC),
+                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                       C.POINTER(RenderStats)]),
+    "mcpt_render_adaptive_device": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(AdaptiveParamsC), _vp, _vp,
+                                              _vp, _vp]),
 }
 
 _lib = None

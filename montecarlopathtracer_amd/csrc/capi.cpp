@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/mcpt.h"
+#include "adaptive_launch.hpp"
 #include "aov_launch.hpp"
 #include "half_box.hpp"
 #include "host_model.hpp"
@@ -205,6 +206,16 @@ struct mcpt_scene {
     std::vector<ncclComm_t> comms;
     void* gather_send = nullptr;
     size_t gather_send_bytes = 0;
+    // adaptive sampling (mcpt_render_adaptive): the pixel list, the `over` flags,
+    // the compaction's block counts and wave ballots, and the pinned word the
+    // list's length is copied to each pass
+    void* ad_list = nullptr;
+    size_t ad_list_bytes = 0;
+    void* ad_flags = nullptr;
+    size_t ad_flags_bytes = 0;
+    void* ad_blocks = nullptr;
+    size_t ad_blocks_bytes = 0;
+    uint32_t* ad_host_n = nullptr;
 
     ~mcpt_scene() {
         if (!on_device) return;
@@ -220,8 +231,10 @@ struct mcpt_scene {
             for (ncclComm_t c : comms) (void)rccl().comm_destroy(c);
             (void)hipSetDevice(device);
         }
-        for (void* p : {d_image, d_normals, ws.partial, ws.small, ws.spill, ws.fb, ws.wf, ws.tail, gather, gather_send})
+        for (void* p : {d_image, d_normals, ws.partial, ws.small, ws.spill, ws.fb, ws.wf, ws.tail, gather, gather_send, ad_list, ad_flags,
+                        ad_blocks})
             if (p) (void)hipFree(p);
+        if (ad_host_n) (void)hipHostFree(ad_host_n);
         for (void* p : retired) (void)hipFree(p);
         for (auto& t : pending) for (auto ev : t.e) (void)hipEventDestroy(ev);
         for (auto& t : free_timing) for (auto ev : t.e) (void)hipEventDestroy(ev);
@@ -1117,7 +1130,7 @@ bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
 // What mcpt_render_var[_device] asks of a render beyond mcpt_render's own
 // checks; throws before anything is launched.  The variance is a batch-means
 // estimate over the render's chunks, so it needs at least two of them.
-void check_var_render(const mcpt_scene& s, const mcpt_render_params* p) {
+void check_var_params(const mcpt_scene& s, const mcpt_render_params* p) {
     if (!p) throw mcpt::Error{MCPT_E_INVALID, "params is NULL"};
     if (p->width <= 0 || p->height <= 0) throw mcpt::Error{MCPT_E_INVALID, "width/height must be positive"};
     if (p->spp == 0) throw mcpt::Error{MCPT_E_INVALID, "spp must be > 0"};
@@ -1128,6 +1141,9 @@ void check_var_render(const mcpt_scene& s, const mcpt_render_params* p) {
         throw mcpt::Error{MCPT_E_UNSUPPORTED, "the variance is not sharded: shard_count <= 1, packed = 0"};
     if (!s.replicas.empty() || p->gather == MCPT_GATHER_RCCL)
         throw mcpt::Error{MCPT_E_UNSUPPORTED, "the variance needs a one-device scene and the peer gather"};
+}
+void check_var_render(const mcpt_scene& s, const mcpt_render_params* p) {
+    check_var_params(s, p);
     if (!s.on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
 }
 
@@ -1140,6 +1156,126 @@ mcpt::DenoiseVarParams denoise_var_resolve(const mcpt_denoise_var_params* p) {
         throw mcpt::Error{MCPT_E_INVALID, "sigma_l must be finite and >= 0 (0 = default)"};
     d.sigma_l = p->sigma_l != 0.0f ? p->sigma_l : 4.0f;
     return d;
+}
+
+// mcpt_adaptive_params with every default resolved (NULL: all defaults)
+struct Adaptive {
+    int32_t max_passes, min_passes, radius;
+    float threshold, lum_floor;
+    bool force_list;
+};
+Adaptive adaptive_resolve(const mcpt_adaptive_params* p) {
+    mcpt_adaptive_params z;
+    std::memset(&z, 0, sizeof z);
+    if (!p) p = &z;
+    if (p->max_passes < 0 || p->max_passes > 4096)
+        throw mcpt::Error{MCPT_E_INVALID, "max_passes must be 0 (default 8) or 1..4096"};
+    Adaptive a;
+    a.max_passes = p->max_passes ? p->max_passes : 8;
+    if (p->min_passes < 0 || p->min_passes > a.max_passes)
+        throw mcpt::Error{MCPT_E_INVALID, "min_passes must be 0 (default 1) or 1..max_passes"};
+    a.min_passes = p->min_passes ? p->min_passes : 1;
+    if (!(p->threshold >= 0.0f) || !std::isfinite(p->threshold))
+        throw mcpt::Error{MCPT_E_INVALID, "threshold must be finite and >= 0 (0 = default 0.2)"};
+    a.threshold = p->threshold != 0.0f ? p->threshold : 0.2f;
+    if (!(p->lum_floor >= 0.0f) || !std::isfinite(p->lum_floor))
+        throw mcpt::Error{MCPT_E_INVALID, "lum_floor must be finite and >= 0 (0 = default 0.01)"};
+    a.lum_floor = p->lum_floor != 0.0f ? p->lum_floor : 0.01f;
+    if (p->dilate > 4) throw mcpt::Error{MCPT_E_INVALID, "dilate must be at most 4 (0 = default 1, < 0 = none)"};
+    a.radius = p->dilate == 0 ? 1 : (p->dilate < 0 ? 0 : p->dilate);
+    if (p->force_list != 0 && p->force_list != 1) throw mcpt::Error{MCPT_E_INVALID, "force_list must be 0 or 1"};
+    a.force_list = p->force_list == 1;
+    return a;
+}
+
+// What mcpt_render_adaptive[_device] asks beyond mcpt_render_var; throws
+// before anything is launched.
+void check_adaptive_render(const mcpt_scene& s, const mcpt_render_params* p, const Adaptive& a, hipStream_t st) {
+    check_var_params(s, p);
+    (void)make_plan(s, p);   // mcpt_render's own argument checks
+    if (p->prev_count != 0)
+        throw mcpt::Error{MCPT_E_INVALID, "prev_count must be 0: an adaptive render starts its own running mean"};
+    if (uint64_t(p->spp_offset) + uint64_t(a.max_passes) * uint64_t(p->spp) > (uint64_t(1) << 32))
+        throw mcpt::Error{MCPT_E_INVALID, "spp_offset + max_passes * spp passes 2^32 sample indices"};
+    if (p->pipeline != MCPT_PIPELINE_MEGAKERNEL)
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "pipeline: adaptive sampling runs on the megakernel only"};
+    if (p->mode != MCPT_MODE_CVMCTRACER)
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "mode: adaptive sampling selects in linear radiance, CVMCTracer mode only"};
+    if (!s.on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
+    if (stream_capturing(st))
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "hip_stream is capturing a graph: the host reads the pixel list's "
+                                              "length each pass"};
+}
+
+// The passes of an adaptive render on st (arguments checked).  The host waits
+// for st once per listed pass, for the list's length; the last pass is left
+// running.
+void adaptive_async(mcpt_scene& s, const mcpt_render_params* p, const Adaptive& a, float* d_fb, float* d_var,
+                    uint32_t* d_count, hipStream_t st) {
+    set_device(s);
+    const Plan full = make_plan(s, p);
+    const size_t npx = size_t(p->width) * size_t(p->height);
+    const uint32_t npix = full.kp.npix_local, nb = mcpt::adaptive_blocks(npix);
+    mcpt::AdaptiveWs aw{};
+    if (a.max_passes > 1) {
+        const size_t counts = (size_t(nb) + 1 + 1) / 2 * 8;   // nb + 1 words, the ballots 8-B aligned behind them
+        grow_ws(s, s.ad_list, s.ad_list_bytes, size_t(npix) * 4, false);
+        grow_ws(s, s.ad_flags, s.ad_flags_bytes, npx * 4, false);
+        grow_ws(s, s.ad_blocks, s.ad_blocks_bytes, counts + size_t(nb) * (mcpt::kAdaptiveBlock / 64) * 8, false);
+        if (!s.ad_host_n) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s.ad_host_n), 64, hipHostMallocDefault));
+        aw.list = static_cast<uint32_t*>(s.ad_list);
+        aw.flags = static_cast<uint32_t*>(s.ad_flags);
+        aw.blocks = static_cast<uint32_t*>(s.ad_blocks);
+        aw.masks = reinterpret_cast<unsigned long long*>(static_cast<char*>(s.ad_blocks) + counts);
+    }
+    float4* fb = reinterpret_cast<float4*>(d_fb);
+    float4* var = reinterpret_cast<float4*>(d_var);
+    render_async(s, p, d_fb, st, nullptr, false, d_var);   // pass 0: every pixel
+    HIP_TRY(mcpt::launch_adaptive_fill(d_count, npx, 1u, st));
+    for (int32_t j = 1; j < a.max_passes; ++j) {
+        mcpt_render_params pj = *p;
+        pj.spp_offset = p->spp_offset + uint32_t(j) * p->spp;
+        pj.prev_count = uint32_t(j);
+        const bool all = j < a.min_passes;
+        if (all && !a.force_list) {   // a uniform pass as it is
+            render_async(s, &pj, d_fb, st, nullptr, false, d_var);
+            HIP_TRY(mcpt::launch_adaptive_fill(d_count, npx, uint32_t(j) + 1u, st));
+            continue;
+        }
+        mcpt::AdaptiveSelect sel;
+        sel.threshold = a.threshold;
+        sel.lum_floor = a.lum_floor;
+        sel.radius = a.radius;
+        sel.pass = uint32_t(j);
+        sel.all = all ? 1 : 0;
+        HIP_TRY(mcpt::launch_adaptive_select(full.kp, sel, aw, fb, var, d_count, st));
+        HIP_TRY(hipMemcpyAsync(s.ad_host_n, aw.blocks + nb, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const uint32_t n = *s.ad_host_n;
+        if (!n) break;
+        if (n > npix) throw mcpt::Error{MCPT_E_DEVICE, "adaptive pixel list longer than the frame"};
+        // a frame of n listed pixels: the unit decode, tail split and partial-sum
+        // layout are the megakernel's own, over n pixels instead of npix_local
+        Plan pl = make_plan(s, &pj);
+        mcpt::KernelParams& k = pl.kp;
+        k.npix_local = n;
+        k.total_units = n * k.nchunks;
+        k.div_npix = mcpt::FastDiv::make(n);
+        prepare_workspace(s, pl, true);
+        k.pixel_list = aw.list;
+        Timing t;
+        if (!s.free_timing.empty()) {
+            t = s.free_timing.back();
+            s.free_timing.pop_back();
+        } else {
+            for (auto& ev : t.e) HIP_TRY(hipEventCreate(&ev));
+        }
+        HIP_TRY(mcpt::launch_render_list(k, s.cus, st, t.e[0], t.e[1], &s.last_variant));
+        HIP_TRY(mcpt::launch_adaptive_merge(k, fb, var, d_count, st));
+        HIP_TRY(hipEventRecord(t.e[2], st));
+        s.pending.push_back(t);
+        s.renders++;
+    }
 }
 
 
@@ -1820,6 +1956,64 @@ int mcpt_render_var(mcpt_scene* s, const mcpt_render_params* p, float* fb_rgb, f
                     mcpt_render_stats* stats) {
     if (!var_rgba) return fail(MCPT_E_INVALID, "NULL argument");
     return render_sync(s, p, fb_rgb, stats, nullptr, var_rgba);
+}
+
+void mcpt_adaptive_params_default(mcpt_adaptive_params* p) {
+    if (!p) return;
+    p->max_passes = 8;
+    p->min_passes = 1;
+    p->threshold = 0.2f;
+    p->lum_floor = 0.01f;
+    p->dilate = 1;
+    p->force_list = 0;
+}
+
+int mcpt_render_adaptive_device(mcpt_scene* s, const mcpt_render_params* p, const mcpt_adaptive_params* ap,
+                                float* d_fb_rgba, float* d_var_rgba, uint32_t* d_pass_count, void* hip_stream) {
+    return guarded([&]() -> int {
+        if (!s) return fail(MCPT_E_INVALID, "NULL scene");
+        if (!d_fb_rgba || !d_var_rgba || !d_pass_count)
+            return fail(MCPT_E_INVALID, "NULL framebuffer, variance buffer or pass-count buffer");
+        if (p && p->width > 0 && p->height > 0) {
+            const size_t px = size_t(p->width) * size_t(p->height);
+            if (ranges_overlap(d_fb_rgba, px * 16, d_var_rgba, px * 16) ||
+                ranges_overlap(d_fb_rgba, px * 16, d_pass_count, px * 4) ||
+                ranges_overlap(d_var_rgba, px * 16, d_pass_count, px * 4))
+                return fail(MCPT_E_INVALID, "the framebuffer, the variance buffer and the pass-count buffer overlap");
+        }
+        const Adaptive a = adaptive_resolve(ap);
+        hipStream_t st = static_cast<hipStream_t>(hip_stream);
+        check_adaptive_render(*s, p, a, st);
+        adaptive_async(*s, p, a, d_fb_rgba, d_var_rgba, d_pass_count, st);
+        return MCPT_OK;
+    });
+}
+
+// fb, var and the pass counts are staged in the scene's host-render buffer
+int mcpt_render_adaptive(mcpt_scene* s, const mcpt_render_params* p, const mcpt_adaptive_params* ap, float* fb_rgb,
+                         float* var_rgba, uint32_t* pass_count, mcpt_render_stats* stats) {
+    return guarded([&]() -> int {
+        if (!s || !fb_rgb || !var_rgba || !pass_count) return fail(MCPT_E_INVALID, "NULL argument");
+        const Adaptive a = adaptive_resolve(ap);
+        check_adaptive_render(*s, p, a, nullptr);
+        set_device(*s);
+        const size_t npx = size_t(p->width) * size_t(p->height);
+        ensure_buf(s->ws.fb, s->ws.fb_bytes, npx * 36);
+        float* d_fb = static_cast<float*>(s->ws.fb);
+        float* d_var = d_fb + npx * 4;
+        uint32_t* d_count = reinterpret_cast<uint32_t*>(d_var + npx * 4);
+        read_stats_all(*s, nullptr);   // start a fresh record
+        adaptive_async(*s, p, a, d_fb, d_var, d_count, nullptr);
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        std::vector<float> rgba(npx * 4);
+        HIP_TRY(hipMemcpy(rgba.data(), d_fb, npx * 16, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < npx; ++i)
+            for (int c = 0; c < 3; ++c) fb_rgb[3 * i + c] = rgba[4 * i + c];
+        HIP_TRY(hipMemcpy(var_rgba, d_var, npx * 16, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(pass_count, d_count, npx * 4, hipMemcpyDeviceToHost));
+        read_stats_all(*s, stats);
+        return MCPT_OK;
+    });
 }
 
 void mcpt_denoise_var_params_default(mcpt_denoise_var_params* p) {

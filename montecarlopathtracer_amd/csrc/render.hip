@@ -52,10 +52,15 @@ __device__ __forceinline__ void store_part(const KernelParams& kp, uint32_t id, 
         kp.partial[id] = val;
 }
 
-template <bool IN_LDS, int S, int BLOCK, bool DBG, bool QE, bool COUNT>
-// counting kernels of the global layout are held to 4 waves per SIMD (128 VGPRs)
-// by the launch bound; the lean (timed) kernels fit without it
-__global__ void __launch_bounds__(BLOCK, (!IN_LDS && COUNT) ? 4 : 1) path_kernel(const KernelParams kp) {
+// The megakernel's body, shared by path_kernel and the pixel-list kernel of
+// the adaptive sampler (LIST: the unit's packed pixel index is looked up in
+// kp.pixel_list, a frame of kp.npix_local listed pixels; everything else --
+// unit decode, tail split, partial-sum layout -- is that of a full frame).
+// kp by value: by reference the inlined body compiled to 2 to 23 instructions
+// more or fewer in the LDS variants of path_kernel; by value every path_kernel keeps
+// its instruction count, instruction mix and registers (scripts/isa_diff.py).
+template <bool IN_LDS, int S, int BLOCK, bool DBG, bool QE, bool COUNT, bool LIST>
+__device__ __forceinline__ void path_body(const KernelParams kp) {
     static_assert((BLOCK & (BLOCK - 1)) == 0, "stack slot addresses (slot_of) mask by a power-of-two block");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = (int)threadIdx.x;
@@ -226,7 +231,7 @@ __global__ void __launch_bounds__(BLOCK, (!IN_LDS && COUNT) ? 4 : 1) path_kernel
                     part = v3(0, 0, 0);
                     if (s >= s_end) {
                         // sample past spp in a ragged last chunk: nothing to do, take another item
-                    } else if (unit_pixel(kp, v, px, py)) {
+                    } else if (unit_pixel(kp, LIST ? kp.pixel_list[v] : v, px, py)) {
                         newp = true;
                         mode = kReady;
                     } else {
@@ -320,6 +325,20 @@ __global__ void __launch_bounds__(BLOCK, (!IN_LDS && COUNT) ? 4 : 1) path_kernel
     }
 #endif
     flush_counters(c, kp.stats);
+}
+
+template <bool IN_LDS, int S, int BLOCK, bool DBG, bool QE, bool COUNT>
+// counting kernels of the global layout are held to 4 waves per SIMD (128 VGPRs)
+// by the launch bound; the lean (timed) kernels fit without it
+__global__ void __launch_bounds__(BLOCK, (!IN_LDS && COUNT) ? 4 : 1) path_kernel(const KernelParams kp) {
+    path_body<IN_LDS, S, BLOCK, DBG, QE, COUNT, false>(kp);
+}
+
+// Adaptive sampling (adaptive.hip): the same body over a device-built pixel
+// list, CVMCTracer mode, lean and counting
+template <bool IN_LDS, int S, int BLOCK, bool COUNT>
+__global__ void __launch_bounds__(BLOCK, (!IN_LDS && COUNT) ? 4 : 1) list_kernel(const KernelParams kp) {
+    path_body<IN_LDS, S, BLOCK, false, false, COUNT, true>(kp);
 }
 
 // running mean of a pixel (CUTracer.cu:214-217; QE gamma-space, rtx.hlsl:401-402):
@@ -438,6 +457,16 @@ hipError_t launch_path(const KernelParams& kp, int grid, size_t lds, hipStream_t
     return hipGetLastError();
 }
 
+template <bool IN_LDS, int S, int BLOCK>
+hipError_t launch_list(const KernelParams& kp, int grid, size_t lds, hipStream_t st) {
+    auto kern = kp.lean ? list_kernel<IN_LDS, S, BLOCK, false> : list_kernel<IN_LDS, S, BLOCK, true>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, kp);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 // LDS need of the in-LDS variant for a scene image of `image_bytes`
@@ -469,6 +498,35 @@ hipError_t launch_render(const KernelParams& kp_in, int cus, hipStream_t st, hip
     if (ev1 && (e = hipEventRecord(ev1, st)) != hipSuccess) return e;
     e = launch_reduce(kp, fb, st);
     if (e == hipSuccess && ev2) e = hipEventRecord(ev2, st);
+    if (variant_out) *variant_out = variant;
+    return e;
+}
+
+// memset counter, pixel-list kernel (events ev0 / ev1 around it): launch_render's
+// variant choice; the caller merges the partial sums (adaptive.hip)
+hipError_t launch_render_list(const KernelParams& kp_in, int cus, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
+                              int* variant_out) {
+    KernelParams kp = kp_in;
+    if (!kp.pixel_list || kp.mode == kModeQE || kp.unit_counters) return hipErrorInvalidValue;
+    const uint32_t img = kp.scene.image_bytes;
+    kp.total_lanes = (uint32_t)total_lanes_for(img, cus);
+    hipError_t e = hipMemsetAsync(kp.counter, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    if (ev0 && (e = hipEventRecord(ev0, st)) != hipSuccess) return e;
+    int variant = 3;
+    if (kp.scene.node_boxes) {
+        e = launch_list<false, 8, kGlobalBlock>(kp, cus * kGlobalBlocksPerCu, (size_t)8 * kGlobalBlock * 16, st);
+    } else if (lds_bytes_in_lds(img, 8) <= kMaxLds) {
+        variant = 1;
+        e = launch_list<true, 8, kLdsBlock>(kp, cus, lds_bytes_in_lds(img, 8), st);
+    } else if (lds_bytes_in_lds(img, 4) <= kMaxLds) {
+        variant = 2;
+        e = launch_list<true, 4, kLdsBlock>(kp, cus, lds_bytes_in_lds(img, 4), st);
+    } else {
+        e = launch_list<false, 8, kGlobalBlock>(kp, cus * kGlobalBlocksPerCu, (size_t)8 * kGlobalBlock * 16, st);
+    }
+    if (e != hipSuccess) return e;
+    if (ev1 && (e = hipEventRecord(ev1, st)) != hipSuccess) return e;
     if (variant_out) *variant_out = variant;
     return e;
 }

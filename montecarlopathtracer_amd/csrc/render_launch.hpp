@@ -113,6 +113,9 @@ struct KernelParams {
     // 1: the reduction writes the plain mean of this call's samples (a device's
     // shard of a multi-device render; gather_kernel applies the running mean)
     int32_t raw_mean;
+    // pixel-list kernel (adaptive sampling): packed pixel index of listed pixel i;
+    // npix_local is then the list's length
+    const uint32_t* pixel_list;
 };
 
 // Multi-device gather (capi.cpp render_multi): shard r of `nshards` wrote the
@@ -181,6 +184,8 @@ int total_lanes_for(uint32_t image_bytes, int cus);
 // memset counter, path kernel (events ev0/ev1 around it), reduce kernel (ev2)
 hipError_t launch_render(const KernelParams& kp, int cus, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
                          hipEvent_t ev2, float4* fb, int* variant_out);
+hipError_t launch_render_list(const KernelParams& kp, int cus, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
+                              int* variant_out);
 hipError_t launch_reduce(const KernelParams& kp, float4* fb, hipStream_t st);
 hipError_t launch_gather(const GatherParams& g, hipStream_t st);
 hipError_t launch_query(const QueryParams& q, hipStream_t st);

@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "mcpt_device.hpp"
+#include "partial_sum.hpp"
 #include "trace_device.hpp"
 #include "variance_launch.hpp"
 
@@ -34,19 +35,6 @@ using namespace dev;
 using namespace trace;
 
 namespace {
-
-// chunk c's partial sum of pixel v, as reduce_kernel reads it
-__device__ __forceinline__ V3 chunk_partial(const KernelParams& kp, uint32_t c, uint32_t v, uint32_t n) {
-    const uint32_t u = c * kp.npix_local + v;
-    if (u >= kp.tail_units) {   // tail split: the unit's samples, in sample order
-        const float4* tb = kp.tail_buf + (size_t)(u - kp.tail_units) * kp.chunk;
-        V3 pc = v3(0, 0, 0);
-        for (uint32_t j = 0; j < n; j++) pc = vadd(pc, v3(tb[j].x, tb[j].y, tb[j].z));
-        return pc;
-    }
-    const float4 p = kp.partial[u];
-    return v3(p.x, p.y, p.z);
-}
 
 __global__ void __launch_bounds__(256) variance_kernel(const KernelParams kp, float4* __restrict__ var) {
     const uint32_t v = blockIdx.x * 256u + threadIdx.x;

@@ -402,6 +402,38 @@ class Scene:
         check(lib().mcpt_render_var_device(self.handle, C.byref(params.to_c()), C.c_void_p(d_fb_rgba_ptr),
                                            C.c_void_p(d_var_rgba_ptr), C.c_void_p(stream_ptr)))
 
+    def render_adaptive(self, params: RenderParams, adaptive=None, fb: Optional[np.ndarray] = None,
+                        var: Optional[np.ndarray] = None):
+        """Variance-driven adaptive sampling (mcpt_render_adaptive): passes of ``params.spp`` samples,
+        each only over the pixels whose luminance standard error is still above the threshold
+        (``adaptive``: an ``adaptive_params(...)``, None = the defaults).  Returns (fb (H, W, 3),
+        var (H, W, 4), count (H, W) uint32 = passes each pixel received, stats summed over the
+        passes).  A pixel with count m holds what m chained uniform ``render_var`` calls leave in it."""
+        H, W = int(params.height), int(params.width)
+        if fb is None:
+            fb = np.zeros((H, W, 3), np.float32)
+        if var is None:
+            var = np.zeros((H, W, 4), np.float32)
+        if fb.dtype != np.float32 or not fb.flags.c_contiguous or fb.size != 3 * H * W:
+            raise McptError(-1, "fb must be a C-contiguous float32 array with 3 floats per pixel")
+        if var.dtype != np.float32 or not var.flags.c_contiguous or var.size != 4 * H * W:
+            raise McptError(-1, "var must be a C-contiguous float32 array with 4 floats per pixel")
+        count = np.zeros((max(H, 0), max(W, 0)), np.uint32)
+        st = RenderStats()
+        check(lib().mcpt_render_adaptive(self.handle, C.byref(params.to_c()),
+                                         C.byref(adaptive) if adaptive is not None else None, _fptr(fb), _fptr(var),
+                                         count.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st)))
+        return fb, var, count, st.as_dict()
+
+    def render_adaptive_device(self, params: RenderParams, adaptive, d_fb_rgba_ptr: int, d_var_rgba_ptr: int,
+                               d_count_ptr: int, stream_ptr: int = 0):
+        """Adaptive render into device buffers (mcpt_render_adaptive_device): RGBA float framebuffer
+        and variance, one uint32 per pixel of pass counts.  Waits for the stream once per listed pass."""
+        check(lib().mcpt_render_adaptive_device(self.handle, C.byref(params.to_c()),
+                                                C.byref(adaptive) if adaptive is not None else None,
+                                                C.c_void_p(d_fb_rgba_ptr), C.c_void_p(d_var_rgba_ptr),
+                                                C.c_void_p(d_count_ptr), C.c_void_p(stream_ptr)))
+
     def reserve(self, params: RenderParams):
         check(lib().mcpt_scene_reserve(self.handle, C.byref(params.to_c())))
 
@@ -449,6 +481,14 @@ def denoise_device(width: int, height: int, color_ptr: int, albedo_ptr: int, nd_
     check(lib().mcpt_denoise_device(C.byref(denoise_params(width, height, **params)), C.c_void_p(color_ptr),
                                     C.c_void_p(albedo_ptr), C.c_void_p(nd_ptr), C.c_void_p(out_ptr),
                                     C.c_void_p(scratch_ptr), C.c_void_p(stream_ptr)))
+
+
+def adaptive_params(max_passes: int = 0, min_passes: int = 0, threshold: float = 0.0, lum_floor: float = 0.0,
+                    dilate: int = 0, force_list: bool = False) -> "_capi.AdaptiveParamsC":
+    """mcpt_adaptive_params; 0 = the default (8 passes, 1 before selection, threshold 0.2, floor 0.01,
+    window radius 1; dilate < 0 = no window)."""
+    return _capi.AdaptiveParamsC(int(max_passes), int(min_passes), float(threshold), float(lum_floor), int(dilate),
+                                 int(force_list))
 
 
 def denoise_var_params(width: int, height: int, sigma_l: float = 0.0, **params) -> "_capi.DenoiseVarParamsC":
