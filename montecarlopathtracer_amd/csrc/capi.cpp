@@ -995,7 +995,9 @@ void render_multi(mcpt_scene& s, const mcpt_render_params* p, float* d_fb, hipSt
         render_async(R, &pr, static_cast<float*>(R.ws.fb), R.stream, nullptr, true);
         if (use_rccl) continue;                        // gathered below, all ranks in one group
         char* dst = static_cast<char*>(s.gather) + size_t(r) * slot * 16;
-        if (R.device == s.device && !p->force_peer_copy)
+        if (!bytes) {
+            // a shard that owns no tile: nothing to copy
+        } else if (R.device == s.device && !p->force_peer_copy)
             HIP_TRY(hipMemcpyAsync(dst, R.ws.fb, bytes, hipMemcpyDeviceToDevice, R.stream));
         else
             HIP_TRY(hipMemcpyPeerAsync(dst, s.device, R.ws.fb, R.device, bytes, R.stream));

@@ -481,7 +481,10 @@ hipError_t launch_render(const KernelParams& kp_in, int cus, hipStream_t st, hip
     if (e != hipSuccess) return e;
     if (ev0 && (e = hipEventRecord(ev0, st)) != hipSuccess) return e;
     int variant = 0;
-    if (kp.scene.node_boxes) {                     // image built for global memory
+    if (!kp.npix_local) {                          // a shard that owns no tile: nothing to trace
+        variant = kp.scene.node_boxes ? 3 : lds_bytes_in_lds(img, 8) <= kMaxLds ? 1
+                                          : lds_bytes_in_lds(img, 4) <= kMaxLds ? 2 : 3;
+    } else if (kp.scene.node_boxes) {              // image built for global memory
         variant = 3;
         e = launch_path<false, 8, kGlobalBlock>(kp, cus * kGlobalBlocksPerCu, (size_t)8 * kGlobalBlock * 16, st);
     } else if (lds_bytes_in_lds(img, 8) <= kMaxLds) {
@@ -540,6 +543,7 @@ void read_lane_use(unsigned long long out[6]) {   // megakernel lane-use counter
 #endif
 
 hipError_t launch_reduce(const KernelParams& kp, float4* fb, hipStream_t st) {
+    if (!kp.npix_local) return hipSuccess;   // (a grid of 0 blocks is an invalid configuration)
     hipLaunchKernelGGL(reduce_kernel, dim3((kp.npix_local + 255u) / 256u), dim3(256), 0, st, kp, fb);
     return hipGetLastError();
 }

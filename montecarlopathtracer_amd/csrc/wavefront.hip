@@ -1023,6 +1023,12 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
     const hipStream_t st = ws.st[0];
     hipError_t e = hipSuccess;
     if (ev0 && (e = hipEventRecord(ev0, st)) != hipSuccess) return e;
+    if (!kp.npix_local) {   // a shard that owns no tile: no batch (the batch split below divides by npix_local)
+        if (ev1 && (e = hipEventRecord(ev1, st)) != hipSuccess) return e;
+        if (ev2 && (e = hipEventRecord(ev2, st)) != hipSuccess) return e;
+        if (variant_out) *variant_out = in_lds ? 4 : 5;
+        return hipSuccess;
+    }
     if (ns > 1) {
         if ((e = hipEventRecord(ws.fork, st)) != hipSuccess) return e;
         for (int i = 1; i < ns; i++)

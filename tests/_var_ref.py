@@ -8,7 +8,8 @@ They are rebuilt from plain renders: for a power-of-two chunk length n, a
 CVMCTracer-mode render with spp = n, spp_offset = c n, prev_count = 0 returns
 P_c / n exactly, so multiplying by n gives chunk c's partial sum bit for bit
 (chunk_partials; tests/test_variance_cpu.py checks this against the oracle's
-spp_chunk render).
+spp_chunk render).  For any other n the partial sum is the in-order float32 sum
+of the chunk's n one-sample renders, which the same test checks the same way.
 """
 import numpy as np
 
@@ -24,11 +25,18 @@ def chunk_lengths(spp, chunk):
 
 def chunk_partials(render, spp, chunk, spp_offset=0):
     """[P_c] from render(n, offset) -> the (H, W, 3) float32 mean of the n samples from
-    `offset` on; every chunk length must be a power of two"""
+    `offset` on.  A power-of-two chunk length n: mean * n, one render.  Any other n: a
+    1-spp render at offset s is sample s itself (0 + x and / 1 are exact) and the kernels
+    form a chunk's sum in sample order from 0, so P_c = ((s_0 + s_1) + s_2) + ... in float32"""
     parts, off = [], spp_offset
     for n in chunk_lengths(spp, chunk):
-        assert n & (n - 1) == 0, "chunk lengths must be powers of two"
-        parts.append((np.asarray(render(n, off), f32) * f32(n)).astype(f32))
+        if n & (n - 1) == 0:
+            P = (np.asarray(render(n, off), f32) * f32(n)).astype(f32)
+        else:
+            P = f32(0)
+            for k in range(n):
+                P = (P + np.asarray(render(1, off + k), f32)).astype(f32)
+        parts.append(P)
         off += n
     return parts
 

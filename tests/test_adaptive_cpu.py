@@ -95,6 +95,35 @@ def test_adaptive_equals_the_uniform_chain_per_pixel_and_every_count_occurs(pass
     assert np.array_equal(count, np.sum(active, axis=0).astype(np.uint32))
 
 
+@pytest.fixture(scope="module")
+def odd_passes(oracle_mod, o_scene):
+    """[(mean, var)] of 4 passes of 15 spp in chunks of 7, 7, 1: the partial sums of the 7-sample
+    chunks are in-order sums of one-sample renders (_var_ref.chunk_partials), so P_c / 7 rounds"""
+    def chunk_render(n, off):
+        return o_scene.render(oracle_mod.RenderParams(width=W, height=H, spp=n, spp_offset=off, seed=SEED,
+                                                      threads=8))[0]
+    return [V.variance(V.chunk_partials(chunk_render, 15, 7, spp_offset=j * 15), 15, 7) for j in range(4)]
+
+
+@pytest.mark.parametrize("dilate_r,histogram", [(1, [1032, 260, 97, 1683]), (0, [2612, 131, 71, 258])])
+def test_adaptive_with_chunks_of_seven_equals_the_uniform_chain_per_pixel(oracle_mod, o_scene, odd_passes, dilate_r,
+                                                                          histogram):
+    chain = AR.uniform_chain(odd_passes)
+    # the chain's first link is the oracle's own chunked render
+    ref, _ = o_scene.render(oracle_mod.RenderParams(width=W, height=H, spp=15, spp_chunk=7, seed=SEED, threads=8))
+    assert np.array_equal(_bits(chain[0][0]), _bits(ref))
+    fb, var, count, active = AR.adaptive(odd_passes, max_passes=4, threshold=0.5, lum_floor=0.01, dilate_r=dilate_r)
+    hist = np.bincount(count.ravel(), minlength=5)[1:].tolist()
+    print("dilate", dilate_r, "count histogram", hist)
+    for m in range(1, 5):
+        sel = count == m
+        assert sel.any(), m
+        assert np.array_equal(_bits(fb[sel]), _bits(chain[m - 1][0][sel])), m
+        assert np.array_equal(_bits(var[sel]), _bits(chain[m - 1][1][sel])), m
+    assert hist == histogram
+    assert np.array_equal(count, np.sum(active, axis=0).astype(np.uint32))
+
+
 def test_min_passes_and_limits_of_the_restatement(passes, chain):
     _, _, count, _ = AR.adaptive(passes, max_passes=PASSES, min_passes=3, threshold=0.5)
     assert count.min() == 3 and count.max() == PASSES

@@ -3,7 +3,10 @@ pixel-list megakernel of csrc/render.hip, the selection, compaction and merge
 kernels of csrc/adaptive.hip), bit for bit against the GPU's own uniform chain:
 `render_var` with prev_count = j and spp_offset = j S saved after each pass,
 the numpy selection (tests/_adaptive_ref.py) applied to those images, and the
-per-unit counters of each uniform pass for the work counters.
+per-unit counters of each uniform pass for the work counters.  Besides the
+64x48 frame: packed pixel counts that leave the last wave or workgroup partly
+filled, lists of one pixel, of less than a wave and of about one wave, window
+radii up to 4, and chunk lengths that are no powers of two.
 """
 import numpy as np
 import pytest
@@ -35,17 +38,18 @@ def _assert_equal(got, ref, what):
                            got[bad][:5].tolist(), ref[bad][:5].tolist())
 
 
-def _chain(mcpt, W, H, S, chunk, passes):
+def _chain(mcpt, W, H, S, chunk, passes, spp_offset=0, **fields):
     """[(fb, var) after j + 1 chained uniform render_var calls], computed once per frame and
-    left unchanged (a longer chain of the same frame serves the shorter ones)"""
-    key = (W, H, S, chunk)
+    left unchanged (a longer chain of the same frame serves the shorter ones); fields: render
+    params that change the image (seed), the same in every call"""
+    key = (W, H, S, chunk, spp_offset, tuple(sorted(fields.items())))
     have = _chains.setdefault(key, [])
     scene = _scene(mcpt)
     while len(have) < passes:
         j = len(have)
         fb, var = (have[-1][0].copy(), have[-1][1].copy()) if j else (None, None)
-        fb, var, _ = scene.render_var(mcpt.RenderParams(width=W, height=H, spp=S, spp_chunk=chunk, spp_offset=j * S,
-                                                        prev_count=j), fb, var)
+        fb, var, _ = scene.render_var(mcpt.RenderParams(width=W, height=H, spp=S, spp_chunk=chunk,
+                                                        spp_offset=spp_offset + j * S, prev_count=j, **fields), fb, var)
         fb.setflags(write=False)
         var.setflags(write=False)
         have.append((fb, var))
@@ -61,25 +65,26 @@ def _unit_order(mcpt, W, H, tile=8):
     return inv
 
 
-def _pass_counters(mcpt, W, H, S, chunk, passes):
+def _pass_counters(mcpt, W, H, S, chunk, passes, tile=8, spp_offset=0, **fields):
     """(passes, H, W, 4) uint64: rays, inner, leaf, tests of every pixel in every uniform pass
     (summed over the pass's chunks), from render_unit_counters; W and H multiples of the tile"""
-    key = (W, H, S, chunk, passes)
+    key = (W, H, S, chunk, passes, tile, spp_offset, tuple(sorted(fields.items())))
     if key not in _counters:
-        assert W % 8 == 0 and H % 8 == 0
-        inv, npix, nch = _unit_order(mcpt, W, H), W * H, (S + chunk - 1) // chunk
+        assert W % tile == 0 and H % tile == 0
+        inv, npix, nch = _unit_order(mcpt, W, H, tile), W * H, (S + chunk - 1) // chunk
         out = np.zeros((passes, H * W, 4), np.uint64)
         for j in range(passes):
             _, uc = _scene(mcpt).render_unit_counters(mcpt.RenderParams(width=W, height=H, spp=S, spp_chunk=chunk,
-                                                                        spp_offset=j * S))
+                                                                        spp_offset=spp_offset + j * S, tile=tile,
+                                                                        **fields))
             assert uc.shape == (npix * nch, 4)
             out[j] = uc.reshape(nch, npix, 4).astype(np.uint64).sum(axis=0)[inv]
         _counters[key] = out.reshape(passes, H, W, 4)
     return _counters[key]
 
 
-def _reference(mcpt, W, H, S, chunk, passes, ap):
-    chain = _chain(mcpt, W, H, S, chunk, passes)
+def _reference(mcpt, W, H, S, chunk, passes, ap, **chain_kw):
+    chain = _chain(mcpt, W, H, S, chunk, passes, **chain_kw)
     fb, var, count, _ = AR.adaptive_from_chain(chain, max_passes=passes, min_passes=ap.get("min_passes", 1),
                                                threshold=ap["threshold"], lum_floor=ap.get("lum_floor", 0.01),
                                                dilate_r=ap.get("dilate_r", 1))
@@ -111,8 +116,8 @@ def _check_images(got, ref, S):
 
 
 def _check_counters(mcpt, st, rcount, W, H, S, chunk, passes, names=("rays", "inner_visits", "leaf_visits",
-                                                                     "tri_tests")):
-    pc = _pass_counters(mcpt, W, H, S, chunk, passes)
+                                                                     "tri_tests"), **counter_kw):
+    pc = _pass_counters(mcpt, W, H, S, chunk, passes, **counter_kw)
     want = np.zeros(4, np.uint64)
     for j in range(passes):
         want += pc[j][rcount > j].sum(axis=0)
@@ -197,6 +202,152 @@ def test_force_list_with_every_pixel_listed_is_the_uniform_chain(mcpt):
     _assert_equal(fb2, fb, "framebuffer, full-frame passes")
     _assert_equal(var2, var, "variance, full-frame passes")
     assert (count2 == 3).all() and {k: st2[k] for k in INT_STATS} == {k: st[k] for k in INT_STATS}
+
+
+# ---- awkward packed counts, short lists, odd chunk lengths -----------------------------
+
+def _packed_count(mcpt, W, H, tile):
+    return len(mcpt.RenderParams(width=W, height=H, tile=tile, packed=True).shard_pixels())
+
+
+def _list_sizes(chain, passes, ap):
+    """pixels listed by every pass after pass 0, from the reference's active sets"""
+    active = AR.adaptive_from_chain(chain, max_passes=passes, min_passes=ap.get("min_passes", 1),
+                                    threshold=ap["threshold"], lum_floor=ap.get("lum_floor", 0.01),
+                                    dilate_r=ap.get("dilate_r", 1))[3]
+    return [int(a.sum()) for a in active[1:]]
+
+
+SMALL_FRAMES = [
+    # tile, W, H, packed pixels, render fields
+    (1, 37, 29, 1073, {}),
+    (4, 36, 28, 1008, {}),
+    (5, 37, 29, 1200, {}),
+    (8, 24, 8, 192, {}),                        # three waves of one block
+    (8, 8, 8, 64, {}),                          # one wave
+    (8, 1, 1, 64, dict(spp_offset=48)),         # one real pixel; samples 48..55: the first with radiance (oracle)
+]
+
+
+@pytest.mark.parametrize("case", SMALL_FRAMES, ids=lambda c: f"tile{c[0]}-{c[1]}x{c[2]}")
+def test_adaptive_at_awkward_packed_counts_equals_the_uniform_chain(mcpt, case):
+    tile, W, H, npk, fields = case
+    assert _packed_count(mcpt, W, H, tile) == npk and npk % 256 != 0
+    assert npk % 64 != 0 or tile == 8
+    frame = dict(W=W, H=H, S=8, chunk=2, passes=4)
+    ap = dict(threshold=0.5)
+    ref = _reference(mcpt, **frame, ap=ap, **fields)
+    sizes = _list_sizes(ref[0], 4, ap)
+    print("listed", sizes, "count histogram", np.bincount(ref[3].ravel()).tolist())
+    assert len(sizes) == 3 and all(0 < n < npk for n in sizes)      # every later pass runs over a list
+    got = _run(mcpt, _scene(mcpt), **frame, ap=ap, tile=tile, **fields)
+    _check_images(got, ref, frame["S"])
+    if W % tile == 0 and H % tile == 0:
+        _check_counters(mcpt, got[3], ref[3], **frame, tile=tile, **fields)
+
+
+SHORT_LISTS = [
+    # threshold, what the reference's lists must contain: (lo, hi) = a pass listing lo..hi pixels
+    (0.97, [(1, 1), (2, 63)]),
+    (0.95, [(65, 127), (2, 63)]),
+    (0.98, [(2, 63)]),
+]
+
+
+@pytest.mark.parametrize("threshold,wanted", SHORT_LISTS, ids=[f"threshold-{t}" for t, _ in SHORT_LISTS])
+def test_short_lists_equal_the_uniform_chain(mcpt, threshold, wanted):
+    """lists of one pixel, of less than a wave and of one wave and a little: list_kernel's unit
+    handout reserves 64 units of which most do not exist"""
+    ap = dict(threshold=threshold, dilate_r=0)
+    ref = _reference(mcpt, **MAIN, ap=ap)
+    sizes = _list_sizes(ref[0], MAIN["passes"], ap)
+    print("threshold", threshold, "listed", sizes)
+    for lo, hi in wanted:
+        assert any(lo <= n <= hi for n in sizes), (lo, hi, sizes)
+    got = _run(mcpt, _scene(mcpt), **MAIN, ap=ap)
+    _check_images(got, ref, MAIN["S"])
+    _check_counters(mcpt, got[3], ref[3], **MAIN)
+
+
+FORCED = [
+    # tile, W, H, list length = packed pixels, render fields
+    (8, 8, 8, 64, {}),
+    (1, 9, 7, 63, {}),
+    (1, 13, 5, 65, {}),
+    (8, 1, 1, 64, dict(spp_offset=48)),         # one real pixel
+]
+
+
+@pytest.mark.parametrize("case", FORCED, ids=lambda c: f"tile{c[0]}-{c[1]}x{c[2]}")
+def test_force_list_over_lists_of_about_one_wave(mcpt, case):
+    """min_passes = max_passes = 3 through the list: the list is the packed frame"""
+    tile, W, H, npk, fields = case
+    assert _packed_count(mcpt, W, H, tile) == npk
+    frame = dict(W=W, H=H, S=8, chunk=2, passes=3)
+    chain = _chain(mcpt, W, H, 8, 2, 3, **fields)
+    assert chain[2][1][..., :3].max() > 0
+    ap = dict(threshold=0.5, min_passes=3, force_list=True)
+    fb, var, count, st = _run(mcpt, _scene(mcpt), **frame, ap=ap, tile=tile, **fields)
+    assert (count == 3).all()
+    _assert_equal(fb, chain[2][0], "framebuffer")
+    _assert_equal(var, chain[2][1], "variance")
+    assert st["paths"] == 3 * 8 * W * H and st["renders"] == 3
+    if W % tile == 0 and H % tile == 0:
+        _check_counters(mcpt, st, count, **frame, tile=tile, **fields)
+
+
+@pytest.mark.parametrize("dilate_r", [2, 4])
+def test_wider_dilation_windows(mcpt, dilate_r):
+    ap = dict(threshold=0.98, dilate_r=dilate_r)
+    ref = _reference(mcpt, **MAIN, ap=ap)
+    sizes = _list_sizes(ref[0], MAIN["passes"], ap)
+    bare = _list_sizes(ref[0], MAIN["passes"], dict(threshold=0.98, dilate_r=0))
+    print("radius", dilate_r, "listed", sizes, "without a window", bare)
+    assert sizes and bare and bare[0] < sizes[0] <= bare[0] * (2 * dilate_r + 1) ** 2
+    got = _run(mcpt, _scene(mcpt), **MAIN, ap=ap)
+    _check_images(got, ref, MAIN["S"])
+    _check_counters(mcpt, got[3], ref[3], **MAIN)
+
+
+def test_a_dilation_window_larger_than_the_frame(mcpt):
+    """radius 4 on 6x5: one noisy pixel keeps all 30 active"""
+    frame = dict(W=6, H=5, S=8, chunk=2, passes=4)
+    ap = dict(threshold=0.5, dilate_r=4)
+    ref = _reference(mcpt, **frame, ap=ap)
+    assert _list_sizes(ref[0], 4, ap) == [30, 30, 30]
+    over = AR.over(ref[0][0][0], ref[0][0][1], 0.5, 0.01)
+    assert 0 < int(over.sum()) < 30                                  # the window, not the pixels themselves
+    got = _run(mcpt, _scene(mcpt), **frame, ap=ap)
+    _check_images(got, ref, frame["S"])
+    assert (got[2] == 4).all()
+
+
+@pytest.mark.parametrize("ap,fields", [(dict(threshold=0.5, lum_floor=0.2), {}),
+                                       (dict(threshold=0.5), dict(spp_offset=1000, seed=12345))],
+                         ids=["lum-floor-0.2", "offset-1000-seed-12345"])
+def test_other_fields_reach_the_selection_and_the_list_kernel(mcpt, ap, fields):
+    ref = _reference(mcpt, **MAIN, ap=ap, **fields)
+    base = _reference(mcpt, **MAIN, ap=dict(threshold=0.5))
+    assert not np.array_equal(ref[3], base[3])                       # the field changes the selection
+    hist = np.bincount(ref[3].ravel())
+    assert (hist > 0).sum() >= 3, hist.tolist()
+    got = _run(mcpt, _scene(mcpt), **MAIN, ap=ap, **fields)
+    _check_images(got, ref, MAIN["S"])
+    _check_counters(mcpt, got[3], ref[3], **MAIN, **fields)
+
+
+@pytest.mark.parametrize("kw", [{}, dict(tail_units=500)], ids=["defaults", "mixed-tail-500"])
+@pytest.mark.parametrize("S,chunk", [(15, 7), (10, 3)])
+def test_chunk_lengths_that_are_no_powers_of_two(mcpt, S, chunk, kw):
+    """chunks of 7 7 1 and 3 3 3 1: the merge's d = P_c / n - mean rounds"""
+    frame = dict(W=64, H=48, S=S, chunk=chunk, passes=4)
+    ap = dict(threshold=0.5)
+    ref = _reference(mcpt, **frame, ap=ap)
+    hist = np.bincount(ref[3].ravel(), minlength=5)
+    assert (hist[1:] > 0).all(), hist.tolist()
+    got = _run(mcpt, _scene(mcpt), **frame, ap=ap, **kw)
+    _check_images(got, ref, S)
+    _check_counters(mcpt, got[3], ref[3], **frame)
 
 
 # ---- edges ------------------------------------------------------------------------

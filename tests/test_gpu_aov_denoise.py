@@ -143,6 +143,22 @@ def test_denoise_equals_restatement_on_random_features_8_iterations(mcpt, oracle
     assert np.abs(got - color).max() > 1e-3
 
 
+@pytest.mark.parametrize("H,W", [(1, 1), (1, 17), (17, 1), (16, 16), (17, 33)], ids=lambda v: str(v))
+def test_denoise_at_degenerate_sizes(mcpt, oracle_mod, H, W):
+    """one pixel, one row, one column, one 16x16 workgroup, one more than two: at 5 iterations the
+    steps of 8 and 16 reach past every such frame (at 1x1 only the centre tap is left)"""
+    rng = np.random.default_rng(100 * H + W)
+    ac, nd = _random_features(rng, H, W)
+    nd[..., :3] = R.normalize_cu((nd[..., :3] + np.float32(3) * np.array([0, 0, 1], np.float32)).astype(np.float32))
+    color = rng.random((H, W, 3)).astype(np.float32)
+    kw = dict(iterations=5, normal_power_log2=2, sigma_z=0.5)
+    got = mcpt.denoise(color, ac, nd, **kw)
+    assert got.shape == (H, W, 3) and np.isfinite(got).all()
+    _assert_equal(got, R.denoise(oracle_mod, color, ac, nd, **kw), f"denoise {W}x{H}")
+    if H * W > 1:
+        assert np.abs(got - color).max() > 1e-3
+
+
 def test_denoise_gamma_space(mcpt, oracle_mod, real_features):
     H, W = 20, 24
     ac, nd = (np.ascontiguousarray(a[:H, :W]) for a in real_features)

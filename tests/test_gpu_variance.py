@@ -2,7 +2,8 @@
 a-trous denoiser (csrc/denoise_var.hip) on the GPU, bit for bit against their
 numpy restatement (tests/_var_ref.py).  The variance kernel's chunk partial
 sums are rebuilt from the GPU's own one-chunk renders (power-of-two chunk
-lengths: mean * n is the partial sum exactly); then the host and device
+lengths: mean * n is the partial sum exactly; any other length: the in-order
+float32 sum of the chunk's one-sample renders); then the host and device
 entries, the absence of side effects, and the public pipeline against a
 converged render.
 """
@@ -15,6 +16,7 @@ pytestmark = pytest.mark.gpu
 
 _scenes = {}
 _parts = {}
+_chunk_renders = {}
 INT_STATS = ("rays", "paths", "inner_visits", "leaf_visits", "leaf_refs", "tri_tests", "shades", "stack_spills",
              "renders", "variant", "devices")
 
@@ -37,15 +39,23 @@ def _assert_equal(got, ref, what):
 
 
 def _partials(mcpt, W, H, spp, chunk, spp_offset=0):
-    """chunk partial sums from the GPU's own one-chunk renders, computed once per frame"""
+    """chunk partial sums from the GPU's own one-chunk renders, computed once per frame (the
+    one-sample renders of the chunk lengths that are no powers of two: once per frame and sample)"""
     key = (W, H, spp, chunk, spp_offset)
     if key not in _parts:
         scene = _scene(mcpt)
 
         def chunk_render(n, off):
-            return scene.render(mcpt.RenderParams(width=W, height=H, spp=n, spp_offset=off))[0]
+            if (W, H, n, off) not in _chunk_renders:
+                _chunk_renders[(W, H, n, off)] = scene.render(mcpt.RenderParams(width=W, height=H, spp=n,
+                                                                                spp_offset=off))[0]
+            return _chunk_renders[(W, H, n, off)]
         _parts[key] = V.chunk_partials(chunk_render, spp, chunk, spp_offset)
     return _parts[key]
+
+
+def _packed_count(mcpt, W, H, tile):
+    return len(mcpt.RenderParams(width=W, height=H, tile=tile, packed=True).shard_pixels())
 
 
 VAR_CASES = [
@@ -58,12 +68,36 @@ VAR_CASES = [
     ("ragged-37x29", 37, 29, 12, 4, "auto", {}),                             # tile padding, three chunks
     ("short-last-chunk", 64, 48, 10, 4, "auto", {}),                         # chunks of 4, 4, 2
     ("more-pixels-than-lanes", 608, 440, 2, 1, "auto", {}),
+    # packed pixel counts (owned tiles x tile^2) that are no multiples of 256 -- or of 64: the
+    # variance kernel's last workgroup and wave are partly filled; an eighth field = that count
+    ("tile1-37x29", 37, 29, 6, 2, "auto", dict(tile=1), 1073),
+    ("tile4-36x28", 36, 28, 6, 2, "auto", dict(tile=4), 1008),
+    ("tile5-37x29", 37, 29, 6, 2, "auto", dict(tile=5), 1200),
+    ("three-waves-24x8", 24, 8, 8, 2, "auto", {}, 192),
+    ("one-wave-8x8", 8, 8, 8, 2, "auto", {}, 64),
+    # one real pixel in a wave of padding; samples 48..55 are the first with radiance in it (oracle)
+    ("one-pixel-1x1", 1, 1, 8, 2, "auto", dict(spp_offset=48), 64),
 ]
+# chunk lengths that are no powers of two (3 3 3 1 | 7 7 1 | 5 5 1 | 6 6): d = P_c / n - mean rounds
+ODD_CHUNKS = [(10, 3), (15, 7), (11, 5), (12, 6)]
+ODD_VARIANTS = [("defaults", "auto", {}), ("no-tail-split", "auto", dict(tail_units_per_lane=-1)),
+                ("mixed-tail", "auto", dict(tail_units=5000)), ("wavefront", "auto", dict(pipeline="wavefront")),
+                ("global-layout", "global", {})]
+VAR_CASES += [(f"spp{s}-chunk{c}-{name}", 64, 48, s, c, layout, kw) for s, c in ODD_CHUNKS
+              for name, layout, kw in ODD_VARIANTS]
 
 
 @pytest.mark.parametrize("case", VAR_CASES, ids=lambda c: c[0])
 def test_render_var_equals_render_and_restatement(mcpt, case):
-    _, W, H, spp, chunk, layout, kw = case
+    _, W, H, spp, chunk, layout, kw = case[:7]
+    if len(case) > 7:
+        npk = _packed_count(mcpt, W, H, kw.get("tile", 8))
+        assert npk == case[7] and npk % 256 != 0
+        assert npk % 64 != 0 or kw.get("tile", 8) == 8
+    if (spp, chunk) in ODD_CHUNKS:
+        assert any(n & (n - 1) for n in V.chunk_lengths(spp, chunk))
+        if "tail_units" in kw:
+            assert 0 < kw["tail_units"] < W * H * len(V.chunk_lengths(spp, chunk))   # both kinds of unit
     scene = _scene(mcpt, layout=layout)
     if layout == "global":
         assert int(scene.info()["node_boxes"]) == 1
@@ -72,7 +106,7 @@ def test_render_var_equals_render_and_restatement(mcpt, case):
     fb, var, st = scene.render_var(p)
     _assert_equal(fb, ref_fb, "framebuffer")
     assert {k: st[k] for k in INT_STATS} == {k: ref_st[k] for k in INT_STATS}
-    mean, ref_var = V.variance(_partials(mcpt, W, H, spp, chunk), spp, chunk)
+    mean, ref_var = V.variance(_partials(mcpt, W, H, spp, chunk, kw.get("spp_offset", 0)), spp, chunk)
     _assert_equal(mean, ref_fb, "restated mean")          # the rebuilt partial sums are the render's
     assert var.shape == (H, W, 4) and (var[..., 3] == 0).all() and var[..., :3].max() > 0
     _assert_equal(var, ref_var, "variance")
@@ -90,6 +124,23 @@ def test_render_var_running_variance_over_two_calls(mcpt):
     _, r2 = V.variance(_partials(mcpt, W, H, spp, chunk, spp_offset=spp), spp, chunk, prev=r1, prev_count=1)
     assert not np.array_equal(r2, r1)
     _assert_equal(var, r2, "running variance")
+    ref_fb, _ = scene.render(p2, fb1.copy())
+    _assert_equal(fb, ref_fb, "running mean")
+
+
+def test_render_var_running_variance_over_two_calls_with_chunks_of_seven(mcpt):
+    scene = _scene(mcpt)
+    W, H, spp, chunk = 64, 48, 15, 7
+    fb, var, _ = scene.render_var(mcpt.RenderParams(width=W, height=H, spp=spp, spp_chunk=chunk))
+    fb1, var1 = fb.copy(), var.copy()
+    p2 = mcpt.RenderParams(width=W, height=H, spp=spp, spp_chunk=chunk, spp_offset=spp, prev_count=1)
+    scene.render_var(p2, fb, var)
+    _, r1 = V.variance(_partials(mcpt, W, H, spp, chunk), spp, chunk)
+    _assert_equal(var1, r1, "first variance")
+    m2, r2 = V.variance(_partials(mcpt, W, H, spp, chunk, spp_offset=spp), spp, chunk, prev=r1, prev_count=1)
+    assert not np.array_equal(r2, r1)
+    _assert_equal(var, r2, "running variance")
+    _assert_equal(fb, ((fb1 * np.float32(1) + m2) / np.float32(2)).astype(np.float32), "running mean, restated")
     ref_fb, _ = scene.render(p2, fb1.copy())
     _assert_equal(fb, ref_fb, "running mean")
 
@@ -181,6 +232,20 @@ def test_denoise_var_equals_restatement_on_random_inputs_8_iterations(mcpt, orac
     assert np.isfinite(got).all()
     _assert_equal(got, V.denoise_var(oracle_mod, color, var, ac, nd, **kw), "denoise_var x8")
     assert np.abs(got - color).max() > 1e-3
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (1, 17), (17, 1), (16, 16), (17, 33)], ids=lambda v: str(v))
+def test_denoise_var_at_degenerate_sizes(mcpt, oracle_mod, H, W):
+    """one pixel, one row, one column, one 16x16 workgroup, one more than two: at 5 iterations the
+    steps of 8 and 16 reach past every such frame (at 1x1 only the centre tap is left), and the
+    3x3 variance prefilter loses its taps outside the image"""
+    color, var, ac, nd = _random_inputs(np.random.default_rng(100 * H + W), H, W)
+    kw = dict(iterations=5, normal_power_log2=2, sigma_z=0.5, sigma_l=2.0)
+    got = mcpt.denoise_var(color, var, ac, nd, **kw)
+    assert got.shape == (H, W, 3) and np.isfinite(got).all()
+    _assert_equal(got, V.denoise_var(oracle_mod, color, var, ac, nd, **kw), f"denoise_var {W}x{H}")
+    if H * W > 1:
+        assert np.abs(got - color).max() > 1e-3
 
 
 def test_denoise_var_gamma_space(mcpt, oracle_mod, real_inputs):

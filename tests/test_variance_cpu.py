@@ -67,11 +67,37 @@ def _rmse(a, b):
     return float(np.sqrt(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)))
 
 
-@pytest.mark.parametrize("spp,chunk", CASES)
+# chunk lengths that are no powers of two (3 | 3 3 3 1 | 7 7 1 | 5 5 1 | 6 6): chunk_partials sums
+# one-sample renders in order; spp_chunk 0 is one chunk of all samples (no variance, the mean only)
+ODD_CASES = [(3, 0), (10, 3), (15, 7), (11, 5), (12, 6)]
+_chunk_renders = {}
+
+
+@pytest.mark.parametrize("spp,chunk", CASES + ODD_CASES)
 def test_rebuilt_partials_reproduce_the_chunked_render(oracle_mod, o_scene, renders, spp, chunk):
     """sum of the rebuilt P_c / spp == the oracle's spp_chunk render, bit for bit"""
     ref, _ = o_scene.render(oracle_mod.RenderParams(width=W, height=H, spp=spp, spp_chunk=chunk, seed=SEED, threads=8))
-    assert np.array_equal(_bits(renders[(spp, chunk)][0]), _bits(ref))
+    if (spp, chunk) in renders:
+        assert np.array_equal(_bits(renders[(spp, chunk)][0]), _bits(ref))
+        return
+
+    def chunk_render(n, off):
+        if (n, off) not in _chunk_renders:
+            _chunk_renders[(n, off)] = o_scene.render(oracle_mod.RenderParams(
+                width=W, height=H, spp=n, spp_offset=off, seed=SEED, threads=8))[0]
+        return _chunk_renders[(n, off)]
+    ns = V.chunk_lengths(spp, chunk or spp)
+    assert any(n & (n - 1) for n in ns), ns                   # the one-sample route is taken
+    parts = V.chunk_partials(chunk_render, spp, chunk or spp)
+    total = np.zeros_like(parts[0])
+    for P in parts:
+        total = total + P
+    mean = (total / np.float32(spp)).astype(np.float32)
+    assert np.array_equal(_bits(mean), _bits(ref))
+    if len(ns) >= 2:
+        rmean, var = V.variance(parts, spp, chunk)
+        assert np.array_equal(_bits(rmean), _bits(mean))
+        assert np.isfinite(var).all() and (var >= 0).all() and var[..., :3].max() > 0
 
 
 @pytest.mark.parametrize("spp,chunk", CASES)
