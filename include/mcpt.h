@@ -486,6 +486,59 @@ int mcpt_render_adaptive(mcpt_scene*, const mcpt_render_params*, const mcpt_adap
 int mcpt_render_adaptive_device(mcpt_scene*, const mcpt_render_params*, const mcpt_adaptive_params*,
                                 float* d_fb_rgba, float* d_var_rgba, uint32_t* d_pass_count, void* hip_stream);
 
+/* ---- device ray queries: closest hit and any hit over ray buffers ------------ */
+/* The renders' traversal for rays of the caller's own, in device memory: a
+ * query is the walk mcpt_intersect runs (the ordered KD walk with the scene's
+ * layout: the LDS image, or the global-memory image with the child-box cull),
+ * in a persistent kernel built like the wavefront extend.  Asynchronous on a
+ * stream; after mcpt_scene_reserve_rays or a first query nothing is allocated.
+ * Preconditions as mcpt_intersect: finite origins, finite non-zero directions;
+ * t_max finite or FLT_MAX (a t_max <= 0 simply misses).
+ * MCPT_E_INVALID, before anything is launched or allocated and in this order:
+ * a NULL scene, n < 0, a NULL required pointer with n > 0, a field of the
+ * params out of range (the message names it); then MCPT_E_UNSUPPORTED for
+ * n >= 2^31 / 3 (mcpt_intersect's limit); then MCPT_E_INVALID for a host-only
+ * scene and for an output buffer that overlaps an input or another output.
+ * n = 0 is a no-op.  A multi-device scene runs the query on devices[0].
+ * The workspace is the scene's: the stack spill area a render of the same
+ * scene uses (32 x 16 B per resident lane), a device copy of the triangle
+ * numbering (4 B per triangle) and a counter block.  Run the queries on the
+ * stream of the scene's renders, or synchronize: they share the spill area. */
+enum { MCPT_TRACE_CLOSEST = 0, MCPT_TRACE_ANY = 1 };
+typedef struct {
+    int32_t kind;        /* MCPT_TRACE_* */
+    float   t_max;       /* initial closest t for every ray when no per-ray array is given; 0 = FLT_MAX
+                            (QuinEngine's t_best is 10000); must be >= 0 */
+    int32_t lean;        /* 1: traversal counters compiled out (rays still counted) */
+    int32_t workgroups;  /* scheduling only, never changes a result: 0 = automatic; > 0 = at most this many
+                            persistent workgroups (1 makes one workgroup refill over the whole batch) */
+    int32_t refill;      /* scheduling only: ready lanes before a wave refills, 1..64; 0 = the extend's default
+                            for the scene's layout */
+} mcpt_trace_params;
+void mcpt_trace_params_default(mcpt_trace_params*);   /* all zeros spelled out: CLOSEST, FLT_MAX */
+
+/* n rays; d_o, d_d: n*3 floats each (mcpt_intersect's layout); d_t_max: n floats or NULL (p->t_max for all).
+ * CLOSEST: d_tri[i] = kd triangle id (mcpt_scene_copy_kd's numbering) or -1; d_hit (may be NULL): n*3 floats
+ * beta, gamma, t, and (0,0,0) on a miss -- exactly what mcpt_intersect returns for the same ray and t_max.
+ * Asynchronous on hip_stream.  p may be NULL (the defaults).  p->kind = MCPT_TRACE_ANY here is
+ * MCPT_E_UNSUPPORTED: the any-hit query reports a flag, not a triangle (mcpt_occluded_device). */
+int mcpt_trace_device(mcpt_scene*, const mcpt_trace_params* p, int64_t n, const float* d_o, const float* d_d,
+                      const float* d_t_max, int32_t* d_tri, float* d_hit, void* hip_stream);
+/* ANY (p->kind is ignored): d_occluded[i] = 1 if some triangle is accepted with t < t_max, else 0.  A lane
+ * stops at the first traversal step that leaves a hit; up to there the walk is the closest-hit walk, so
+ * d_occluded[i] == (d_tri[i] >= 0) of mcpt_trace_device for the same ray and t_max. */
+int mcpt_occluded_device(mcpt_scene*, const mcpt_trace_params* p, int64_t n, const float* d_o, const float* d_d,
+                         const float* d_t_max, uint8_t* d_occluded, void* hip_stream);
+/* host arrays, synchronous; stats may be NULL (rays, inner/leaf visits, leaf refs, tri tests, spills of
+ * this call; the counters mcpt_trace_stats_read reports are not touched) */
+int mcpt_occluded(mcpt_scene*, const mcpt_trace_params* p, int64_t n, const float* o, const float* d,
+                  const float* t_max, uint8_t* occluded, mcpt_render_stats* stats);
+/* counters of the device ray queries since the last read; waits for them and resets.  The render stats
+ * (mcpt_render_stats_read) are never touched by a ray query, and the other way round. */
+int mcpt_trace_stats_read(mcpt_scene*, mcpt_render_stats* out);
+/* allocate what ray queries need (above), so that the device entries allocate nothing afterwards */
+int mcpt_scene_reserve_rays(mcpt_scene*);
+
 #ifdef __cplusplus
 }
 #endif

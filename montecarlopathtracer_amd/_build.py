@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, os.environ.get("MCPT_LIB_NAME", "libmcpt.so"))
 SOURCES = ["host_model.cpp", "kd_cache.cpp", "capi.cpp", "render.hip", "wavefront.hip", "wavefront_primary.hip",
-           "aov.hip", "denoise.hip", "variance.hip", "denoise_var.hip", "adaptive.hip"]
+           "aov.hip", "denoise.hip", "variance.hip", "denoise_var.hip", "adaptive.hip", "rayquery.hip"]
 # per-source code generation (wavefront_primary.hip: the bounce-0 packet extend's
 # wave-uniform control flow as scalar branches; render.hip: GVN hoisting,
 # megakernel +1.4%, no effect on the wavefront kernels, and the global-memory
@@ -29,9 +29,11 @@ _WF_FLAGS = ["-mllvm", "-amdgpu-set-wave-priority=1", "-mllvm", "-two-entry-phi-
              "-mllvm", "-unroll-threshold=2000"]
 SOURCE_FLAGS = {"wavefront_primary.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=1"] + _WF_FLAGS,
                 "wavefront.hip": _WF_FLAGS,
+                # the ray queries' kernel is the extend's loop: it starts from the extend's flags
+                "rayquery.hip": _WF_FLAGS,
                 "render.hip": ["-mllvm", "-enable-gvn-hoist", "-mllvm", "-unroll-threshold=2000"]}
 HEADERS = ["host_model.hpp", "mcpt_device.hpp", "render_launch.hpp", "trace_device.hpp", "half_box.hpp",
-           "aov_device.hpp", "aov_launch.hpp", "variance_launch.hpp", "adaptive_launch.hpp", "partial_sum.hpp"]
+           "aov_device.hpp", "aov_launch.hpp", "variance_launch.hpp", "adaptive_launch.hpp", "partial_sum.hpp", "rayquery_launch.hpp"]
 ARCH = os.environ.get("MCPT_OFFLOAD_ARCH", "gfx950")
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-Wall",

@@ -106,6 +106,13 @@ class AdaptiveParamsC(C.Structure):
                 ("lum_floor", C.c_float), ("dilate", C.c_int32), ("force_list", C.c_int32)]
 
 
+class TraceParamsC(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("t_max", C.c_float), ("lean", C.c_int32), ("workgroups", C.c_int32),
+                ("refill", C.c_int32)]
+
+
+TRACE_CLOSEST = 0
+TRACE_ANY = 1
 OBJ_CVMCTRACER = 0
 OBJ_TINYOBJ = 1
 LAYOUT_AUTO = 0
@@ -182,6 +189,13 @@ _SIGS = {
                                        C.POINTER(RenderStats)]),
     "mcpt_render_adaptive_device": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(AdaptiveParamsC), _vp, _vp,
                                               _vp, _vp]),
+    "mcpt_trace_params_default": (None, [C.POINTER(TraceParamsC)]),
+    "mcpt_trace_device": (C.c_int, [_vp, C.POINTER(TraceParamsC), C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcpt_occluded_device": (C.c_int, [_vp, C.POINTER(TraceParamsC), C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "mcpt_occluded": (C.c_int, [_vp, C.POINTER(TraceParamsC), C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(RenderStats)]),
+    "mcpt_trace_stats_read": (C.c_int, [_vp, C.POINTER(RenderStats)]),
+    "mcpt_scene_reserve_rays": (C.c_int, [_vp]),
 }
 
 _lib = None

@@ -24,6 +24,7 @@
 #include "aov_launch.hpp"
 #include "half_box.hpp"
 #include "host_model.hpp"
+#include "rayquery_launch.hpp"
 #include "render_launch.hpp"
 #include "variance_launch.hpp"
 
@@ -216,6 +217,11 @@ struct mcpt_scene {
     void* ad_blocks = nullptr;
     size_t ad_blocks_bytes = 0;
     uint32_t* ad_host_n = nullptr;
+    // device ray queries (mcpt_trace_device, mcpt_occluded_device): tri_order on
+    // the device, and the queries' own counters -- two 64-B blocks, the device
+    // entries' (mcpt_trace_stats_read) and the synchronous host entry's
+    void* rq_order = nullptr;
+    void* rq_stats = nullptr;
 
     ~mcpt_scene() {
         if (!on_device) return;
@@ -232,7 +238,7 @@ struct mcpt_scene {
             (void)hipSetDevice(device);
         }
         for (void* p : {d_image, d_normals, ws.partial, ws.small, ws.spill, ws.fb, ws.wf, ws.tail, gather, gather_send, ad_list, ad_flags,
-                        ad_blocks})
+                        ad_blocks, rq_order, rq_stats})
             if (p) (void)hipFree(p);
         if (ad_host_n) (void)hipHostFree(ad_host_n);
         for (void* p : retired) (void)hipFree(p);
@@ -1127,6 +1133,93 @@ mcpt::DenoiseParams denoise_resolve(const mcpt_denoise_params* p) {
 bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return x < y + nb && y < x + na;
+}
+
+// ---- device ray queries (rayquery.hip) ----------------------------------------
+// The checks of a ray query that need no device, in the header's order; p
+// resolved (NULL = the defaults).  `closest`: mcpt_trace_device (kind is read).
+mcpt_trace_params trace_resolve(const mcpt_scene* s, const mcpt_trace_params* p, int64_t n, bool ptrs, bool closest) {
+    if (!s) throw mcpt::Error{MCPT_E_INVALID, "NULL scene"};
+    if (n < 0) throw mcpt::Error{MCPT_E_INVALID, "n must be >= 0"};
+    if (n && !ptrs) throw mcpt::Error{MCPT_E_INVALID, "NULL ray or result buffer"};
+    mcpt_trace_params q;
+    mcpt_trace_params_default(&q);
+    if (p) q = *p;
+    if (closest && q.kind != MCPT_TRACE_CLOSEST && q.kind != MCPT_TRACE_ANY)
+        throw mcpt::Error{MCPT_E_INVALID, "kind must be MCPT_TRACE_CLOSEST or MCPT_TRACE_ANY"};
+    if (!(q.t_max >= 0.0f)) throw mcpt::Error{MCPT_E_INVALID, "t_max must be >= 0 (0 = FLT_MAX)"};
+    if (q.lean != 0 && q.lean != 1) throw mcpt::Error{MCPT_E_INVALID, "lean must be 0 or 1"};
+    if (q.workgroups < 0) throw mcpt::Error{MCPT_E_INVALID, "workgroups must be >= 0"};
+    if (q.refill < 0 || q.refill > 64) throw mcpt::Error{MCPT_E_INVALID, "refill must be 0 (default) or 1..64"};
+    if (n >= (int64_t(1) << 31) / 3) throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many rays for one call"};
+    if (closest && q.kind == MCPT_TRACE_ANY)
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "kind MCPT_TRACE_ANY reports a flag, not a triangle: "
+                                              "call mcpt_occluded_device"};
+    if (!s->on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
+    if (q.t_max == 0.0f) q.t_max = FLT_MAX;
+    return q;
+}
+
+// What the ray queries need on the scene's (current) device: tri_order, the
+// counter blocks and the renders' stack spill area.  Nothing once they exist.
+void ensure_rays(mcpt_scene& s, bool capturing) {
+    const size_t lanes = static_cast<size_t>(mcpt::total_lanes_for(s.gpu.image_bytes, s.cus));
+    if (capturing && (!s.rq_order || !s.rq_stats))
+        throw mcpt::Error{MCPT_E_NOMEM, "the first ray query of a scene allocates: call mcpt_scene_reserve_rays "
+                                        "before capturing a graph"};
+    grow_ws(s, s.ws.spill, s.ws.spill_bytes, 32 * lanes * 16, capturing);
+    if (!s.rq_order) {
+        void* t = nullptr;
+        const size_t bytes = s.tri_order.size() * 4;
+        HIP_TRY(hipMalloc(&t, bytes ? bytes : 16));
+        hipError_t e = bytes ? hipMemcpy(t, s.tri_order.data(), bytes, hipMemcpyHostToDevice) : hipSuccess;
+        if (e != hipSuccess) {
+            (void)hipFree(t);
+            HIP_TRY(e);
+        }
+        s.rq_order = t;
+    }
+    if (!s.rq_stats) {
+        void* t = nullptr;
+        HIP_TRY(hipMalloc(&t, 128));
+        hipError_t e = hipMemset(t, 0, 128);
+        if (e == hipSuccess) e = mcpt::prepare_rayquery(s.gpu);   // (the kernels' code object loaded now)
+        if (e != hipSuccess) {
+            (void)hipFree(t);
+            HIP_TRY(e);
+        }
+        s.rq_stats = t;
+    }
+}
+
+// One query on st: closest hit (d_occ NULL) or any hit.  host_block: count
+// into the host entry's counter block.
+void rays_async(mcpt_scene& s, const mcpt_trace_params& q, int64_t n, const float* d_o, const float* d_d,
+                const float* d_t_max, int32_t* d_tri, float* d_hit, uint8_t* d_occ, bool host_block, hipStream_t st) {
+    ensure_rays(s, stream_capturing(st));
+    mcpt::RayQueryParams rq{};
+    rq.scene = s.gpu;
+    rq.o = d_o;
+    rq.d = d_d;
+    rq.t_max = d_t_max;
+    rq.tri = d_tri;
+    rq.hit = d_hit;
+    rq.occ = d_occ;
+    rq.tri_order = static_cast<const uint32_t*>(s.rq_order);
+    rq.spill = static_cast<uint4*>(s.ws.spill);
+    rq.spill_stride = static_cast<uint32_t>(mcpt::total_lanes_for(s.gpu.image_bytes, s.cus));
+    rq.stats = static_cast<unsigned long long*>(s.rq_stats) + (host_block ? 8 : 0);
+    rq.n = static_cast<uint32_t>(n);
+    rq.refill = q.refill;
+    rq.best_init = q.t_max;
+    HIP_TRY(mcpt::launch_rayquery(rq, d_occ != nullptr, q.lean != 0, s.cus, q.workgroups, st));
+}
+
+void stats_from_counters(const unsigned long long c[8], mcpt_render_stats& st) {
+    std::memset(&st, 0, sizeof st);
+    st.devices = 1;
+    st.rays = c[0]; st.inner_visits = c[2]; st.leaf_visits = c[3]; st.leaf_refs = c[4];
+    st.tri_tests = c[5]; st.stack_spills = c[7];
 }
 
 // What mcpt_render_var[_device] asks of a render beyond mcpt_render's own
@@ -2078,6 +2171,113 @@ int mcpt_denoise_var(const mcpt_denoise_var_params* p, const float* color_rgb, c
         HIP_TRY(hipMemcpy(rgba.data(), buf + 4 * bytes, bytes, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < npx; ++i)
             for (int c = 0; c < 3; ++c) out_rgb[3 * i + c] = rgba[4 * i + c];
+        return MCPT_OK;
+    });
+}
+
+void mcpt_trace_params_default(mcpt_trace_params* p) {
+    if (!p) return;
+    p->kind = MCPT_TRACE_CLOSEST;
+    p->t_max = 0.0f;
+    p->lean = 0;
+    p->workgroups = 0;
+    p->refill = 0;
+}
+
+int mcpt_trace_device(mcpt_scene* s, const mcpt_trace_params* p, int64_t n, const float* d_o, const float* d_d,
+                      const float* d_t_max, int32_t* d_tri, float* d_hit, void* hip_stream) {
+    return guarded([&]() -> int {
+        const mcpt_trace_params q = trace_resolve(s, p, n, d_o && d_d && d_tri, true);
+        const size_t N = static_cast<size_t>(n);
+        const void* in[3] = {d_o, d_d, d_t_max};
+        const size_t in_bytes[3] = {N * 12, N * 12, d_t_max ? N * 4 : 0};
+        for (int i = 0; i < 3; ++i)
+            if (ranges_overlap(d_tri, N * 4, in[i], in_bytes[i]) ||
+                (d_hit && ranges_overlap(d_hit, N * 12, in[i], in_bytes[i])))
+                return fail(MCPT_E_INVALID, "an output buffer overlaps an input of the call");
+        if (d_hit && ranges_overlap(d_tri, N * 4, d_hit, N * 12))
+            return fail(MCPT_E_INVALID, "the triangle and hit buffers overlap");
+        if (!n) return MCPT_OK;
+        set_device(*s);                   // (a multi-device scene: devices[0], the primary)
+        rays_async(*s, q, n, d_o, d_d, d_t_max, d_tri, d_hit, nullptr, false, static_cast<hipStream_t>(hip_stream));
+        return MCPT_OK;
+    });
+}
+
+int mcpt_occluded_device(mcpt_scene* s, const mcpt_trace_params* p, int64_t n, const float* d_o, const float* d_d,
+                         const float* d_t_max, uint8_t* d_occluded, void* hip_stream) {
+    return guarded([&]() -> int {
+        const mcpt_trace_params q = trace_resolve(s, p, n, d_o && d_d && d_occluded, false);
+        const size_t N = static_cast<size_t>(n);
+        if (ranges_overlap(d_occluded, N, d_o, N * 12) || ranges_overlap(d_occluded, N, d_d, N * 12) ||
+            ranges_overlap(d_occluded, N, d_t_max, d_t_max ? N * 4 : 0))
+            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+        if (!n) return MCPT_OK;
+        set_device(*s);
+        rays_async(*s, q, n, d_o, d_d, d_t_max, nullptr, nullptr, d_occluded, false,
+                   static_cast<hipStream_t>(hip_stream));
+        return MCPT_OK;
+    });
+}
+
+// rays, t_max and the flags are staged in the scene's host-render buffer
+int mcpt_occluded(mcpt_scene* s, const mcpt_trace_params* p, int64_t n, const float* o, const float* d,
+                  const float* t_max, uint8_t* occluded, mcpt_render_stats* stats) {
+    return guarded([&]() -> int {
+        const mcpt_trace_params q = trace_resolve(s, p, n, o && d && occluded, false);
+        const size_t N = static_cast<size_t>(n);
+        if (ranges_overlap(occluded, N, o, N * 12) || ranges_overlap(occluded, N, d, N * 12) ||
+            ranges_overlap(occluded, N, t_max, t_max ? N * 4 : 0))
+            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+        mcpt_render_stats st;
+        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (n) {
+            set_device(*s);
+            ensure_buf(s->ws.fb, s->ws.fb_bytes, N * 29);
+            float* d_o = static_cast<float*>(s->ws.fb);
+            float* d_d = d_o + 3 * N;
+            float* d_t = d_d + 3 * N;
+            uint8_t* d_occ = reinterpret_cast<uint8_t*>(d_t + N);
+            HIP_TRY(hipMemcpy(d_o, o, N * 12, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_d, d, N * 12, hipMemcpyHostToDevice));
+            if (t_max) HIP_TRY(hipMemcpy(d_t, t_max, N * 4, hipMemcpyHostToDevice));
+            ensure_rays(*s, false);
+            unsigned long long* blk = static_cast<unsigned long long*>(s->rq_stats) + 8;
+            HIP_TRY(hipMemset(blk, 0, 64));
+            rays_async(*s, q, n, d_o, d_d, t_max ? d_t : nullptr, nullptr, nullptr, d_occ, true, nullptr);
+            HIP_TRY(hipStreamSynchronize(nullptr));
+            HIP_TRY(hipMemcpy(occluded, d_occ, N, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(c, blk, 64, hipMemcpyDeviceToHost));
+        }
+        stats_from_counters(c, st);
+        if (stats) *stats = st;
+        return MCPT_OK;
+    });
+}
+
+int mcpt_trace_stats_read(mcpt_scene* s, mcpt_render_stats* out) {
+    return guarded([&]() -> int {
+        if (!s || !s->on_device) return fail(MCPT_E_INVALID, "scene is not on a device");
+        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (s->rq_stats) {                // (no query yet: zeros)
+            DeviceGuard guard;
+            set_device(*s);
+            // the queries may run on any stream: wait for the device, then read and clear
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(hipMemcpy(c, s->rq_stats, 64, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemset(s->rq_stats, 0, 64));
+        }
+        if (out) stats_from_counters(c, *out);
+        return MCPT_OK;
+    });
+}
+
+int mcpt_scene_reserve_rays(mcpt_scene* s) {
+    return guarded([&]() -> int {
+        if (!s || !s->on_device) return fail(MCPT_E_INVALID, "scene is not on a device");
+        DeviceGuard guard;
+        set_device(*s);
+        ensure_rays(*s, false);
         return MCPT_OK;
     });
 }

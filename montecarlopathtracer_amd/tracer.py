@@ -341,6 +341,59 @@ class Scene:
                                    tri.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(hit), C.byref(st)))
         return tri, hit, st.as_dict()
 
+    def trace_device(self, n: int, o_ptr: int, d_ptr: int, tri_ptr: int, hit_ptr: int = 0, t_max_ptr: int = 0,
+                     stream_ptr: int = 0, **params):
+        """Closest hits of n rays in device memory (mcpt_trace_device), asynchronous on the
+        stream: o / d (n, 3) float32, tri (n,) int32 = kd triangle id or -1, hit (n, 3) float32
+        beta gamma t (optional), t_max (n,) float32 (optional: params' t_max for all).  What
+        ``intersect`` returns for the same rays, without leaving the device.  params: the fields
+        of ``trace_params``.  Run it on the stream of the scene's renders, or synchronize."""
+        check(lib().mcpt_trace_device(self.handle, C.byref(trace_params(**params)), int(n), C.c_void_p(o_ptr),
+                                      C.c_void_p(d_ptr), C.c_void_p(t_max_ptr), C.c_void_p(tri_ptr),
+                                      C.c_void_p(hit_ptr), C.c_void_p(stream_ptr)))
+
+    def occluded_device(self, n: int, o_ptr: int, d_ptr: int, occluded_ptr: int, t_max_ptr: int = 0,
+                        stream_ptr: int = 0, **params):
+        """Any-hit query of n rays in device memory (mcpt_occluded_device): occluded (n,) uint8 =
+        1 where some triangle is hit with t < t_max -- (tri >= 0) of ``trace_device`` for the same
+        rays, from a walk that stops at its first accepted triangle."""
+        check(lib().mcpt_occluded_device(self.handle, C.byref(trace_params(**params)), int(n), C.c_void_p(o_ptr),
+                                         C.c_void_p(d_ptr), C.c_void_p(t_max_ptr), C.c_void_p(occluded_ptr),
+                                         C.c_void_p(stream_ptr)))
+
+    def occluded(self, o: np.ndarray, d: np.ndarray, t_max=None, **params):
+        """Any-hit query of host rays (mcpt_occluded), synchronous: (uint8 array, counters of this
+        call).  t_max: None, a scalar for all rays, or one value per ray."""
+        o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise McptError(-1, "o and d must have the same shape")
+        n = o.shape[0]
+        tm = None
+        if t_max is not None and np.ndim(t_max) == 0:
+            params = {**params, "t_max": float(t_max)}
+        elif t_max is not None:
+            tm = np.ascontiguousarray(t_max, np.float32).reshape(-1)
+            if tm.shape[0] != n:
+                raise McptError(-1, "t_max must hold one value per ray")
+        occ = np.zeros(n, np.uint8)
+        st = RenderStats()
+        check(lib().mcpt_occluded(self.handle, C.byref(trace_params(**params)), n, _fptr(o), _fptr(d),
+                                  _fptr(tm) if tm is not None else None, occ.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                  C.byref(st)))
+        return occ, st.as_dict()
+
+    def trace_stats(self) -> dict:
+        """Counters of the device ray queries since the last read (mcpt_trace_stats_read): waits
+        for them and resets.  The render stats (``stats``) are separate."""
+        st = RenderStats()
+        check(lib().mcpt_trace_stats_read(self.handle, C.byref(st)))
+        return st.as_dict()
+
+    def reserve_rays(self):
+        """Allocate what the ray queries need (mcpt_scene_reserve_rays): later queries allocate nothing."""
+        check(lib().mcpt_scene_reserve_rays(self.handle))
+
     def render_unit_counters(self, params: RenderParams):
         """Synchronous render returning (fb, per-unit counters (units, 4): rays, inner, leaf, tests)."""
         n = params.output_pixels()
@@ -489,6 +542,16 @@ def adaptive_params(max_passes: int = 0, min_passes: int = 0, threshold: float =
     window radius 1; dilate < 0 = no window)."""
     return _capi.AdaptiveParamsC(int(max_passes), int(min_passes), float(threshold), float(lum_floor), int(dilate),
                                  int(force_list))
+
+
+TRACE_KINDS = {"closest": _capi.TRACE_CLOSEST, "any": _capi.TRACE_ANY}
+
+
+def trace_params(kind="closest", t_max: float = 0.0, lean: bool = False, workgroups: int = 0,
+                 refill: int = 0) -> "_capi.TraceParamsC":
+    """mcpt_trace_params; t_max 0 = FLT_MAX, workgroups / refill 0 = automatic (scheduling only)."""
+    k = TRACE_KINDS[kind] if isinstance(kind, str) else int(kind)
+    return _capi.TraceParamsC(k, float(t_max), int(lean), int(workgroups), int(refill))
 
 
 def denoise_var_params(width: int, height: int, sigma_l: float = 0.0, **params) -> "_capi.DenoiseVarParamsC":
