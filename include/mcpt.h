@@ -293,6 +293,11 @@ int mcpt_scene_create_ex(const mcpt_model* m, const mcpt_scene_options* options,
                          int32_t* cache_hit);
 void mcpt_scene_destroy(mcpt_scene* s);
 int mcpt_scene_get_info(const mcpt_scene* s, mcpt_scene_info* out);
+/* Emitter boxes of the wavefront's terminal cull (1..8: one per emitter
+ * geometry), or 0 when the scene does not allow it: a non-emitter with a Ka
+ * other than zero, a non-finite Kd or Ks, no emitter, or more than 8.  (Its own
+ * entry: mcpt_scene_info keeps its ABI 9 size.) */
+int mcpt_scene_terminal_cull_boxes(const mcpt_scene* s);
 /* KD tree as built (BFS order, QuinEngine/RTX/ShaderResource.hpp:128-179):
  * nodes n_nodes*12 words {left,right,axis(0 leaf,1..3),split bits,min[3],max[3],
  * leaf_begin,leaf_count}; leaf ids = kd triangle ids; kd_tris = kd id -> OBJ

@@ -168,6 +168,11 @@ struct mcpt_scene {
     std::vector<unsigned char> image;   // host copy of the device image
     std::vector<uint32_t> tri_order;    // image triangle slot -> kd id
     mcpt::GpuScene gpu{};
+    // terminal cull: emitter boxes as box_hit reads them (fp16 rounded outward);
+    // n_cull_boxes == 0: the scene does not allow the cull (host_model.hpp)
+    uint32_t n_cull_boxes = 0;
+    uint32_t cull_box[mcpt::kMaxCullBoxes][3] = {};
+    float cull_gain = 0.0f;             // the largest |Kd| or |Ks| component (finite when there are boxes)
     void* d_image = nullptr;
     void* d_normals = nullptr;
     Workspace ws;
@@ -459,6 +464,22 @@ void build_image(mcpt_scene& s, bool force_global) {
     if (nn) {
         for (int a = 0; a < 3; ++a) { gs.root_min[a] = hs.nodes[0].bmin[a]; gs.root_max[a] = hs.nodes[0].bmax[a]; }
     }
+    // terminal cull: the emitter boxes, packed like a pair record's child box
+    // (lo.x lo.y | lo.z hi.x | hi.y hi.z)
+    float eb[mcpt::kMaxCullBoxes][6];
+    s.n_cull_boxes = static_cast<uint32_t>(mcpt::terminal_cull_boxes(hs, eb, mcpt::kMaxCullBoxes));
+    for (uint32_t b = 0; b < s.n_cull_boxes; ++b) {
+        uint16_t hb[6];
+        for (int a = 0; a < 3; ++a) {
+            hb[a] = mcpt::f32_to_f16_dir(eb[b][a], -1);
+            hb[3 + a] = mcpt::f32_to_f16_dir(eb[b][3 + a], +1);
+        }
+        std::memcpy(s.cull_box[b], hb, 12);
+    }
+    s.cull_gain = 0.0f;
+    for (const mcpt::Geometry& ge : hs.geoms)
+        for (float k : {ge.Kd.x, ge.Kd.y, ge.Kd.z, ge.Ks.x, ge.Ks.y, ge.Ks.z})
+            if (std::fabs(k) > s.cull_gain) s.cull_gain = std::fabs(k);
 }
 
 void ensure_buf(void*& p, size_t& have, size_t need) {
@@ -804,6 +825,15 @@ void prepare_wavefront(mcpt_scene& s, const Plan& pl, int sets, mcpt::WfParams* 
         w.refill_thresh = clamp_i(pl.wf_refill, 1, 64);
         w.group_shift = pl.wf_group_shift;
         w.sort = pl.wf_sort;
+#if MCPT_TERMINAL_CULL
+        // a culled ray stands for color * (0 * illum) = 0: illum must be finite,
+        // and so must the throughput, a product of at most max_depth Kd / Ks
+        // components (each rounding grows it by 2^-24 at most: 2^127 leaves room)
+        const bool zero = std::isfinite(pl.kp.illum) &&
+                          std::log2(std::max(1.0, double(s.cull_gain))) * pl.kp.max_depth < 127.0;
+        w.n_cull_boxes = zero ? s.n_cull_boxes : 0u;
+        std::memcpy(w.cull_box, s.cull_box, sizeof w.cull_box);
+#endif
     }
 }
 
@@ -1622,6 +1652,9 @@ static int scene_create_impl(const mcpt_model* m, mcpt_scene** out, bool device,
             for (size_t i = 1; i < devs.size(); ++i) {
                 auto R = std::make_unique<mcpt_scene>();
                 R->gpu = s->gpu;
+                R->n_cull_boxes = s->n_cull_boxes;
+                std::memcpy(R->cull_box, s->cull_box, sizeof s->cull_box);
+                R->cull_gain = s->cull_gain;
                 upload(*R, devs[i], s->image, nrm);
                 HIP_TRY(hipStreamCreateWithFlags(&R->stream, hipStreamNonBlocking));
                 HIP_TRY(hipEventCreateWithFlags(&R->done, hipEventDisableTiming));
@@ -1663,6 +1696,10 @@ int mcpt_scene_get_info(const mcpt_scene* s, mcpt_scene_info* out) {
     out->n_devices = s->on_device ? 1 + static_cast<int64_t>(s->replicas.size()) : 0;
     out->kd_build = s->hs.kd_build;
     return MCPT_OK;
+}
+
+int mcpt_scene_terminal_cull_boxes(const mcpt_scene* s) {
+    return s && MCPT_TERMINAL_CULL ? static_cast<int>(s->n_cull_boxes) : 0;
 }
 
 int mcpt_scene_copy_kd(const mcpt_scene* s, uint32_t* nodes, uint32_t* leaf_ids, int32_t* kd_tris, float* geoms) {

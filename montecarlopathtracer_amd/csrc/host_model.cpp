@@ -459,7 +459,46 @@ void build_host_scene(const ObjModel& m, HostScene& hs, const char* kd_cache_dir
 }
 
 // ---------------------------------------------------------------------------
-// KD build (KDTree.hpp:58-287).  Literal std::min/std::max forms keep the
+// Terminal cull: may the path loop's last query (CUTracer.cu:162-175, which
+// adds color * Ka(hit) * illum) be skipped for a ray that can reach no emitter?
+// Yes when only emitters (any Ka component > 0, CUTracer.cu:111) have a Ka
+// other than zero -- a negative or NaN Ka on any other geometry is radiance the
+// query must collect -- and every Kd and Ks is finite, so the throughput the
+// zero multiplies comes from finite factors.  Then one AABB per emitter
+// geometry over its triangles' vertices (all finite, build_host_scene).
+int terminal_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes) {
+    auto finite3 = [](const Vec3& v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); };
+    std::vector<int> box_of(hs.geoms.size(), -1);
+    int n = 0;
+    for (size_t g = 0; g < hs.geoms.size(); ++g) {
+        const Geometry& ge = hs.geoms[g];
+        if (!finite3(ge.Kd) || !finite3(ge.Ks)) return 0;
+        if (ge.Ka.x > 0 || ge.Ka.y > 0 || ge.Ka.z > 0) {
+            if (n == max_boxes) return 0;          // (boxes are not merged)
+            for (int a = 0; a < 3; ++a) {
+                boxes[n][a] = INFINITY;            // empty until a triangle widens it: always culled
+                boxes[n][3 + a] = -INFINITY;
+            }
+            box_of[g] = n++;
+        } else if (!(ge.Ka.x == 0 && ge.Ka.y == 0 && ge.Ka.z == 0)) {
+            return 0;
+        }
+    }
+    for (size_t k = 0; k < hs.kd_geom.size(); ++k) {
+        const int b = box_of[hs.kd_geom[k]];
+        if (b < 0) continue;
+        const float* v = &hs.kd_verts[9 * k];
+        for (int j = 0; j < 3; ++j)
+            for (int a = 0; a < 3; ++a) {
+                boxes[b][a] = std::min(boxes[b][a], v[3 * j + a]);
+                boxes[b][3 + a] = std::max(boxes[b][3 + a], v[3 * j + a]);
+            }
+    }
+    return n;
+}
+
+// ---------------------------------------------------------------------------
+// KD build (KDTree.hpp:58-287). Literal std::min/std::max forms keep the
 // signed-zero/NaN behaviour of the reference; float expressions keep its
 // operand order (the library is compiled with -ffp-contract=off).
 namespace {

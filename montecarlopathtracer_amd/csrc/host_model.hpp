@@ -80,6 +80,11 @@ struct HostScene {
 // kd_build: MCPT_KD_BUILD_REFERENCE (KDTree.hpp) or MCPT_KD_BUILD_SAH.
 void build_host_scene(const ObjModel& m, HostScene& out, const char* kd_cache_dir = nullptr,
                       int* cache_hit = nullptr, int kd_build = 0);
+// Terminal cull (render_launch.hpp MCPT_TERMINAL_CULL): the number of emitter
+// geometries and their AABBs (min xyz, max xyz) if the scene allows the cull --
+// every non-emitter has Ka == 0 exactly, every Kd and Ks is finite, and there
+// are 1..max_boxes emitter geometries -- else 0.
+int terminal_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes);
 // on-disk KD cache (kd_cache.cpp): load returns false unless a valid file exists
 // (files are keyed by the vertices and the build rule)
 bool kd_cache_load(const std::string& dir, const std::vector<float>& tri_verts, std::vector<KdNode>& nodes,

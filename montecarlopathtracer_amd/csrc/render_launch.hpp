@@ -34,6 +34,17 @@ constexpr int kGlobalBlocksPerCu = 4;
 #endif
 constexpr int kWfGlobalSegsPerCu = MCPT_WF_GLOBAL_SEGS;
 constexpr size_t kMaxLds = 160 * 1024;   // gfx950 LDS per CU
+// Terminal cull (wavefront, lean CV renders): after max_depth scatters the path
+// loop traces once more and adds color * Ka(hit) * illum.  In a scene whose
+// non-emitters all have Ka == 0 a terminal ray that cannot reach an emitter
+// adds exactly 0, so wf_cull_terminal (wavefront.hip) takes every ray that
+// misses all emitter boxes out of the last queue before its closest-hit walk
+// (scene01: ~99% of the last bounce's rays, 6.7% of the frame's extend time).
+// 0: the pipeline without it, the same kernels as before it (A/B builds).
+#ifndef MCPT_TERMINAL_CULL
+#define MCPT_TERMINAL_CULL 1
+#endif
+constexpr int kMaxCullBoxes = 8;         // emitter geometries a scene may have and keep the cull
 
 struct GpuGeom {
     float Ka[3], Kd[3], Ks[3];
@@ -177,6 +188,13 @@ struct WfParams {
     int32_t refill_thresh;               // idle lanes before an extend wave refills
     int32_t sort;                        // 1: shade sorts each block of slots by material first
     uint32_t xcd_deal;                   // 1: groups dealt to segments by XCD (global-memory scenes, seg_of)
+    // terminal cull: the scene's emitter boxes (one per emitter geometry, fp16
+    // rounded outward, packed as box_hit reads them); 0 boxes = no cull.  Last in
+    // the kernel arguments, outside the scene image: no offset before them moves
+#if MCPT_TERMINAL_CULL
+    uint32_t n_cull_boxes;
+    uint32_t cull_box[kMaxCullBoxes][3];
+#endif
 };
 
 size_t lds_bytes_in_lds(uint32_t image_bytes, int S);

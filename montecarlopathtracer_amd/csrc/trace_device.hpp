@@ -335,6 +335,30 @@ __device__ __forceinline__ bool box_hit(const RayState& r, uint32_t b0, uint32_t
     return !(lo * kEpsLo > hi * kEpsHi);
 }
 
+// Terminal cull (render_launch.hpp MCPT_TERMINAL_CULL): can the closest hit of
+// ray (o, d) lie on an emitter?  box_hit itself, on the segment (0, best_init]
+// against each of the scene's n emitter boxes (kernel arguments: scalar
+// operands, n wave-uniform).  The child-box cull's argument: a hit the walk
+// could accept on an emitter triangle lies inside that triangle's box, hence
+// inside its geometry's stored one, and the margins cover the rounding -- a ray
+// that fails every box has no emitter as its closest hit.  inv: the IEEE
+// reciprocals of d, as begin_ray computes them.
+__device__ __forceinline__ bool emitter_reachable(V3 o, V3 d, V3 inv, float best_init,
+                                                  const uint32_t (&boxes)[kMaxCullBoxes][3], uint32_t n) {
+    RayState r;                               // (box_hit reads o, d, the reciprocals and best)
+    r.o = o;
+    r.d = d;
+    r.ix = inv.x;
+    r.iy = inv.y;
+    r.iz = inv.z;
+    r.best = best_init;
+    bool hit = false;
+    // (rolled: unrolled over the 8 possible boxes the caller took 78 VGPRs instead of 34)
+#pragma unroll 1
+    for (uint32_t i = 0; i < n; i++) hit |= box_hit(r, boxes[i][0], boxes[i][1], boxes[i][2]);
+    return hit;
+}
+
 // a loaded value made an asm output: its wait sits here, not at a later join
 __device__ __forceinline__ uint4 settle4(uint4 v) {
     asm volatile("v_mov_b32 %0, %0\n\tv_mov_b32 %1, %1\n\tv_mov_b32 %2, %2\n\tv_mov_b32 %3, %3"

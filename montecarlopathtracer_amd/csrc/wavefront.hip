@@ -20,6 +20,8 @@
 //               compaction by one LDS atomic per wave); with the material sort
 //               (wf_sort = 1) each block is first sorted by material in LDS, so
 //               a wave runs one material branch
+//   cull        lean renders, before the last extend: the terminal query's rays
+//               that can reach no emitter leave the queue (wf_cull_terminal)
 //   accumulate  per pixel, the batch's samples summed in sample order into the
 //               same [chunk][pixel] partial sums the megakernel writes
 // followed by the megakernel's reduction.  A path never leaves its segment,
@@ -926,6 +928,71 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
     if (threadIdx.x == 0) nx->queued = lnext;
 }
 
+#if MCPT_TERMINAL_CULL
+// ---- terminal cull: the last queue without the rays that cannot add radiance --
+// Runs between the last scattering shade and the terminal query's extend
+// (lean renders; render_launch.hpp MCPT_TERMINAL_CULL), one workgroup per
+// segment on its queue wf.bounce.  CV: a ray that can reach no emitter box
+// (emitter_reachable) would add color * 0 * illum whatever it hits; QE: the
+// hit of the query at depth 3 * max_depth is never read.  Such a ray's path
+// gets the zero radiance its shade would write and leaves the queue; the kept
+// rays are compacted in place, block by block -- a block's slots are all read
+// before any of them is overwritten, and kept rays only move toward the
+// queue's start -- and the segment's queue length becomes their count.  The
+// rays stay counted (shade counted them when it made them).
+// (A kernel of its own: the same test inside the shade took the queue-order
+// shade from 77 to 125 VGPRs and put the sorting shade into scratch.)
+// (512 threads at <= 80 VGPRs, as the shade: two of its waves per SIMD fit beside the LDS extend's four)
+constexpr int kCullBlock = 512;
+__global__ void __launch_bounds__(kCullBlock, 6) wf_cull_terminal(const KernelParams kp, const WfParams wf) {
+    const uint32_t g = blockIdx.x;
+    if (g >= wf.nseg) return;
+    __shared__ uint32_t lnext;
+    WfCounters* cn = wf.cnt + (size_t)wf.bounce * wf.nseg + g;
+    const uint32_t total = cn->queued;
+    if (threadIdx.x == 0) lnext = 0;
+    __syncthreads();
+    const size_t seg0 = (size_t)g * wf.seg;
+    float4* q = wf.q[wf.bounce & 1];
+    const uint32_t qs = wf.slot_stride;
+    const bool qe = kp.mode == kModeQE;
+    const int lane = (int)(threadIdx.x & 63u);
+    for (uint32_t base = 0; base < total; base += kCullBlock) {     // block-uniform trip count
+        const uint32_t i = base + threadIdx.x;
+        bool keep = false;
+        float4 o4 = make_float4(0, 0, 0, 0), d4 = o4, ps = o4;
+        if (i < total) {
+            const size_t js = seg0 + i;
+            o4 = ldq(&q[qf(js, kQO, qs)]);
+            if (!qe) {
+                d4 = ldq(&q[qf(js, kQD, qs)]);
+                const V3 d = xyz(d4);
+                keep = emitter_reachable(xyz(o4), d, v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), kp.best_init,
+                                         wf.cull_box, wf.n_cull_boxes);
+                if (keep) ps = ldq(&q[qf(js, kQPS, qs)]);
+            }
+            if (!keep) stq(&wf.radiance[__float_as_uint(o4.w)], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+        }
+        __syncthreads();                                            // the block's slots are read
+        const uint64_t m = __ballot(keep);
+        if (m) {
+            const int leader = __ffsll((unsigned long long)m) - 1;
+            uint32_t b0 = 0;
+            if (lane == leader) b0 = atomicAdd(&lnext, (uint32_t)__popcll(m));
+            b0 = lane_bcast(b0, leader);
+            if (keep) {
+                const size_t ji = seg0 + b0 + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+                stq(&q[qf(ji, kQO, qs)], o4);
+                stq(&q[qf(ji, kQD, qs)], d4);
+                stq(&q[qf(ji, kQPS, qs)], ps);
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) cn->queued = lnext;
+}
+#endif
+
 // ---- accumulate: samples of the batch in sample order -> partial sums -------
 // A batch holds wf.ns / wf.nsc whole chunks of nsc samples each (blockIdx.y).
 __global__ void __launch_bounds__(256) wf_accumulate(const KernelParams kp, const WfParams wf) {
@@ -1111,6 +1178,18 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
                 else
                     hipLaunchKernelGGL(shade_kernel<256>(geo_bytes != 0, sortb), dim3(nseg), dim3(256), geo_bytes, bs, kb, wf);
                 e = hipGetLastError();
+#if MCPT_TERMINAL_CULL
+                // the terminal query's queue (CV: a scene with emitter boxes; QE:
+                // every ray) loses the rays whose hit adds nothing; counting
+                // renders keep the full walk, so their visit counters stay the oracle's
+                const bool qe = kb.mode == kModeQE;
+                if (e == hipSuccess && kb.lean && b + 1 < max_bounces && b + 1 == (qe ? 3 : 1) * kb.max_depth &&
+                    (qe || wf.n_cull_boxes)) {
+                    wf.bounce = b + 1;
+                    hipLaunchKernelGGL(wf_cull_terminal, dim3(nseg), dim3(kCullBlock), 0, bs, kb, wf);
+                    e = hipGetLastError();
+                }
+#endif
             }
             if (e != hipSuccess) break;
             hipLaunchKernelGGL(wf_accumulate, dim3((wf.nb + 255u) / 256u, ncb), dim3(256), 0, bs, kb, wf);

@@ -299,7 +299,10 @@ class Scene:
     def info(self) -> dict:
         i = _capi.SceneInfo()
         check(lib().mcpt_scene_get_info(self.handle, C.byref(i)))
-        return {n: int(getattr(i, n)) for n, _ in i._fields_}
+        d = {n: int(getattr(i, n)) for n, _ in i._fields_}
+        # emitter boxes of the wavefront's terminal cull; 0: the scene does not allow it
+        d["terminal_cull_boxes"] = int(lib().mcpt_scene_terminal_cull_boxes(self.handle))
+        return d
 
     def kd(self):
         """(nodes (n,12) u32, leaf ids, kd_tris, geoms (g,14) f32) as built."""

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Per-bounce extend / shade times from a rocprofv3 kernel trace of wavefront
 renders on ONE stream (kernels serialized): dispatches are grouped per batch
-(wf_generate starts one) and indexed by bounce.  usage: wf_bounce_times.py DIR"""
+(wf_generate, or the generate-free bounce-0 extend wf_extend_primary, starts
+one) and indexed by bounce; wf_cull_terminal (the terminal cull in front of the
+last extend) is summed on its own.  usage: wf_bounce_times.py DIR"""
 import csv
 import glob
 import sys
@@ -16,12 +18,15 @@ def main(d):
                 rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
     rows.sort()
     ext, sh = defaultdict(list), defaultdict(list)
+    cull = []
     b_ext = b_sh = -1
     batches = 0
     for t0, t1, name in rows:
-        if "wf_generate" in name:
+        if "wf_generate" in name or "wf_extend_primary" in name:
             b_ext = b_sh = -1
             batches += 1
+        if "wf_cull_terminal" in name:
+            cull.append((t1 - t0) / 1e6)
         elif "wf_extend" in name:
             b_ext += 1
             ext[b_ext].append((t1 - t0) / 1e6)
@@ -34,6 +39,9 @@ def main(d):
         print(f"bounce {b}: extend {sum(e) / batches:8.2f} ms/frame-batch-avg x{len(e)}  "
               f"(per dispatch {sum(e) / len(e):.3f})  shade {sum(s) / max(len(s), 1):.3f}")
     print("extend total per batch", sum(sum(v) for v in ext.values()) / batches)
+    print("shade total per batch", sum(sum(v) for v in sh.values()) / batches)
+    if cull:
+        print(f"terminal cull per batch {sum(cull) / batches:.3f} x{len(cull)}")
 
 
 if __name__ == "__main__":
