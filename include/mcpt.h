@@ -298,6 +298,13 @@ int mcpt_scene_get_info(const mcpt_scene* s, mcpt_scene_info* out);
  * other than zero, a non-finite Kd or Ks, no emitter, or more than 8.  (Its own
  * entry: mcpt_scene_info keeps its ABI 9 size.) */
 int mcpt_scene_terminal_cull_boxes(const mcpt_scene* s);
+/* Primary lists of the scene's last render (wavefront, lean CV renders of a
+ * scene in LDS with 8x8 tiles): out[0..2] = the owned tiles whose candidate
+ * list is empty (no primary ray made), holds 1..K triangles (tested straight
+ * from the list) or more than K (the packet walk), out[3] = K (0: built
+ * without the lists).  All three are 0 after a render that did not use the
+ * lists.  Waits for the device.  (Its own entry, as the one above.) */
+int mcpt_scene_primary_tile_classes(mcpt_scene* s, uint32_t out[4]);
 /* KD tree as built (BFS order, QuinEngine/RTX/ShaderResource.hpp:128-179):
  * nodes n_nodes*12 words {left,right,axis(0 leaf,1..3),split bits,min[3],max[3],
  * leaf_begin,leaf_count}; leaf ids = kd triangle ids; kd_tris = kd id -> OBJ

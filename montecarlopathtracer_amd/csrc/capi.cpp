@@ -554,8 +554,12 @@ int wavefront_streams(const mcpt_scene& s, uint64_t work, const mcpt_render_para
 // the radiance (the material sort too: it sorts in LDS).  Segments hold
 // whole path groups (2^group_shift paths: 64 for LDS scenes, up to 2^14 for
 // global-memory ones): up to one group of slots per segment beyond the paths.
+// Each stream's part also has room for the primary lists' tile records
+// (render_launch.hpp MCPT_PRIMARY_LISTS; one record per owned 8x8 tile, only
+// the first stream's is used), so the records come out of the same plan and
+// reservation as the queues.
 struct WfLayout {
-    size_t cap_slots, f4, queue, need;
+    size_t cap_slots, f4, queue, tiles, need;
 };
 WfLayout wf_layout(const mcpt_scene& s, const Plan& pl, uint64_t cap) {
     const mcpt::KernelParams& kp = pl.kp;
@@ -567,7 +571,11 @@ WfLayout wf_layout(const mcpt_scene& s, const Plan& pl, uint64_t cap) {
     l.cap_slots = size_t(cap) + (nseg << pl.wf_group_shift);
     l.f4 = l.cap_slots * 16;
     l.queue = al256(3 * l.f4 + 4 * l.cap_slots);
-    l.need = al256(2 * l.queue + l.f4 + bounces * sizeof(mcpt::WfCounters) + 256);
+    l.tiles = 0;
+#if MCPT_PRIMARY_LISTS
+    if (kp.tile == 8) l.tiles = al256(size_t(kp.npix_local >> 6) * mcpt::kListRecWords * 4);
+#endif
+    l.need = al256(2 * l.queue + l.f4 + l.tiles + bounces * sizeof(mcpt::WfCounters) + 256);
     return l;
 }
 
@@ -802,6 +810,12 @@ void prepare_workspace(mcpt_scene& s, Plan& pl, bool tail_split = false, int spi
     }
 }
 
+// the last render's tile classes (primary lists): three counters behind the
+// render counters in the scene's small block (prepare_workspace)
+uint32_t* tile_classes(const mcpt_scene& s) {
+    return reinterpret_cast<uint32_t*>(static_cast<char*>(s.ws.small) + 192);
+}
+
 // wavefront workspace: 2 ray queues (o, d float4), hits, 4 class lists,
 // path state and radiance, per-bounce counters -- carved from one buffer, once
 // per stream (`sets`: batches rotate over the wavefront's streams, each with its own)
@@ -819,6 +833,10 @@ void prepare_wavefront(mcpt_scene& s, const Plan& pl, int sets, mcpt::WfParams* 
         w.q[0] = reinterpret_cast<float4*>(b); b += l.queue;
         w.q[1] = reinterpret_cast<float4*>(b); b += l.queue;
         w.radiance = reinterpret_cast<float4*>(b); b += l.f4;
+#if MCPT_PRIMARY_LISTS
+        uint32_t* const tiles = l.tiles ? reinterpret_cast<uint32_t*>(b) : nullptr;
+        b += l.tiles;
+#endif
         w.cnt = reinterpret_cast<mcpt::WfCounters*>(b);
         w.capacity = pl.wf_capacity;                   // paths per batch (pid range)
         w.slot_stride = static_cast<uint32_t>(l.cap_slots);
@@ -833,6 +851,10 @@ void prepare_wavefront(mcpt_scene& s, const Plan& pl, int sets, mcpt::WfParams* 
                           std::log2(std::max(1.0, double(s.cull_gain))) * pl.kp.max_depth < 127.0;
         w.n_cull_boxes = zero ? s.n_cull_boxes : 0u;
         std::memcpy(w.cull_box, s.cull_box, sizeof w.cull_box);
+#endif
+#if MCPT_PRIMARY_LISTS
+        w.tile_cand = tiles;
+        w.tile_classes = tile_classes(s);
 #endif
     }
 }
@@ -886,6 +908,10 @@ void render_async(mcpt_scene& s, const mcpt_render_params* p, float* d_fb, hipSt
     const int wf_sets = pl.pipeline == MCPT_PIPELINE_WAVEFRONT ? pl.wf_streams : 1;
     prepare_workspace(s, pl, pl.pipeline == MCPT_PIPELINE_MEGAKERNEL && !d_unit_counters, wf_sets);
     pl.kp.unit_counters = d_unit_counters;
+#if MCPT_PRIMARY_LISTS
+    // (a render without primary lists reports none)
+    HIP_TRY(hipMemsetAsync(tile_classes(s), 0, 16, st));
+#endif
     Timing t;
     if (pl.capturing) {
         ensure_capture_timing(s);
@@ -1696,6 +1722,19 @@ int mcpt_scene_get_info(const mcpt_scene* s, mcpt_scene_info* out) {
     out->n_devices = s->on_device ? 1 + static_cast<int64_t>(s->replicas.size()) : 0;
     out->kd_build = s->hs.kd_build;
     return MCPT_OK;
+}
+
+int mcpt_scene_primary_tile_classes(mcpt_scene* s, uint32_t out[4]) {
+    if (!s || !out) return MCPT_E_INVALID;
+    return guarded([&] {
+        out[0] = out[1] = out[2] = 0;
+        out[3] = MCPT_PRIMARY_LISTS ? mcpt::kListK : 0u;
+        if (!s->on_device || !s->ws.small) return MCPT_OK;
+        set_device(*s);
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(out, tile_classes(*s), 12, hipMemcpyDeviceToHost));
+        return MCPT_OK;
+    });
 }
 
 int mcpt_scene_terminal_cull_boxes(const mcpt_scene* s) {

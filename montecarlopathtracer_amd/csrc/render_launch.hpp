@@ -45,6 +45,34 @@ constexpr size_t kMaxLds = 160 * 1024;   // gfx950 LDS per CU
 #define MCPT_TERMINAL_CULL 1
 #endif
 constexpr int kMaxCullBoxes = 8;         // emitter geometries a scene may have and keep the cull
+// Primary lists (wavefront, lean CV renders of scenes in LDS, 8x8 tiles): which
+// triangles the primary rays of a tile can hit depends on the camera, the tile
+// and the scene, not on the sample, so wf_tile_candidates (wavefront.hip) lists
+// them once per render call -- every triangle not wholly outside one side plane
+// of the tile's jitter-grown frustum -- and wf_primary_lists resolves bounce 0
+// from the lists: a tile with no candidate needs no ray, one with up to
+// kListK tests them two at a time, a longer list keeps the packet walk.  The
+// closest hit is the minimum of (t, rank) over the triangles tested, so a
+// superset of the triangles a ray can hit gives the walk's hit id, bit for bit.
+// 0: the pipeline without it, the same kernels as before it (A/B builds).
+#ifndef MCPT_PRIMARY_LISTS
+#define MCPT_PRIMARY_LISTS 1
+#endif
+// candidates a tile's record holds (longer lists: the walk).  C2 frame, ms,
+// three runs each: K = 2 222.1-224.2, 4 221.5-223.5, 6 220.8-227.0, 8 229.2-230.2,
+// 16 229.3-229.8 (the parent 234.3-234.8; PERFLOG row 175)
+#ifndef MCPT_PRIMARY_LIST_K
+#define MCPT_PRIMARY_LIST_K 4
+#endif
+constexpr uint32_t kListK = MCPT_PRIMARY_LIST_K;
+// words of a tile's record: the count, kListK triangle record indices and one
+// word more (the extend reads its indices in pairs), in whole 16-B units
+constexpr uint32_t kListRecWords = (kListK + 2u + 3u) & ~3u;
+// The candidate pass scans every triangle for every tile (one wave per tile).
+// Scenes whose image fits in LDS hold fewer than 2000 triangles (48-B records
+// in at most 96 KB beside the stack), so the bound only guards the scan's cost
+// should that limit ever move: above it the render keeps the packet walk.
+constexpr uint32_t kListMaxTris = 4096;
 
 struct GpuGeom {
     float Ka[3], Kd[3], Ks[3];
@@ -194,6 +222,13 @@ struct WfParams {
 #if MCPT_TERMINAL_CULL
     uint32_t n_cull_boxes;
     uint32_t cull_box[kMaxCullBoxes][3];
+#endif
+    // primary lists: one record of kListRecWords words per owned tile of the
+    // call {count, indices}, and the call's tile classes {0, 1..K, > K}
+    // (stream 0's are used; also last in the kernel arguments)
+#if MCPT_PRIMARY_LISTS
+    uint32_t* tile_cand;
+    uint32_t* tile_classes;
 #endif
 };
 

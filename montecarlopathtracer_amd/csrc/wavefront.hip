@@ -22,6 +22,9 @@
 //               a wave runs one material branch
 //   cull        lean renders, before the last extend: the terminal query's rays
 //               that can reach no emitter leave the queue (wf_cull_terminal)
+//   candidates  lean CV renders of an LDS scene, once per call: per 8x8 tile, the
+//               triangles its primary rays can hit (wf_tile_candidates); bounce
+//               0's extend then resolves its groups from them (wf_primary_lists)
 //   accumulate  per pixel, the batch's samples summed in sample order into the
 //               same [chunk][pixel] partial sums the megakernel writes
 // followed by the megakernel's reduction.  A path never leaves its segment,
@@ -509,6 +512,10 @@ wf_extend(const KernelParams kp, const WfParams wf) {
 #define MCPT_WF_PACKET0 1
 #endif
 __device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+// read-only words another kernel wrote, at wave-uniform addresses: the
+// constant address space (scalar loads; wf_primary_body.hpp)
+typedef const __attribute__((address_space(4))) uint32_t const_u32;
+typedef const __attribute__((address_space(4))) u32x4 const_u32x4;
 
 // MCPT_WF_GEN0 (default 1): no generate kernel before this extend -- each
 // lane computes its slot's primary ray itself (the inverse dealing slot_pid
@@ -519,244 +526,32 @@ __device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin
 #ifndef MCPT_WF_GEN0
 #define MCPT_WF_GEN0 1
 #endif
+// The kernel's body is wf_primary_body.hpp, included once per kernel below:
+// source text, not a function, so that wf_extend_primary's code stays what it
+// was without the second kernel (inlined from a shared function, its epilogue
+// came out one instruction shorter).
+// LIST (wf_primary_lists, render_launch.hpp MCPT_PRIMARY_LISTS; lean renders
+// whose groups are whole 8x8 tiles): a group first reads its tile's candidate
+// record (wf_tile_candidates), fetched one group ahead.  No candidate: every
+// lane's ray is a miss, and nothing but the path count is computed.  Up to
+// kListK: each lane makes its ray as the walk would (a root-box miss stays a
+// miss) and tests the listed triangles two at a time from their LDS records,
+// the next pair's indices loaded behind the current pair's tests.  More: the
+// packet walk.  (Its name must not contain "wf_extend": the resource pins
+// count the kernels that do.)
 template <int S, int BLOCK, bool COUNT>
 __global__ void __launch_bounds__(BLOCK, 1) wf_extend_primary(const KernelParams kp, const WfParams wf) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const uint32_t g = blockIdx.x;
-    WfCounters* cn = wf.cnt + (size_t)wf.bounce * wf.nseg + g;
-    uint32_t count = 0;
-    if (g < wf.nseg) {
-        if constexpr (MCPT_WF_GEN0) {
-            count = seg_queue0_len(wf, g);
-            if (threadIdx.x == 0) cn->queued = count;          // (read by bounce 0's shade)
-        } else {
-            count = cn->queued;
-        }
-    }
-    if (count == 0) {
-        if (g < wf.nseg && threadIdx.x == 0) cn->hits = 0;
-        return;
-    }
-    const int tid = (int)threadIdx.x;
-    const int lane = tid & 63;
-    const GpuScene& sc = kp.scene;
-    // LDS: [stack S x BLOCK x 16 B | scene image | group counter]
-    unsigned char* const lds_image = smem + (size_t)S * BLOCK * 16;
-    uint32_t* lgrp = reinterpret_cast<uint32_t*>(lds_image + sc.image_bytes);
-    if (tid == 0) *lgrp = 0;
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(sc.image);
-        uint4* dst = reinterpret_cast<uint4*>(lds_image);
-        const uint32_t n16 = sc.image_bytes / 16u;
-        for (uint32_t i = (uint32_t)tid; i < n16; i += BLOCK) dst[i] = src[i];
-    }
-    const float4* tris = reinterpret_cast<const float4*>(lds_image + sc.off_tris);
-    const uint2* nodes = reinterpret_cast<const uint2*>(lds_image + sc.off_nodes) + 1;
-    const uint32_t* leafs = reinterpret_cast<const uint32_t*>(lds_image + sc.off_leafs);
-    __syncthreads();
-    uint4* st = reinterpret_cast<uint4*>(smem) + tid;
-    uint4* spill = kp.spill + (blockIdx.x * BLOCK + (uint32_t)tid);
-    const uint32_t spill_stride = kp.total_lanes;
-    const size_t seg0 = (size_t)g * wf.seg;
-    float4* qb = wf.q[0];
-    const uint32_t qs = wf.slot_stride;
-    const int32_t U = BLOCK * 16;                      // one stack position (see slot_of)
-    const V3 eye = v3(kp.eye[0], kp.eye[1], kp.eye[2]);
-    Counters c = {0, 0, 0, 0, 0, 0, 0, 0};
-    __builtin_amdgcn_s_setprio(MCPT_WF_EXT_PRIO);
-    // a wave's 64-slot groups: the next group is taken, and its directions
-    // loaded, before this one's walk, so the load's latency hides behind it
-    auto take_group = [&]() {
-        uint32_t grp = 0;
-        if (lane == 0) grp = atomicAdd(lgrp, 1u);
-        return lane_bcast(grp, 0) << 6;
-    };
-    // The hits of a group are stored one group later, after the wait for the
-    // next directions: a store issued at the end of the walk would make that
-    // wait (vmcnt counts stores too) wait for its acknowledgement.
-    int32_t* const hq = reinterpret_cast<int32_t*>(qb + qf(0, kQHIT, qs)) + seg0;
-    // the primary ray of local slot j: direction and depth (kNoRay: a pixel
-    // outside the image, an empty slot)
-    auto dir_of = [&](uint32_t j) {
-        if constexpr (MCPT_WF_GEN0) {
-            const uint32_t pid = slot_pid(wf, g, j);
-            const uint32_t s_local = pid / wf.nb;
-            int px, py;
-            float4 d4 = make_float4(0, 0, 0, __uint_as_float(kNoRay));
-            if (unit_pixel(kp, wf.v0 + (pid - s_local * wf.nb), px, py)) {
-                uint32_t sd;
-                V3 d;
-                primary_ray(kp, (uint32_t)py * (uint32_t)kp.width + (uint32_t)px, px, py, wf.s_begin + s_local, sd, d);
-                d4 = pack(d, 0u);
-                c.paths++;                                      // (generate's counts)
-                c.rays++;
-            }
-            return d4;
-        } else {
-            return ldq(&qb[qf(seg0 + j, kQD, qs)]);
-        }
-    };
-    uint32_t base = take_group();
-    float4 nd4 = make_float4(0, 0, 0, 0);
-    if (base + (uint32_t)lane < count) nd4 = dir_of(base + (uint32_t)lane);
-    uint32_t pslot = count;                             // the previous group's slot (count: none)
-    int32_t phit = -1;
-    for (;;) {
-        if (base >= count) break;
-        const uint32_t slot = base + (uint32_t)lane;
-        const float4 d4 = make_float4(opaque(nd4.x), opaque(nd4.y), opaque(nd4.z), opaque(nd4.w));
-        if (pslot < count) hq[pslot] = phit;
-        const uint32_t nbase = take_group();
-        if (nbase + (uint32_t)lane < count) nd4 = dir_of(nbase + (uint32_t)lane);
-        RayState r;
-        r.o = eye;
-        r.d = v3(0, 0, 1);
-        r.htri = -1;
-        bool active = false, done = false;
-        if (slot < count && __float_as_uint(d4.w) != kNoRay) {
-            r.d = xyz(d4);
-            active = begin_ray(r, sc, kp.best_init);
-        }
-        uint32_t w0 = sc.root_w[0], w1 = sc.root_w[1];  // the wave's node
-        int32_t sp = 0, lo = 0;                         // wave-uniform stack positions
-        if (__ballot(active)) {
-            for (;;) {
-                if ((w0 >> 30) != 3u) {
-                    // ---- inner node: each lane's step of isect_kd_ordered ----
-                    if constexpr (COUNT) c.inner += active ? 1u : 0u;
-                    const uint32_t left = w0 & kLeftMask;
-                    const uint4 pr = *reinterpret_cast<const uint4*>(nodes + left);
-                    const int a = (int)(w0 >> 30);
-                    const float sv = __uint_as_float(w1);
-                    const float oa = sel3(a, eye.x, eye.y, eye.z);   // wave-uniform (common origin)
-                    const float ia = sel3(a, r.ix, r.iy, r.iz);
-                    const float t = (sv - oa) * ia;
-                    const float te = t * kEpsHi;
-                    const bool no = !(t > 0.0f) | (t > r.tmax);
-                    const bool fo = te < r.tmin;
-                    bool first_left, need1, need2;
-                    float lo1, hi1, lo2, hi2;
-                    if (__builtin_expect(oa != sv, 1)) {
-                        // (a uniform branch) the origin is off the plane: every lane's
-                        // near side is the wave's first child, below == first_left,
-                        // and no lane lies in the plane (pp false)
-                        first_left = oa < sv;
-                        const bool go_far = !no & fo, both = !no & !fo;
-                        need1 = active & !go_far;
-                        need2 = active & (go_far | both);
-                        // (both interval ends computed unconditionally: a select of the
-                        // asm min/max, not a branch around it)
-                        const float mn = min_qnan(te, r.tmax), mx = max_qnan(t, r.tmin);
-                        lo1 = r.tmin;
-                        hi1 = both ? mn : r.tmax;
-                        lo2 = go_far ? r.tmin : mx;
-                        hi2 = r.tmax;
-                    } else {
-                        // the origin on the plane: the near side by each lane's direction
-                        const float da = sel3(a, r.d.x, r.d.y, r.d.z);
-                        const bool below = da <= 0.0f, pp = da == 0.0f;
-                        const bool go_far = !pp & !no & fo;
-                        const bool push_it = pp | (!pp & !no & !fo);
-                        const bool need_near = active & !go_far, need_far = active & (go_far | push_it);
-                        const float near_max = push_it ? min_qnan(te, r.tmax) : r.tmax;   // near: [tmin, near_max]
-                        const float far_min = go_far ? r.tmin : max_qnan(t, r.tmin);      // far: [far_min, tmax]
-                        // the wave's order: left first (the near side of every lane not in the plane)
-                        first_left = true;
-                        need1 = below ? need_near : need_far;
-                        need2 = below ? need_far : need_near;
-                        lo1 = below ? r.tmin : far_min;
-                        hi1 = below ? near_max : r.tmax;
-                        lo2 = below ? far_min : r.tmin;
-                        hi2 = below ? r.tmax : near_max;
-                    }
-                    const uint32_t f0 = first_left ? pr.x : pr.z, f1 = first_left ? pr.y : pr.w;
-                    const uint32_t s0 = first_left ? pr.z : pr.x, s1 = first_left ? pr.w : pr.y;
-                    if (__ballot(need1)) {
-                        if (__ballot(need2)) {                   // push the second child
-                            lds_uint4* sl = slot_of<S>(st, BLOCK, sp);
-                            if (sp - lo == S * U) {              // LDS part full: its oldest entry to memory
-                                spill[((uint32_t)lo / (uint32_t)U) * spill_stride] = ld4(sl);
-                                lo += U;
-                                if constexpr (COUNT) c.spills++;
-                            }
-                            st4(sl, make_uint4(s0, s1, __float_as_uint(lo2),
-                                               need2 ? __float_as_uint(hi2) : 0x7FC00001u));
-                            sp += U;
-                        }
-                        w0 = f0;
-                        w1 = f1;
-                        active = need1;
-                        r.tmin = lo1;
-                        r.tmax = hi1;
-                    } else {
-                        w0 = s0;
-                        w1 = s1;
-                        active = need2;
-                        r.tmin = lo2;
-                        r.tmax = hi2;
-                    }
-                    continue;
-                }
-                // ---- leaf: the active lanes test its triangles, two per round ----
-                {
-                    const uint32_t lpos = w0 & 0x3FFFFFFFu, lend = lpos + w1;
-                    if constexpr (COUNT) c.leaf += active ? 1u : 0u;
-                    for (uint32_t i = lpos; i < lend; i += 2u) {
-                        const bool two = lend - i >= 2u;
-                        const uint32_t k0 = leafs[i], k1n = leafs[i + 1u];
-                        const uint32_t k1 = two ? k1n : k0;
-                        const float4 a0 = ld_tri<true>(tris + k0), a1 = ld_tri<true>(tris + k0 + 1);
-                        const float4 a2 = ld_tri<true>(tris + k0 + 2), b0 = ld_tri<true>(tris + k1);
-                        const float4 b1 = ld_tri<true>(tris + k1 + 1), b2 = ld_tri<true>(tris + k1 + 2);
-                        if (active) {
-                            test_tri_pair(r, a0, a1, a2, k0, b0, b1, b2, k1, two);
-                            if constexpr (COUNT) {
-                                c.refs += two ? 2u : 1u;
-                                c.tests += two ? 2u : 1u;
-                            }
-                        }
-                    }
-                }
-                // ---- pop until an entry with an active lane (or the stack is empty) ----
-                bool more = false;
-                while (sp > 0) {
-                    sp -= U;
-                    uint4 e;
-                    if (sp < lo) {                               // LDS part empty: the entry is in memory
-                        e = settle4(spill[((uint32_t)sp / (uint32_t)U) * spill_stride]);   // (wait here)
-                        lo = sp;
-                    } else {
-                        e = ld4(slot_of<S>(st, BLOCK, sp));
-                    }
-                    w0 = uni(e.x);
-                    w1 = uni(e.y);
-                    const float emin = __uint_as_float(e.z), emax = __uint_as_float(e.w);
-                    active = false;
-                    if ((emax == emax) & !done) {                // this lane's own entry (pop_entry)
-                        if (r.best <= emin * kEpsLo) {
-                            done = true;                         // its walk ends here
-                        } else {
-                            active = true;
-                            r.tmin = emin;
-                            r.tmax = emax;
-                        }
-                    }
-                    if (__ballot(active)) {
-                        more = true;
-                        break;
-                    }
-                }
-                if (!more) break;
-            }
-        }
-        pslot = slot;
-        phit = r.htri;
-        base = nbase;
-    }
-    if (pslot < count) hq[pslot] = phit;
-    flush_counters(c, kp.stats);
-    if (tid == 0) cn->hits = count;
+    constexpr bool LIST = false;
+#include "wf_primary_body.hpp"
 }
+#if MCPT_PRIMARY_LISTS
+// (<= 88 VGPRs, as the LDS scenes' other lean extends: two shade waves per SIMD beside it)
+template <int S, int BLOCK>
+__global__ void __launch_bounds__(BLOCK, 1) wf_primary_lists(const KernelParams kp, const WfParams wf) {
+    constexpr bool LIST = true, COUNT = false;
+#include "wf_primary_body.hpp"
+}
+#endif
 
 #if !MCPT_WF_PRIMARY_TU
 // ---- shade: one workgroup per segment, its queue in blocks of slots ---------
@@ -993,6 +788,92 @@ __global__ void __launch_bounds__(kCullBlock, 6) wf_cull_terminal(const KernelPa
 }
 #endif
 
+#if MCPT_PRIMARY_LISTS
+// ---- candidate pass: the triangles each owned tile's primary rays can hit ---
+// Once per render call (render_launch.hpp MCPT_PRIMARY_LISTS), one wave per
+// owned 8x8 tile.  Every sample of the tile's pixels has its jittered position
+// (primary_ray_sd's bias) in [x0 - 1, x0 + 8] x [y0 - 1, y0 + 8], so its ray
+// lies in the cone through the eye and that rectangle's corners, mapped as
+// primary_ray_sd maps a position, in double.  A triangle is dropped when its
+// three vertices lie outside one of the cone's four side planes, or behind the
+// eye (the plane through it across the cone's axis), by more than a margin:
+// 1e-3 of the root box's largest side plus 2^-16 of the vertex's distance from
+// the eye.  The margin stands for everything that separates the float ray the
+// extend tests from this double cone: the float rounding of the
+// mapping and of the normalize (a few 2^-24 of the distance), the vertices
+// rebuilt from the records' edges, and the Cramer test accepting a ray that
+// passes a triangle's edge by a rounding error.
+// Record of tile k: {count, up to kListK triangle record indices in image
+// order}; a count above kListK leaves the tile to the packet walk.
+constexpr int kCandBlock = 256;
+__global__ void __launch_bounds__(kCandBlock) wf_tile_candidates(const KernelParams kp, const WfParams wf) {
+    const uint32_t tile = blockIdx.x * (uint32_t)(kCandBlock / 64) + (threadIdx.x >> 6);   // (wave-uniform)
+    if (tile >= (kp.npix_local >> 6)) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const GpuScene& sc = kp.scene;
+    int x0, y0;
+    (void)unit_pixel(kp, tile << 6, x0, y0);               // the tile's first pixel
+    const double th = (double)kp.tan_half_fov, W = (double)(uint32_t)kp.width;
+    double cn[4][3];                                        // corner directions, around the rectangle
+    for (int i = 0; i < 4; i++) {
+        const double bx = (double)x0 + ((i == 1 || i == 2) ? 8.0 : -1.0), by = (double)y0 + (i >= 2 ? 8.0 : -1.0);
+        const double idx = (2.0 * bx / W - 1.0) * th, idy = (kp.h_over_w - 2.0 * by / W) * th;
+        for (int a = 0; a < 3; a++)
+            cn[i][a] = (double)kp.right[a] * idx + (double)kp.up[a] * idy + (double)kp.fwd[a];
+    }
+    // planes 0-3: the sides, unit normals pointing into the cone; 4: across the axis
+    double pn[5][3];
+    for (int a = 0; a < 3; a++) pn[4][a] = cn[0][a] + cn[1][a] + cn[2][a] + cn[3][a];
+    for (int i = 0; i < 4; i++) {
+        const double* u = cn[i];
+        const double* v = cn[(i + 1) & 3];
+        pn[i][0] = u[1] * v[2] - u[2] * v[1];
+        pn[i][1] = u[2] * v[0] - u[0] * v[2];
+        pn[i][2] = u[0] * v[1] - u[1] * v[0];
+        if (pn[i][0] * pn[4][0] + pn[i][1] * pn[4][1] + pn[i][2] * pn[4][2] < 0.0)
+            for (int a = 0; a < 3; a++) pn[i][a] = -pn[i][a];
+    }
+    for (int i = 0; i < 5; i++) {   // (a degenerate cone: NaN normals, every test below false, every triangle kept)
+        const double l = sqrt(pn[i][0] * pn[i][0] + pn[i][1] * pn[i][1] + pn[i][2] * pn[i][2]);
+        for (int a = 0; a < 3; a++) pn[i][a] /= l;
+    }
+    double ext = 0.0;
+    for (int a = 0; a < 3; a++) ext = fmax(ext, (double)sc.root_max[a] - (double)sc.root_min[a]);
+    const double m0 = 1e-3 * ext;
+    const float4* tris = reinterpret_cast<const float4*>(sc.image + sc.off_tris);
+    uint32_t* rec = wf.tile_cand + (size_t)tile * kListRecWords;
+    uint32_t n = 0;                                         // candidates so far (wave-uniform)
+    for (uint32_t i0 = 0; i0 < sc.n_tris; i0 += 64u) {
+        const uint32_t i = i0 + lane;
+        bool keep = false;
+        if (i < sc.n_tris) {
+            const float4 A0 = tris[3u * i], A1 = tris[3u * i + 1u], A2 = tris[3u * i + 2u];   // a, a - b, a - c
+            uint32_t out = 0x1Fu;                           // planes all three vertices are outside of
+            for (int k = 0; k < 3; k++) {
+                double p[3] = {(double)A0.x, (double)A0.y, (double)A0.z};
+                if (k == 1) { p[0] -= (double)A1.x; p[1] -= (double)A1.y; p[2] -= (double)A1.z; }
+                if (k == 2) { p[0] -= (double)A2.x; p[1] -= (double)A2.y; p[2] -= (double)A2.z; }
+                for (int a = 0; a < 3; a++) p[a] -= (double)kp.eye[a];
+                const double m = m0 + sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) * (1.0 / 65536.0);
+                for (int q = 0; q < 5; q++)
+                    if (!(pn[q][0] * p[0] + pn[q][1] * p[1] + pn[q][2] * p[2] < -m)) out &= ~(1u << q);
+            }
+            keep = out == 0u;
+        }
+        const uint64_t mk = __ballot(keep);
+        if (keep) {
+            const uint32_t pos = n + (uint32_t)__popcll(mk & ((1ull << lane) - 1ull));
+            if (pos < kListK) rec[1u + pos] = 3u * i;
+        }
+        n += (uint32_t)__popcll(mk);
+    }
+    if (lane == 0) {
+        rec[0] = n;
+        atomicAdd(&wf.tile_classes[n == 0u ? 0 : (n <= kListK ? 1 : 2)], 1u);
+    }
+}
+#endif
+
 // ---- accumulate: samples of the batch in sample order -> partial sums -------
 // A batch holds wf.ns / wf.nsc whole chunks of nsc samples each (blockIdx.y).
 __global__ void __launch_bounds__(256) wf_accumulate(const KernelParams kp, const WfParams wf) {
@@ -1016,6 +897,17 @@ hipError_t launch_extend_primary(const KernelParams& kp, const WfParams& wf, int
     hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, kp, wf);
     return hipGetLastError();
 }
+#if MCPT_PRIMARY_LISTS
+template <int S, int BLOCK>
+hipError_t launch_primary_lists(const KernelParams& kp, const WfParams& wf, int grid, size_t lds, hipStream_t st) {
+    auto kern = wf_primary_lists<S, BLOCK>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, kp, wf);
+    return hipGetLastError();
+}
+#endif
 
 #if !MCPT_WF_PRIMARY_TU
 template <int BLOCK>
@@ -1048,9 +940,19 @@ hipError_t launch_wavefront_primary(const KernelParams& kp, const WfParams& wf, 
                                     hipStream_t st) {
     return launch_extend_primary<4, kLdsBlock>(kp, wf, grid, lds, st);
 }
+#if MCPT_PRIMARY_LISTS
+hipError_t launch_wavefront_primary_lists(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
+                                          hipStream_t st) {
+    return launch_primary_lists<4, kLdsBlock>(kp, wf, grid, lds, st);
+}
+#endif
 #else
 hipError_t launch_wavefront_primary(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
                                     hipStream_t st);   // wavefront_primary.hip
+#if MCPT_PRIMARY_LISTS
+hipError_t launch_wavefront_primary_lists(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
+                                          hipStream_t st);   // wavefront_primary.hip
+#endif
 
 #ifdef MCPT_PHASE_TIMING
 void read_lane_use_wf(unsigned long long out[6]) {   // wavefront extend lane-use counters, then reset
@@ -1096,6 +998,22 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
         if (variant_out) *variant_out = in_lds ? 4 : 5;
         return hipSuccess;
     }
+#if MCPT_PRIMARY_LISTS
+    // primary lists: lean renders where the packet extend runs (CV mode, scene
+    // in LDS, implicit queue 0) whose tiles are 8x8 -- one tile of one sample
+    // per 64-slot group -- and whose scene a per-tile scan of every triangle
+    // suits (kListMaxTris).  The candidate pass runs once, on the caller's
+    // stream, before the batches' streams fork from it.
+    const bool lists = MCPT_WF_PACKET0 && MCPT_WF_GEN0 && MCPT_WF_IMPLICIT0 >= 2 && kp.lean && in_lds &&
+                       implicit0(kp, wf_in[0]) && kp.tile == 8 && kp.scene.n_tris <= kListMaxTris &&
+                       wf_in[0].tile_cand && wf_in[0].tile_classes;
+    if (lists) {
+        const uint32_t tiles = kp.npix_local >> 6;
+        hipLaunchKernelGGL(wf_tile_candidates, dim3((tiles + kCandBlock / 64 - 1) / (kCandBlock / 64)),
+                           dim3(kCandBlock), 0, st, kp, wf_in[0]);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+#endif
     if (ns > 1) {
         if ((e = hipEventRecord(ws.fork, st)) != hipSuccess) return e;
         for (int i = 1; i < ns; i++)
@@ -1160,6 +1078,14 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
             for (int b = 0; b < max_bounces && e == hipSuccess; b++) {
                 wf.bounce = b;
                 const size_t llds = in_lds ? wf_lds_extend_bytes(kb.scene) : 0;
+#if MCPT_PRIMARY_LISTS
+                // (a batch whose pixel range is not whole tiles keeps the walk: its
+                // 64-slot groups would straddle tiles)
+                if (lists && packet && b == 0 && (wf.v0 & 63u) == 0u && (wf.nb & 63u) == 0u) {
+                    wf.tile_cand = wf_in[0].tile_cand;
+                    e = launch_wavefront_primary_lists(kb, wf, (int)nseg, llds, bs);
+                } else
+#endif
                 if (packet && b == 0) {
                     e = launch_wavefront_primary(kb, wf, (int)nseg, llds, bs);
                 } else if (in_lds) {

@@ -304,6 +304,14 @@ class Scene:
         d["terminal_cull_boxes"] = int(lib().mcpt_scene_terminal_cull_boxes(self.handle))
         return d
 
+    def primary_tile_classes(self):
+        """The last render's primary lists: owned 8x8 tiles by candidate count --
+        {"empty", "listed", "walked", "k"}; all three counts are 0 after a render
+        that did not resolve its primary rays from tile lists."""
+        out = (C.c_uint32 * 4)()
+        check(lib().mcpt_scene_primary_tile_classes(self.handle, out))
+        return {"empty": int(out[0]), "listed": int(out[1]), "walked": int(out[2]), "k": int(out[3])}
+
     def kd(self):
         """(nodes (n,12) u32, leaf ids, kd_tris, geoms (g,14) f32) as built."""
         i = self.info()

@@ -11,7 +11,7 @@ import os
 import sys
 
 CUS = 256
-KINDS = (("wf_extend_primary", "extend_bounce0"), ("wf_extend<", "extend"), ("wf_shade", "shade"),
+KINDS = (("wf_extend_primary", "extend_bounce0"), ("wf_primary_lists", "extend_bounce0"), ("wf_extend<", "extend"), ("wf_shade", "shade"),
          ("wf_generate", "generate"))
 
 

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Per-bounce extend / shade times from a rocprofv3 kernel trace of wavefront
 renders on ONE stream (kernels serialized): dispatches are grouped per batch
-(wf_generate, or the generate-free bounce-0 extend wf_extend_primary, starts
-one) and indexed by bounce; wf_cull_terminal (the terminal cull in front of the
-last extend) is summed on its own.  usage: wf_bounce_times.py DIR"""
+(wf_generate, or a generate-free bounce-0 extend -- wf_extend_primary, or
+wf_primary_lists, which resolves the tiles' candidate lists -- starts one) and
+indexed by bounce; wf_cull_terminal (the terminal cull in front of the last
+extend) and wf_tile_candidates (the primary lists' candidate pass, once per
+render) are summed on their own.  usage: wf_bounce_times.py DIR"""
 import csv
 import glob
 import sys
@@ -18,16 +20,18 @@ def main(d):
                 rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
     rows.sort()
     ext, sh = defaultdict(list), defaultdict(list)
-    cull = []
+    cull, cand = [], []
     b_ext = b_sh = -1
     batches = 0
     for t0, t1, name in rows:
-        if "wf_generate" in name or "wf_extend_primary" in name:
+        if "wf_generate" in name or "wf_extend_primary" in name or "wf_primary_lists" in name:
             b_ext = b_sh = -1
             batches += 1
         if "wf_cull_terminal" in name:
             cull.append((t1 - t0) / 1e6)
-        elif "wf_extend" in name:
+        elif "wf_tile_candidates" in name:
+            cand.append((t1 - t0) / 1e6)
+        elif "wf_extend" in name or "wf_primary_lists" in name:
             b_ext += 1
             ext[b_ext].append((t1 - t0) / 1e6)
         elif "wf_shade" in name:
@@ -42,6 +46,8 @@ def main(d):
     print("shade total per batch", sum(sum(v) for v in sh.values()) / batches)
     if cull:
         print(f"terminal cull per batch {sum(cull) / batches:.3f} x{len(cull)}")
+    if cand:
+        print(f"candidate pass per render {sum(cand) / len(cand):.4f} x{len(cand)}")
 
 
 if __name__ == "__main__":
