@@ -34,7 +34,7 @@ SOURCE_FLAGS = {"wavefront_primary.hip": ["-mllvm", "-structurizecfg-skip-unifor
                 "render.hip": ["-mllvm", "-enable-gvn-hoist", "-mllvm", "-unroll-threshold=2000"]}
 HEADERS = ["host_model.hpp", "mcpt_device.hpp", "render_launch.hpp", "trace_device.hpp", "half_box.hpp",
            "aov_device.hpp", "aov_launch.hpp", "variance_launch.hpp", "adaptive_launch.hpp", "partial_sum.hpp", "rayquery_launch.hpp",
-           "wf_primary_body.hpp"]
+           "wf_device.hpp", "wf_primary_body.hpp"]
 ARCH = os.environ.get("MCPT_OFFLOAD_ARCH", "gfx950")
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-Wall",

@@ -43,11 +43,7 @@ __global__ void __launch_bounds__(kAovBlock) aov_kernel(const KernelParams kp, f
     const int tid = (int)threadIdx.x;
     const uint32_t gl = blockIdx.x * kAovBlock + (uint32_t)tid;
     const uint32_t lanes = gridDim.x * kAovBlock;               // <= kp.total_lanes (launch_aov)
-    const float4* tris = reinterpret_cast<const float4*>(sc.image + sc.off_tris);
-    const uint2* nodes = reinterpret_cast<const uint2*>(sc.image + sc.off_nodes) + 1;
-    const uint32_t* leafs = reinterpret_cast<const uint32_t*>(sc.image + sc.off_leafs);
-    const GpuGeom* geoms = reinterpret_cast<const GpuGeom*>(sc.image + sc.off_geoms);
-    const uint4* pairs = reinterpret_cast<const uint4*>(sc.image + sc.off_nodes);
+    const SceneView sv = open_scene<false, kAovBlock>(nullptr, sc, tid);
     uint4* spill = kp.spill + gl;
     const V3 eye = v3(kp.eye[0], kp.eye[1], kp.eye[2]);
     Counters c = {0, 0, 0, 0, 0, 0, 0, 0};   // compiled out (COUNT = false): the scene's stats are not touched
@@ -71,11 +67,11 @@ __global__ void __launch_bounds__(kAovBlock) aov_kernel(const KernelParams kp, f
                 r.o = eye;
             }
             if (begin_ray(r, sc, kp.best_init))
-                while (!trav_iter<S, BOXES, false>(r, tris, nodes, leafs, stk + tid, kAovBlock, spill, kp.total_lanes,
-                                                   c MCPT_LU_ARG, pairs)) {
+                while (!trav_iter<S, BOXES, false>(r, sv.tris, sv.nodes, sv.leafs, stk + tid, kAovBlock, spill,
+                                                   kp.total_lanes, c MCPT_LU_ARG, sv.pairs)) {
                 }
             if (r.htri < 0) continue;                           // a miss adds zeros
-            const GpuGeom& g = geoms[__float_as_uint(tris[r.htri + 1].w)];
+            const GpuGeom& g = sv.geoms[__float_as_uint(sv.tris[r.htri + 1].w)];
             // (QuinEngine's scatter never tints a Fresnel bounce, rtx.hlsl:345)
             const V3 alb = first_scatter_albedo(g, QE ? 0 : kp.fresnel_kd);
             V3 n = shading_normal_raw(sc.normals, r.htri, r.hbeta, r.hgamma);

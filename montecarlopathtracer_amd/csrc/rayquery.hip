@@ -4,8 +4,9 @@
 // The walk is the renders' (trace_device.hpp: begin_ray, then trav_iter until
 // it returns true -- what render.hip's query_kernel runs for mcpt_intersect),
 // with the scene's own layout; the kernel around it is the wavefront extend's
-// (wavefront.hip wf_extend): persistent workgroups, the scene image copied into
-// LDS when it fits (one 1024-thread workgroup per CU) or read through L1/L2
+// (wavefront.hip wf_extend; its layouts and tuning defaults come from
+// wf_device.hpp, the scene prologue from trace_device.hpp): persistent
+// workgroups, the scene image copied into LDS when it fits (one 1024-thread workgroup per CU) or read through L1/L2
 // with the child-box cull (256-thread workgroups, several per CU), the top of
 // every lane's stack in LDS.  Workgroup g owns a contiguous range of the rays;
 // its waves reserve 64 consecutive rays per LDS atomic, every lane loads its
@@ -19,41 +20,29 @@
 
 #include <cstdint>
 
-#include "mcpt_device.hpp"
 #include "rayquery_launch.hpp"
-#include "render_launch.hpp"
-#include "trace_device.hpp"
+#include "wf_device.hpp"
 
 namespace mcpt {
 
-using namespace dev;
-using namespace trace;
-
 namespace {
 
-// The wavefront extend's measured choices (wavefront.hip), the starting point
+// The wavefront extend's measured choices (wf_device.hpp), the starting point
 // here: descent steps per traversal call, LDS stack entries per lane and the
 // waves per SIMD the lean global-memory kernel is held to.
 #ifndef MCPT_RQ_DESCENT_CAP
-#define MCPT_RQ_DESCENT_CAP 5
+#define MCPT_RQ_DESCENT_CAP MCPT_WF_DESCENT_CAP
 #endif
 #ifndef MCPT_RQ_DESCENT_CAP_GLOBAL
-#define MCPT_RQ_DESCENT_CAP_GLOBAL 6
+#define MCPT_RQ_DESCENT_CAP_GLOBAL MCPT_WF_DESCENT_CAP_GLOBAL
 #endif
 #ifndef MCPT_RQ_GLOBAL_S
-#define MCPT_RQ_GLOBAL_S 6
+#define MCPT_RQ_GLOBAL_S MCPT_WF_GLOBAL_S
 #endif
 #ifndef MCPT_RQ_GLOBAL_WAVES
-#define MCPT_RQ_GLOBAL_WAVES 6
+#define MCPT_RQ_GLOBAL_WAVES MCPT_WF_GLOBAL_WAVES
 #endif
-constexpr int kLayGlobal = 0, kLayLds = 1;
 constexpr int kRqLdsS = 4;
-
-__device__ __forceinline__ float opaque(float x) {
-    float y;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(y) : "v"(x));
-    return y;
-}
 
 // a lane's next ray, loaded a burst ahead
 struct NextRay {
@@ -76,23 +65,7 @@ rq_trace(const RayQueryParams q) {
     unsigned char* const lds_image = smem + (size_t)S * BLOCK * 16;
     uint32_t* const lslot = reinterpret_cast<uint32_t*>(lds_image + (IN_LDS ? sc.image_bytes : 0u));
     if (tid == 0) *lslot = 0;
-    const float4* tris;
-    const uint2* nodes;
-    const uint32_t* leafs;
-    if constexpr (IN_LDS) {
-        const uint4* src = reinterpret_cast<const uint4*>(sc.image);
-        uint4* dst = reinterpret_cast<uint4*>(lds_image);
-        const uint32_t n16 = sc.image_bytes / 16u;
-        for (uint32_t i = (uint32_t)tid; i < n16; i += BLOCK) dst[i] = src[i];
-        tris = reinterpret_cast<const float4*>(lds_image + sc.off_tris);
-        nodes = reinterpret_cast<const uint2*>(lds_image + sc.off_nodes) + 1;
-        leafs = reinterpret_cast<const uint32_t*>(lds_image + sc.off_leafs);
-    } else {
-        tris = reinterpret_cast<const float4*>(sc.image + sc.off_tris);
-        nodes = reinterpret_cast<const uint2*>(sc.image + sc.off_nodes) + 1;
-        leafs = reinterpret_cast<const uint32_t*>(sc.image + sc.off_leafs);
-    }
-    const uint4* pairs = reinterpret_cast<const uint4*>(sc.image + sc.off_nodes);   // 48-B pair records (global variant)
+    const SceneView sv = open_scene<IN_LDS, BLOCK>(lds_image, sc, tid);
     __syncthreads();
     uint4* st = reinterpret_cast<uint4*>(smem) + tid;
     uint4* spill = q.spill + (blockIdx.x * BLOCK + (uint32_t)tid);
@@ -148,7 +121,7 @@ rq_trace(const RayQueryParams q) {
             if (mode == kTrav) {
                 const bool end = trav_iter<S, !IN_LDS, COUNT, LAY == kLayLds,
                                            IN_LDS ? MCPT_RQ_DESCENT_CAP : MCPT_RQ_DESCENT_CAP_GLOBAL>(
-                    r, tris, nodes, leafs, st, BLOCK, spill, spill_stride, c MCPT_LU_ARG, pairs);
+                    r, sv.tris, sv.nodes, sv.leafs, st, BLOCK, spill, spill_stride, c MCPT_LU_ARG, sv.pairs);
                 if (end || (ANY && r.htri >= 0)) mode = kReady;
             }
             const uint64_t trv = __ballot(mode == kTrav);
@@ -206,21 +179,15 @@ template <int LAY, int S, int BLOCK>
 hipError_t launch_rq(const RayQueryParams& q, bool any, bool lean, uint32_t grid, size_t lds, hipStream_t st) {
     auto kern = any ? (lean ? rq_trace<LAY, S, BLOCK, false, true> : rq_trace<LAY, S, BLOCK, true, true>)
                     : (lean ? rq_trace<LAY, S, BLOCK, false, false> : rq_trace<LAY, S, BLOCK, true, false>);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, q);
-    return hipGetLastError();
+    return launch_dyn_lds(kern, dim3(grid), dim3(BLOCK), lds, st, q);
 }
 
 template <int LAY, int S, int BLOCK>
 hipError_t prepare_rq(size_t lds) {
-    const void* kerns[4] = {reinterpret_cast<const void*>(rq_trace<LAY, S, BLOCK, false, true>),
-                            reinterpret_cast<const void*>(rq_trace<LAY, S, BLOCK, true, true>),
-                            reinterpret_cast<const void*>(rq_trace<LAY, S, BLOCK, false, false>),
-                            reinterpret_cast<const void*>(rq_trace<LAY, S, BLOCK, true, false>)};
-    for (const void* k : kerns) {
-        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    void (*const kerns[4])(RayQueryParams) = {rq_trace<LAY, S, BLOCK, false, true>, rq_trace<LAY, S, BLOCK, true, true>,
+                                              rq_trace<LAY, S, BLOCK, false, false>, rq_trace<LAY, S, BLOCK, true, false>};
+    for (auto k : kerns) {
+        hipError_t e = set_dyn_lds(k, lds);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -232,9 +199,10 @@ hipError_t prepare_rq(size_t lds) {
 // code object at the first use of one of its kernels, which allocates): part
 // of the reserve, so that a query after it allocates nothing.
 hipError_t prepare_rayquery(const GpuScene& sc) {
-    if (sc.node_boxes) return prepare_rq<kLayGlobal, MCPT_RQ_GLOBAL_S, kGlobalBlock>((size_t)MCPT_RQ_GLOBAL_S * kGlobalBlock * 16 + 32);
-    if (lds_bytes_in_lds(sc.image_bytes, kRqLdsS) + 32 > kMaxLds) return hipErrorInvalidValue;
-    return prepare_rq<kLayLds, kRqLdsS, kLdsBlock>(lds_bytes_in_lds(sc.image_bytes, kRqLdsS) + 32);
+    if (sc.node_boxes) return prepare_rq<kLayGlobal, MCPT_RQ_GLOBAL_S, kGlobalBlock>(lds_bytes_global(MCPT_RQ_GLOBAL_S, true));
+    const size_t lds = lds_bytes_counted_in_lds(sc.image_bytes, kRqLdsS);
+    if (lds > kMaxLds) return hipErrorInvalidValue;
+    return prepare_rq<kLayLds, kRqLdsS, kLdsBlock>(lds);
 }
 
 RayQueryGrid rayquery_grid(const GpuScene& sc, uint32_t n, int cus, int max_workgroups) {
@@ -262,11 +230,11 @@ hipError_t launch_rayquery(const RayQueryParams& q_in, bool any, bool lean, int 
     if (q.refill <= 0) q.refill = q.scene.node_boxes ? 8 : 16;
     if (q.scene.node_boxes)
         return launch_rq<kLayGlobal, MCPT_RQ_GLOBAL_S, kGlobalBlock>(q, any, lean, g.workgroups,
-                                                                    (size_t)MCPT_RQ_GLOBAL_S * kGlobalBlock * 16 + 32, st);
+                                                                    lds_bytes_global(MCPT_RQ_GLOBAL_S, true), st);
     // (an image without child boxes fits: capi.cpp build_image)
-    if (lds_bytes_in_lds(q.scene.image_bytes, kRqLdsS) + 32 > kMaxLds) return hipErrorInvalidValue;
-    return launch_rq<kLayLds, kRqLdsS, kLdsBlock>(q, any, lean, g.workgroups,
-                                                  lds_bytes_in_lds(q.scene.image_bytes, kRqLdsS) + 32, st);
+    const size_t lds = lds_bytes_counted_in_lds(q.scene.image_bytes, kRqLdsS);
+    if (lds > kMaxLds) return hipErrorInvalidValue;
+    return launch_rq<kLayLds, kRqLdsS, kLdsBlock>(q, any, lean, g.workgroups, lds, st);
 }
 
 }  // namespace mcpt

@@ -76,10 +76,9 @@ __device__ __forceinline__ void path_body(const KernelParams kp) {
     // fewer instructions per push and pop than an offset base
     unsigned char* const lds_image = smem + (size_t)S * BLOCK * 16;
     if constexpr (IN_LDS) {
-        const uint4* src = reinterpret_cast<const uint4*>(sc.image);
-        uint4* dst = reinterpret_cast<uint4*>(lds_image);
-        const uint32_t n16 = sc.image_bytes / 16u;
-        for (uint32_t i = (uint32_t)tid; i < n16; i += BLOCK) dst[i] = src[i];
+        // (the pointers below as they are: taken from open_scene's view, the LDS
+        // variants of the QuinEngine kernels and the lean list_kernel compile differently)
+        MCPT_COPY_SCENE_TO_LDS(lds_image, sc, tid, BLOCK);
         __syncthreads();
         tris = reinterpret_cast<const float4*>(lds_image + sc.off_tris);
         nodes = reinterpret_cast<const uint2*>(lds_image + sc.off_nodes) + 1;   // node i at slot i+1
@@ -416,10 +415,7 @@ __global__ void __launch_bounds__(kQueryBlock) query_kernel(const QueryParams q)
     const int tid = (int)threadIdx.x;
     const uint32_t i = blockIdx.x * kQueryBlock + (uint32_t)tid;
     const bool live = i < q.n;
-    const float4* tris = reinterpret_cast<const float4*>(sc.image + sc.off_tris);
-    const uint2* nodes = reinterpret_cast<const uint2*>(sc.image + sc.off_nodes) + 1;
-    const uint32_t* leafs = reinterpret_cast<const uint32_t*>(sc.image + sc.off_leafs);
-    const uint4* pairs = reinterpret_cast<const uint4*>(sc.image + sc.off_nodes);
+    const SceneView sv = open_scene<false, kQueryBlock>(nullptr, sc, tid);
     Counters c = {0, 0, 0, 0, 0, 0, 0, 0};
 #ifdef MCPT_PHASE_TIMING
     LaneUse lu = {0, 0, 0, 0, 0, 0};
@@ -429,8 +425,8 @@ __global__ void __launch_bounds__(kQueryBlock) query_kernel(const QueryParams q)
     r.d = live ? v3(q.d[3 * i], q.d[3 * i + 1], q.d[3 * i + 2]) : v3(0, 0, 1);
     if (live) c.rays++;
     if (begin_ray(r, sc, q.best_init) && live)
-        while (!trav_iter<S, BOXES, true>(r, tris, nodes, leafs, stk + tid, kQueryBlock, q.spill + i, q.n,
-                                          c MCPT_LU_ARG, pairs)) {
+        while (!trav_iter<S, BOXES, true>(r, sv.tris, sv.nodes, sv.leafs, stk + tid, kQueryBlock, q.spill + i, q.n,
+                                          c MCPT_LU_ARG, sv.pairs)) {
         }
     if (live) {
         q.slot[i] = r.htri < 0 ? -1 : r.htri / 3;
@@ -441,67 +437,56 @@ __global__ void __launch_bounds__(kQueryBlock) query_kernel(const QueryParams q)
     flush_counters(c, q.stats);
 }
 
-template <bool IN_LDS, int S, int BLOCK>
+// LIST: the pixel-list kernel (CVMCTracer mode, no per-unit counters: launch_render_list)
+template <bool LIST, bool IN_LDS, int S, int BLOCK>
 hipError_t launch_path(const KernelParams& kp, int grid, size_t lds, hipStream_t st) {
     const bool qe = kp.mode == kModeQE;
-    auto kern = kp.unit_counters
+    auto kern = LIST ? (kp.lean ? list_kernel<IN_LDS, S, BLOCK, false> : list_kernel<IN_LDS, S, BLOCK, true>)
+                : kp.unit_counters
                     ? (qe ? path_kernel<IN_LDS, S, BLOCK, true, true, true> : path_kernel<IN_LDS, S, BLOCK, true, false, true>)
                 : kp.lean ? (qe ? path_kernel<IN_LDS, S, BLOCK, false, true, false>
                                 : path_kernel<IN_LDS, S, BLOCK, false, false, false>)
                           : (qe ? path_kernel<IN_LDS, S, BLOCK, false, true, true>
                                 : path_kernel<IN_LDS, S, BLOCK, false, false, true>);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, kp);
-    return hipGetLastError();
+    return launch_dyn_lds(kern, dim3(grid), dim3(BLOCK), lds, st, kp);
 }
 
-template <bool IN_LDS, int S, int BLOCK>
-hipError_t launch_list(const KernelParams& kp, int grid, size_t lds, hipStream_t st) {
-    auto kern = kp.lean ? list_kernel<IN_LDS, S, BLOCK, false> : list_kernel<IN_LDS, S, BLOCK, true>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, kp);
-    return hipGetLastError();
+// the scene's megakernel variant, launched (path_kernel, or LIST list_kernel)
+template <bool LIST>
+hipError_t launch_megakernel(const KernelParams& kp, const MegakernelVariant& v, int cus, hipStream_t st) {
+    const uint32_t img = kp.scene.image_bytes;
+    if (!v.in_lds)
+        return launch_path<LIST, false, 8, kGlobalBlock>(kp, cus * kGlobalBlocksPerCu, lds_bytes_global(8, false), st);
+    if (v.S == 8) return launch_path<LIST, true, 8, kLdsBlock>(kp, cus, lds_bytes_in_lds(img, 8), st);
+    return launch_path<LIST, true, 4, kLdsBlock>(kp, cus, lds_bytes_in_lds(img, 4), st);
 }
 
 }  // namespace
 
-// LDS need of the in-LDS variant for a scene image of `image_bytes`
 size_t lds_bytes_in_lds(uint32_t image_bytes, int S) { return (size_t)image_bytes + (size_t)S * kLdsBlock * 16; }
+
+MegakernelVariant megakernel_variant(const GpuScene& sc) {
+    if (!sc.node_boxes) {                          // (else: an image built for global memory)
+        if (lds_bytes_in_lds(sc.image_bytes, 8) <= kMaxLds) return {1, true, 8};
+        if (lds_bytes_in_lds(sc.image_bytes, 4) <= kMaxLds) return {2, true, 4};
+    }
+    return {3, false, 8};
+}
 
 hipError_t launch_render(const KernelParams& kp_in, int cus, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
                          hipEvent_t ev2, float4* fb, int* variant_out) {
     KernelParams kp = kp_in;
-    const uint32_t img = kp.scene.image_bytes;
-    kp.total_lanes = (uint32_t)total_lanes_for(img, cus);
+    kp.total_lanes = (uint32_t)total_lanes_for(kp.scene.image_bytes, cus);
     hipError_t e = hipMemsetAsync(kp.counter, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
     if (ev0 && (e = hipEventRecord(ev0, st)) != hipSuccess) return e;
-    int variant = 0;
-    if (!kp.npix_local) {                          // a shard that owns no tile: nothing to trace
-        variant = kp.scene.node_boxes ? 3 : lds_bytes_in_lds(img, 8) <= kMaxLds ? 1
-                                          : lds_bytes_in_lds(img, 4) <= kMaxLds ? 2 : 3;
-    } else if (kp.scene.node_boxes) {              // image built for global memory
-        variant = 3;
-        e = launch_path<false, 8, kGlobalBlock>(kp, cus * kGlobalBlocksPerCu, (size_t)8 * kGlobalBlock * 16, st);
-    } else if (lds_bytes_in_lds(img, 8) <= kMaxLds) {
-        variant = 1;
-        e = launch_path<true, 8, kLdsBlock>(kp, cus, lds_bytes_in_lds(img, 8), st);
-    } else if (lds_bytes_in_lds(img, 4) <= kMaxLds) {
-        variant = 2;
-        e = launch_path<true, 4, kLdsBlock>(kp, cus, lds_bytes_in_lds(img, 4), st);
-    } else {
-        variant = 3;
-        e = launch_path<false, 8, kGlobalBlock>(kp, cus * kGlobalBlocksPerCu, (size_t)8 * kGlobalBlock * 16, st);
-    }
+    const MegakernelVariant v = megakernel_variant(kp.scene);
+    if (kp.npix_local) e = launch_megakernel<false>(kp, v, cus, st);   // (a shard that owns no tile: nothing to trace)
     if (e != hipSuccess) return e;
     if (ev1 && (e = hipEventRecord(ev1, st)) != hipSuccess) return e;
     e = launch_reduce(kp, fb, st);
     if (e == hipSuccess && ev2) e = hipEventRecord(ev2, st);
-    if (variant_out) *variant_out = variant;
+    if (variant_out) *variant_out = v.variant;
     return e;
 }
 
@@ -511,26 +496,15 @@ hipError_t launch_render_list(const KernelParams& kp_in, int cus, hipStream_t st
                               int* variant_out) {
     KernelParams kp = kp_in;
     if (!kp.pixel_list || kp.mode == kModeQE || kp.unit_counters) return hipErrorInvalidValue;
-    const uint32_t img = kp.scene.image_bytes;
-    kp.total_lanes = (uint32_t)total_lanes_for(img, cus);
+    kp.total_lanes = (uint32_t)total_lanes_for(kp.scene.image_bytes, cus);
     hipError_t e = hipMemsetAsync(kp.counter, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
     if (ev0 && (e = hipEventRecord(ev0, st)) != hipSuccess) return e;
-    int variant = 3;
-    if (kp.scene.node_boxes) {
-        e = launch_list<false, 8, kGlobalBlock>(kp, cus * kGlobalBlocksPerCu, (size_t)8 * kGlobalBlock * 16, st);
-    } else if (lds_bytes_in_lds(img, 8) <= kMaxLds) {
-        variant = 1;
-        e = launch_list<true, 8, kLdsBlock>(kp, cus, lds_bytes_in_lds(img, 8), st);
-    } else if (lds_bytes_in_lds(img, 4) <= kMaxLds) {
-        variant = 2;
-        e = launch_list<true, 4, kLdsBlock>(kp, cus, lds_bytes_in_lds(img, 4), st);
-    } else {
-        e = launch_list<false, 8, kGlobalBlock>(kp, cus * kGlobalBlocksPerCu, (size_t)8 * kGlobalBlock * 16, st);
-    }
+    const MegakernelVariant v = megakernel_variant(kp.scene);
+    e = launch_megakernel<true>(kp, v, cus, st);
     if (e != hipSuccess) return e;
     if (ev1 && (e = hipEventRecord(ev1, st)) != hipSuccess) return e;
-    if (variant_out) *variant_out = variant;
+    if (variant_out) *variant_out = v.variant;
     return e;
 }
 
@@ -566,7 +540,7 @@ hipError_t launch_gather(const GatherParams& g, hipStream_t st) {
 
 int total_lanes_for(uint32_t image_bytes, int cus) {
     // an image that fits in LDS is built without leaf boxes (capi.cpp build_image)
-    if (lds_bytes_in_lds(image_bytes, 4) + 32 <= kMaxLds) return cus * kLdsBlock;
+    if (lds_bytes_counted_in_lds(image_bytes, 4) <= kMaxLds) return cus * kLdsBlock;
     return cus * (kGlobalBlocksPerCu > kWfGlobalSegsPerCu ? kGlobalBlocksPerCu : kWfGlobalSegsPerCu) * kGlobalBlock;
 }
 

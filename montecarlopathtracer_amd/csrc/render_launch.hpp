@@ -1,4 +1,6 @@
-// render_launch.hpp -- device scene image layout and kernel parameters.
+// render_launch.hpp -- device scene image layout, kernel parameters, and the
+// host side's shared launch helpers: LDS bytes of a workgroup (lds_bytes_*),
+// the megakernel's variant choice, launch_dyn_lds.
 //
 // Scene image (one contiguous device buffer, 16-byte aligned sections; the
 // same bytes are copied verbatim into LDS by the in-LDS kernel variant):
@@ -232,8 +234,44 @@ struct WfParams {
 #endif
 };
 
+// LDS need of the in-LDS variant for a scene image of `image_bytes`: the
+// stack's S entries per lane, then the image
 size_t lds_bytes_in_lds(uint32_t image_bytes, int S);
+// The persistent kernels that hand out slots from an LDS counter (wavefront
+// extends, ray queries) keep it behind the stack and the image, in a 32-B block:
+// LDS bytes of such a workgroup with the scene in LDS, and with it in global memory
+constexpr size_t kLdsCounterBytes = 32;
+inline size_t lds_bytes_counted_in_lds(uint32_t image_bytes, int S) {
+    return lds_bytes_in_lds(image_bytes, S) + kLdsCounterBytes;
+}
+constexpr size_t lds_bytes_global(int S, bool counted) {
+    return (size_t)S * kGlobalBlock * 16 + (counted ? kLdsCounterBytes : 0);
+}
+// the megakernel's variant for a scene (mcpt_render_stats::variant): 1 / 2 the
+// image in LDS with S = 8 / 4 stack entries, 3 in global memory (an image built
+// with child boxes, or one too large for LDS)
+struct MegakernelVariant {
+    int variant;
+    bool in_lds;
+    int S;
+};
+MegakernelVariant megakernel_variant(const GpuScene& sc);
 int total_lanes_for(uint32_t image_bytes, int cus);
+#ifdef __HIP__
+// a kernel's dynamic LDS limit raised to lds_bytes; then also its launch
+template <typename K>
+hipError_t set_dyn_lds(K kernel, size_t lds_bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)lds_bytes);
+}
+template <typename K, typename... Args>
+hipError_t launch_dyn_lds(K kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Args&... args) {
+    const hipError_t e = set_dyn_lds(kernel, lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, st, args...);
+    return hipGetLastError();
+}
+#endif
 // memset counter, path kernel (events ev0/ev1 around it), reduce kernel (ev2)
 hipError_t launch_render(const KernelParams& kp, int cus, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
                          hipEvent_t ev2, float4* fb, int* variant_out);

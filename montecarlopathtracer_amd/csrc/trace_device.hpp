@@ -3,6 +3,8 @@
 // interval, the exact Cramer test with its prefilter, the resumable ordered
 // KD traversal step, pixel mapping and primary-ray generation.  Both
 // pipelines run exactly these operations, so their images are bit-identical.
+// Also the scene prologue every traversal kernel starts with (SceneView,
+// open_scene, MCPT_COPY_SCENE_TO_LDS) and opaque().
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -776,6 +778,51 @@ __device__ __forceinline__ void bound_counters(Counters& c, unsigned long long* 
         flush_counters(c, stats);
         c = Counters{0, 0, 0, 0, 0, 0, 0, 0};
     }
+}
+
+// x through a register move the compiler cannot see through: the value no
+// longer counts as memory-loaded (wavefront.hip wf_extend says what for)
+__device__ __forceinline__ float opaque(float x) {
+    float y;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(y) : "v"(x));
+    return y;
+}
+
+// ---- scene prologue ------------------------------------------------------------
+// The sections of the scene image a kernel reads (render_launch.hpp), in the
+// workgroup's LDS copy or in global memory; pairs (the global-memory variants'
+// 48-B pair records) is always the global image.
+struct SceneView {
+    const float4* tris;
+    const uint2* nodes;                   // node i at slot i + 1
+    const uint32_t* leafs;
+    const GpuGeom* geoms;
+    const uint4* pairs;
+};
+// The workgroup copies the scene image to lds_image (unsigned char*; the
+// caller's __syncthreads() ends the copy).  Source text, not a function: as an
+// inlined function the same loop compiled differently in the megakernel's LDS
+// variants (8 of 28 kernels of render.hip) and in wf_primary_lists.
+#define MCPT_COPY_SCENE_TO_LDS(lds_image, sc, tid, BLOCK)                                   \
+    {                                                                                       \
+        const uint4* src = reinterpret_cast<const uint4*>((sc).image);                      \
+        uint4* dst = reinterpret_cast<uint4*>(lds_image);                                   \
+        const uint32_t n16 = (sc).image_bytes / 16u;                                        \
+        for (uint32_t i = (uint32_t)(tid); i < n16; i += (BLOCK)) dst[i] = src[i];          \
+    }
+// IN_LDS: the copy above, and a view of it; else a view of the global image
+// (lds_image, BLOCK and tid unused).  No barrier: the kernels place it differently.
+template <bool IN_LDS, int BLOCK>
+__device__ __forceinline__ SceneView open_scene(unsigned char* lds_image, const GpuScene& sc, int tid) {
+    if constexpr (IN_LDS) MCPT_COPY_SCENE_TO_LDS(lds_image, sc, tid, BLOCK);
+    const unsigned char* const base = IN_LDS ? lds_image : sc.image;
+    SceneView v;
+    v.tris = reinterpret_cast<const float4*>(base + sc.off_tris);
+    v.nodes = reinterpret_cast<const uint2*>(base + sc.off_nodes) + 1;
+    v.leafs = reinterpret_cast<const uint32_t*>(base + sc.off_leafs);
+    v.geoms = reinterpret_cast<const GpuGeom*>(base + sc.off_geoms);
+    v.pairs = reinterpret_cast<const uint4*>(sc.image + sc.off_nodes);
+    return v;
 }
 
 

@@ -34,162 +34,25 @@
 // operation is shared (trace_device.hpp), so the image is bit-identical to the
 // megakernel's and the oracle's; queue order is scheduling-dependent but
 // nothing reads it: a path's state is keyed by its path id.
+//
+// Where things live: the queue layout, the dealing of paths to segments and
+// the MCPT_WF_* tuning macros are in wf_device.hpp; bounce 0's packet extend
+// and its primary-list form (wf_extend_primary, wf_primary_lists) are in
+// wavefront_primary.hip, a translation unit with flags of its own, reached
+// through launch_wavefront_primary[_lists]; every other kernel and the host
+// pipeline are here.
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
 #include <cstdlib>
 
-#include "mcpt_device.hpp"
-#include "render_launch.hpp"
-#include "trace_device.hpp"
-
-
-// MCPT_WF_PRIMARY_TU = 1 (wavefront_primary.hip): this file compiled for the
-// bounce-0 packet extend alone, in a translation unit of its own so that it
-// can take its own code-generation flags (_build.py: its wave-uniform control
-// flow left unstructurized); every other kernel and the host launch code are
-// compiled here with MCPT_WF_PRIMARY_TU = 0.
-#ifndef MCPT_WF_PRIMARY_TU
-#define MCPT_WF_PRIMARY_TU 0
-#endif
+#include "wf_device.hpp"
 
 namespace mcpt {
-
-using namespace dev;
-using namespace trace;
-
 namespace {
 
 constexpr int kGenBlock = 256;
 constexpr int kClassTerminate = 0;
-// Rays are carried as (o.xyz, pid) and (d.xyz, depth); depth kNoRay marks a
-// queue slot without a ray (pixel outside the image): it ends as a miss with
-// zero radiance and is counted nowhere, like the megakernel's empty units.
-constexpr uint32_t kNoRay = 0xFFFFFFFFu;
 
-__device__ __forceinline__ float opaque(float x) {
-    float y;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(y) : "v"(x));
-    return y;
-}
-__device__ __forceinline__ float4 pack(V3 v, uint32_t w) { return make_float4(v.x, v.y, v.z, __uint_as_float(w)); }
-
-// Queue layout: field k of slot j (kQO {o, pid}, kQD {d, depth}, kQPS
-// {throughput, rng}: SoA float4 streams of slot_stride entries each, then
-// kQHIT, the 4-B hit ids) -- extend's ray reads and hit writes are dense lane
-// streams (64-B AoS records: generate 9 -> 33 ms per C2 frame, round 2).
-// WfParams::sort (mcpt_render_params::wf_sort): 0 (default) -- shade takes its
-// segment's queue in slot order, dense streams, the merged samplers absorbing
-// the material mix; 1 -- shade sorts each block of slots by material first
-// (wf_shade_slots SORTB).  Either way continuing rays go to the next queue
-// with one LDS atomic per wave.  (Until round 6 the sort went through
-// per-class slot lists that extend appended to and shade gathered from: 9.5
-// against 13.6 G rays/s for the block sort on C2, PERFLOG row 156.)
-__device__ __forceinline__ size_t qf(uint32_t slot, uint32_t k, uint32_t stride) {
-    return (size_t)k * stride + slot;
-}
-// queue streams: origin + path id, direction + depth, throughput + RNG state,
-// hit (last: it holds only 4-B triangle ids, so the queue is 3 x 16 + 4 B per
-// slot)
-constexpr uint32_t kQO = 0, kQD = 1, kQPS = 2, kQHIT = 3;
-__device__ __forceinline__ V3 xyz(float4 v) { return v3(v.x, v.y, v.z); }
-
-// Queue streams are touched once per bounce: MCPT_WF_NT marks the streaming
-// reads (bit 0) and writes (bit 1) of generate, shade and extend's ray reads
-// non-temporal, so that they do not push extend's partially written hit lines
-// out of the L2.  Default 3 (C2 wavefront +3.5%, C4 +2%; the 4-B hit ids
-// themselves are plain stores, PERFLOG row 79).
-#ifndef MCPT_WF_NT
-#define MCPT_WF_NT 3
-#endif
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ldq(const float4* p) {
-#if MCPT_WF_NT & 1
-    const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return *p;
-#endif
-}
-__device__ __forceinline__ void stq(float4* p, float4 v) {
-#if MCPT_WF_NT & 2
-    const f32x4 x = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(x, reinterpret_cast<f32x4*>(p));
-#else
-    *p = v;
-#endif
-}
-
-// Group k of block b (b-th run of nseg consecutive groups) -> its segment:
-// every block deals one group to each segment, rotated by a hash of b.  With
-// a plain k -> k (an image of 2^14 8x8 tiles, 256 segments) each segment got
-// the same 64 tiles for every sample -- a fixed stripe of the image, whose
-// cost differs from the others' and left CUs idle at the end of every extend.
-// WfParams::xcd_deal (global-memory scenes, MCPT_WF_XCD): the rotation is a
-// multiple of 8, so group k of every block goes to a segment g = k (mod 8).
-// Extend and shade workgroup g (one per segment) is dispatched to XCD g mod 8,
-// and a group's image region (a 1024x16 strip of 2^14 paths) is k mod (regions
-// per sample): every sample of a region then runs on the same XCD, whose L2
-// and the caches behind it serve the part of the scene image that region's
-// paths walk.  C4 +1.6% (9.31 / 9.34 -> 9.48 / 9.48 G rays/s; serialized
-// extends 880 -> 771 ms per two frames at the same L2 hit rate, 0.776 /
-// 0.778); LDS scenes keep the finer rotation (C2 -2.3% with it: the coarser
-// rotation balances the segments' work less well).
-#ifndef MCPT_WF_XCD
-#define MCPT_WF_XCD 1
-#endif
-__device__ __forceinline__ uint32_t seg_of(uint32_t k, uint32_t b, uint32_t nseg, bool xcd) {
-    const uint32_t rot = (MCPT_WF_XCD && xcd && (nseg & 7u) == 0u)
-                             ? (uint32_t)(((uint64_t)(b * 2654435761u) * (nseg >> 3)) >> 32) << 3
-                             : (uint32_t)(((uint64_t)(b * 2654435761u) * nseg) >> 32);
-    const uint32_t g = k + rot;
-    return g >= nseg ? g - nseg : g;
-}
-
-// Inverse of generate's dealing: path id of local slot j of segment g's queue 0.
-__device__ __forceinline__ uint32_t slot_pid(const WfParams& wf, uint32_t g, uint32_t j) {
-    const uint32_t gs = wf.group_shift, blk = j >> gs;
-    const uint32_t rot = seg_of(0, blk, wf.nseg, wf.xcd_deal);
-    const uint32_t k = g >= rot ? g - rot : g + wf.nseg - rot;
-    return ((blk * wf.nseg + k) << gs) | (j & ((1u << gs) - 1u));
-}
-
-// Length of segment g's queue 0 for the batch: its whole groups (the last
-// group of the batch may be partial).  Written by generate, or by the
-// generate-free bounce-0 extend (MCPT_WF_GEN0).
-__device__ __forceinline__ uint32_t seg_queue0_len(const WfParams& wf, uint32_t g) {
-    const uint32_t n = wf.nb * wf.ns;
-    const uint32_t gs = wf.group_shift, gm = (1u << gs) - 1u;
-    const uint32_t ngroups = (n + gm) >> gs;
-    const uint32_t full = ngroups / wf.nseg, rem = ngroups - full * wf.nseg;
-    // block `full` (partial, rem groups) covers segments rot, rot+1, ... (mod nseg)
-    const uint32_t k = (g + wf.nseg - seg_of(0, full, wf.nseg, wf.xcd_deal)) % wf.nseg;
-    uint32_t len = (full + (k < rem ? 1u : 0u)) << gs;
-    const uint32_t lb = (ngroups - 1u) / wf.nseg;            // block of the last group
-    if (seg_of(ngroups - 1u - lb * wf.nseg, lb, wf.nseg, wf.xcd_deal) == g) len -= (ngroups << gs) - n;
-    return len;
-}
-
-// MCPT_WF_IMPLICIT0 = 1: bounce 0's shade (queue order, CV mode) recomputes a
-// primary ray's origin, direction and RNG state from its slot instead of
-// reading them, and generate skips the {throughput, rng} stream (64 B of
-// queue traffic less per path); 2 (default): also the {o, pid} stream
-// (extend's bounce-0 origins are the eye; 32 B more).  With MCPT_WF_NT = 3:
-// level 1 C2 wavefront +0.3%, level 2 +0.9% (C4 +1.4%).
-#ifndef MCPT_WF_IMPLICIT0
-#define MCPT_WF_IMPLICIT0 2
-#endif
-__host__ __device__ __forceinline__ bool implicit0(const KernelParams& kp, const WfParams& wf) {
-    return MCPT_WF_IMPLICIT0 && kp.mode != kModeQE;
-}
-// Hit ids: extend writes only the hit triangle's id (4 B, the
-// first quarter of the hit stream as i32) and shade recomputes t, beta, gamma
-// of a scattering ray from it (tri_hit_params: the traversal's own
-// operations, bit-identical).  The 16-B hit records cost the extend 2.4x their
-// bytes in partly written L2 lines; C2 wavefront +3.7% (12.70 -> 13.18, three
-// rounds), C4 +2.8%.  (capi.cpp wf_layout sizes the queues for this.)
-
-#if !MCPT_WF_PRIMARY_TU
 // ---- generate: primary rays of the batch (CUTracer.cu:186-211) -------------
 // Paths go to segments in groups of 2^group_shift (64 = one 8x8 tile of one
 // sample: a coherent wave of primary rays), group j -> segment j % nseg, so
@@ -230,71 +93,6 @@ __global__ void __launch_bounds__(kGenBlock) wf_generate(const KernelParams kp, 
     flush_counters(c, kp.stats);
 }
 
-#endif  // !MCPT_WF_PRIMARY_TU
-
-// Issue priority of the extend's traversal bursts (its hand-off runs one
-// higher); the co-resident shade runs at 0.
-#ifndef MCPT_WF_EXT_PRIO
-#define MCPT_WF_EXT_PRIO 0
-#endif
-
-// Descent steps per traversal call in the wavefront extend (the megakernel's
-// MCPT_DESCENT_CAP is 4): with shading out of the loop a longer descent burst
-// pays (C2 wf cap 3 / 4 / 5 / 6: 13.57 / 13.64 / 13.84 / 13.57 G rays/s)
-#ifndef MCPT_WF_DESCENT_CAP
-#define MCPT_WF_DESCENT_CAP 5
-#endif
-// Global-memory scenes: 6 since round 6's cheaper descent step (C4 cap
-// 4 / 5 / 6 / 7: 10.84 / 11.19 / 11.40 / 11.06 and 10.86 / 11.14 / 11.30 /
-// 11.05 G rays/s, PERFLOG row 164); the megakernel keeps MCPT_DESCENT_CAP_GLOBAL
-#ifndef MCPT_WF_DESCENT_CAP_GLOBAL
-#define MCPT_WF_DESCENT_CAP_GLOBAL 6
-#endif
-constexpr int kWfLdsCap = MCPT_WF_DESCENT_CAP;
-
-// Residency of the global-memory extend (C4: a walk bound by the latency of
-// node and triangle reads from L2 / MALL, so every resident wave counts).
-// Workgroups of 256 threads, kGlobalBlocksPerCu per CU per launch; other
-// streams' extends fill further slots as far as LDS and VGPRs allow.
-// MCPT_WF_GLOBAL_S: LDS stack entries per lane; MCPT_WF_GLOBAL_WAVES: waves per
-// SIMD the compiler must allow (its VGPR budget; the lean kernel only -- the
-// untimed counting kernels keep their registers) -- with 256-thread
-// workgroups (one wave per SIMD each) that is the resident workgroups per CU.
-// 6 x 6: 80 VGPRs (no scratch) and 6 x 24 KB of LDS, six extend waves per
-// SIMD.  C4 G rays/s:
-// S = 8, no hint (round 3: 32 KB, four workgroups, 88 VGPRs) 9.46 / 9.47;
-// S = 6 9.61 / 9.63; S = 7 (five workgroups) 9.85 / 9.87; S = 5 9.20; S = 4
-// 8.78 (spills); S = 6 with six workgroups (80 VGPRs) 10.36 / 10.31.
-#ifndef MCPT_WF_GLOBAL_S
-#define MCPT_WF_GLOBAL_S 6
-#endif
-#ifndef MCPT_WF_GLOBAL_WAVES
-#define MCPT_WF_GLOBAL_WAVES 6
-#endif
-static_assert(kGlobalBlock == 256, "MCPT_WF_GLOBAL_WAVES = workgroups per CU only for one wave per SIMD each");
-#ifndef MCPT_WF_GLOBAL_PREFETCH
-#define MCPT_WF_GLOBAL_PREFETCH 1
-#endif
-// register budgets (waves per SIMD the compiler plans for; 0 = none) of the
-// LDS scenes' lean extend and of the queue-order shade, and the shade's
-// workgroup beside an LDS extend workgroup (512: two waves per SIMD)
-#ifndef MCPT_WF_LDS_WPE
-#define MCPT_WF_LDS_WPE 0
-#endif
-#ifndef MCPT_WF_SHADE_WPE
-#define MCPT_WF_SHADE_WPE 0
-#endif
-#ifndef MCPT_WF_SHADE_LDS_BLOCK
-#define MCPT_WF_SHADE_LDS_BLOCK 512
-#endif
-#ifndef MCPT_WF_GEO_LDS
-#define MCPT_WF_GEO_LDS 1
-#endif
-constexpr size_t kLdsPerCu = 160 * 1024;
-constexpr int kLayGlobal = 0, kLayLds = 1;
-
-
-#if !MCPT_WF_PRIMARY_TU
 // ---- extend: closest hit of every ray of this workgroup's segment -----------
 // COUNT = false (lean renders): the traversal counters are compiled out.
 // LAY: kLayGlobal (scene image with child-box records in global memory) or
@@ -322,23 +120,7 @@ wf_extend(const KernelParams kp, const WfParams wf) {
     unsigned char* const lds_image = smem + (size_t)S * BLOCK * 16;
     uint32_t* const lslot = reinterpret_cast<uint32_t*>(lds_image + (IN_LDS ? sc.image_bytes : 0u));
     if (tid == 0) *lslot = 0;
-    const float4* tris;
-    const uint2* nodes;
-    const uint32_t* leafs;
-    if constexpr (IN_LDS) {
-        const uint4* src = reinterpret_cast<const uint4*>(sc.image);
-        uint4* dst = reinterpret_cast<uint4*>(lds_image);
-        const uint32_t n16 = sc.image_bytes / 16u;
-        for (uint32_t i = (uint32_t)tid; i < n16; i += BLOCK) dst[i] = src[i];
-        tris = reinterpret_cast<const float4*>(lds_image + sc.off_tris);
-        nodes = reinterpret_cast<const uint2*>(lds_image + sc.off_nodes) + 1;
-        leafs = reinterpret_cast<const uint32_t*>(lds_image + sc.off_leafs);
-    } else {
-        tris = reinterpret_cast<const float4*>(sc.image + sc.off_tris);
-        nodes = reinterpret_cast<const uint2*>(sc.image + sc.off_nodes) + 1;
-        leafs = reinterpret_cast<const uint32_t*>(sc.image + sc.off_leafs);
-    }
-    const uint4* pairs = reinterpret_cast<const uint4*>(sc.image + sc.off_nodes);   // 48-B pair records (global variant)
+    const SceneView sv = open_scene<IN_LDS, BLOCK>(lds_image, sc, tid);
     __syncthreads();
     uint4* st = reinterpret_cast<uint4*>(smem) + tid;
     uint4* spill = kp.spill + (blockIdx.x * BLOCK + (uint32_t)tid);
@@ -407,8 +189,8 @@ wf_extend(const KernelParams kp, const WfParams wf) {
 #endif
             MCPT_MARK(5);
             if (mode == kTrav) {
-                if (trav_iter<S, !IN_LDS, COUNT, LAY == kLayLds, IN_LDS ? kWfLdsCap : MCPT_WF_DESCENT_CAP_GLOBAL>(r, tris, nodes, leafs, st, BLOCK, spill, spill_stride, c MCPT_LU_ARG,
-                                                 pairs))
+                if (trav_iter<S, !IN_LDS, COUNT, LAY == kLayLds, IN_LDS ? kWfLdsCap : MCPT_WF_DESCENT_CAP_GLOBAL>(
+                        r, sv.tris, sv.nodes, sv.leafs, st, BLOCK, spill, spill_stride, c MCPT_LU_ARG, sv.pairs))
                     mode = kReady;
             }
             MCPT_MARK(6);
@@ -489,71 +271,6 @@ wf_extend(const KernelParams kp, const WfParams wf) {
     if (tid == 0) cn->hits = count;                        // every slot's hit id is written
 }
 
-#endif  // !MCPT_WF_PRIMARY_TU
-
-// ---- extend of bounce 0, wave-coherent (CV mode, queue-order shade) ---------
-// Primary rays share the eye as their origin, and generate deals them in
-// 64-path groups -- one 8x8 tile of one sample -- so a wave takes one group
-// and walks the KD tree ONCE for its 64 rays: the node is wave-uniform (read
-// by one LDS broadcast), each lane keeps its own interval, hit and an active
-// flag, and the wave enters a child if any lane's interval reaches it.  With
-// a common origin every lane has the same near side at every split plane (an
-// origin exactly on the plane leaves only lanes inside the plane needing both
-// children, and their near child is the left one), so the wave's front-to-back
-// order is each lane's own: a lane is active at exactly the nodes its own
-// ordered walk (trav_iter) visits, with the same interval and best hit there,
-// and it stops at the same pop.  Hits, visit and test counts are therefore
-// those of the per-ray walk, bit for bit; only the schedule differs (one
-// wave-uniform descent per node instead of 64 divergent ones).
-// Stack: the per-ray walk's lazy LDS stack (S entries in LDS, older ones in
-// the spill area) with a wave-uniform position; a lane's copy of an entry
-// carries its interval, or tmax = NaN if the lane is not in that subtree.
-#ifndef MCPT_WF_PACKET0
-#define MCPT_WF_PACKET0 1
-#endif
-__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-// read-only words another kernel wrote, at wave-uniform addresses: the
-// constant address space (scalar loads; wf_primary_body.hpp)
-typedef const __attribute__((address_space(4))) uint32_t const_u32;
-typedef const __attribute__((address_space(4))) u32x4 const_u32x4;
-
-// MCPT_WF_GEN0 (default 1): no generate kernel before this extend -- each
-// lane computes its slot's primary ray itself (the inverse dealing slot_pid
-// and primary_ray, as bounce 0's shade already does), writes the segment's
-// queue length and counts the paths; queue 0 holds no direction stream.
-// Generate was the only kernel of a frame's start (0.9 ms of one rank's 33 ms
-// share at N = 8) and moved 16 B per path through HBM twice.
-#ifndef MCPT_WF_GEN0
-#define MCPT_WF_GEN0 1
-#endif
-// The kernel's body is wf_primary_body.hpp, included once per kernel below:
-// source text, not a function, so that wf_extend_primary's code stays what it
-// was without the second kernel (inlined from a shared function, its epilogue
-// came out one instruction shorter).
-// LIST (wf_primary_lists, render_launch.hpp MCPT_PRIMARY_LISTS; lean renders
-// whose groups are whole 8x8 tiles): a group first reads its tile's candidate
-// record (wf_tile_candidates), fetched one group ahead.  No candidate: every
-// lane's ray is a miss, and nothing but the path count is computed.  Up to
-// kListK: each lane makes its ray as the walk would (a root-box miss stays a
-// miss) and tests the listed triangles two at a time from their LDS records,
-// the next pair's indices loaded behind the current pair's tests.  More: the
-// packet walk.  (Its name must not contain "wf_extend": the resource pins
-// count the kernels that do.)
-template <int S, int BLOCK, bool COUNT>
-__global__ void __launch_bounds__(BLOCK, 1) wf_extend_primary(const KernelParams kp, const WfParams wf) {
-    constexpr bool LIST = false;
-#include "wf_primary_body.hpp"
-}
-#if MCPT_PRIMARY_LISTS
-// (<= 88 VGPRs, as the LDS scenes' other lean extends: two shade waves per SIMD beside it)
-template <int S, int BLOCK>
-__global__ void __launch_bounds__(BLOCK, 1) wf_primary_lists(const KernelParams kp, const WfParams wf) {
-    constexpr bool LIST = true, COUNT = false;
-#include "wf_primary_body.hpp"
-}
-#endif
-
-#if !MCPT_WF_PRIMARY_TU
 // ---- shade: one workgroup per segment, its queue in blocks of slots ---------
 // Reads the segment's queue b as dense streams (o, d, hit, throughput/rng),
 // finishes terminated paths (radiance by path id) and scatters the others; a
@@ -594,8 +311,9 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
         for (uint32_t i = threadIdx.x; i < sc.n_geoms * 4u; i += BLOCK) dst[i] = src[i];
     }
     __syncthreads();
-    const float4* tris = reinterpret_cast<const float4*>(sc.image + sc.off_tris);
-    const GpuGeom* geoms = GEO_LDS ? lgeo : reinterpret_cast<const GpuGeom*>(sc.image + sc.off_geoms);
+    const SceneView sv = open_scene<false, BLOCK>(nullptr, sc, 0);
+    const float4* tris = sv.tris;
+    const GpuGeom* geoms = GEO_LDS ? lgeo : sv.geoms;
     const size_t seg0 = (size_t)g * wf.seg;
     const float4* qb = wf.q[wf.bounce & 1];
     float4* qb2 = wf.q[(wf.bounce + 1) & 1];
@@ -840,7 +558,7 @@ __global__ void __launch_bounds__(kCandBlock) wf_tile_candidates(const KernelPar
     double ext = 0.0;
     for (int a = 0; a < 3; a++) ext = fmax(ext, (double)sc.root_max[a] - (double)sc.root_min[a]);
     const double m0 = 1e-3 * ext;
-    const float4* tris = reinterpret_cast<const float4*>(sc.image + sc.off_tris);
+    const float4* tris = open_scene<false, kCandBlock>(nullptr, sc, 0).tris;
     uint32_t* rec = wf.tile_cand + (size_t)tile * kListRecWords;
     uint32_t n = 0;                                         // candidates so far (wave-uniform)
     for (uint32_t i0 = 0; i0 < sc.n_tris; i0 += 64u) {
@@ -886,30 +604,6 @@ __global__ void __launch_bounds__(256) wf_accumulate(const KernelParams kp, cons
     kp.partial[(size_t)(wf.chunk_index + j) * kp.npix_local + wf.v0 + u] = make_float4(part.x, part.y, part.z, 0.0f);
 }
 
-#endif  // !MCPT_WF_PRIMARY_TU
-
-template <int S, int BLOCK>
-hipError_t launch_extend_primary(const KernelParams& kp, const WfParams& wf, int grid, size_t lds, hipStream_t st) {
-    auto kern = kp.lean ? wf_extend_primary<S, BLOCK, false> : wf_extend_primary<S, BLOCK, true>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, kp, wf);
-    return hipGetLastError();
-}
-#if MCPT_PRIMARY_LISTS
-template <int S, int BLOCK>
-hipError_t launch_primary_lists(const KernelParams& kp, const WfParams& wf, int grid, size_t lds, hipStream_t st) {
-    auto kern = wf_primary_lists<S, BLOCK>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, kp, wf);
-    return hipGetLastError();
-}
-#endif
-
-#if !MCPT_WF_PRIMARY_TU
 template <int BLOCK>
 auto shade_kernel(bool geo_lds, bool sortb) {
     return sortb ? (geo_lds ? wf_shade_slots<BLOCK, true, true> : wf_shade_slots<BLOCK, false, true>)
@@ -919,40 +613,14 @@ auto shade_kernel(bool geo_lds, bool sortb) {
 template <int LAY, int S, int BLOCK>
 hipError_t launch_extend(const KernelParams& kp, const WfParams& wf, int grid, size_t lds, hipStream_t st) {
     auto kern = kp.lean ? wf_extend<LAY, S, BLOCK, false> : wf_extend<LAY, S, BLOCK, true>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, kp, wf);
-    return hipGetLastError();
+    return launch_dyn_lds(kern, dim3(grid), dim3(BLOCK), lds, st, kp, wf);
 }
 
 // the scene image (8-B node records) is copied into LDS; an image built with
 // child-box pair records (node_boxes) is always read from global memory
-bool wf_in_lds(const GpuScene& sc) { return !sc.node_boxes && lds_bytes_in_lds(sc.image_bytes, 4) + 32 <= kMaxLds; }
+bool wf_in_lds(const GpuScene& sc) { return !sc.node_boxes && lds_bytes_counted_in_lds(sc.image_bytes, 4) <= kMaxLds; }
 
-#endif  // !MCPT_WF_PRIMARY_TU
 }  // namespace
-
-#if MCPT_WF_PRIMARY_TU
-// the bounce-0 packet extend's launch, called by launch_wavefront (the other
-// translation unit)
-hipError_t launch_wavefront_primary(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
-                                    hipStream_t st) {
-    return launch_extend_primary<4, kLdsBlock>(kp, wf, grid, lds, st);
-}
-#if MCPT_PRIMARY_LISTS
-hipError_t launch_wavefront_primary_lists(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
-                                          hipStream_t st) {
-    return launch_primary_lists<4, kLdsBlock>(kp, wf, grid, lds, st);
-}
-#endif
-#else
-hipError_t launch_wavefront_primary(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
-                                    hipStream_t st);   // wavefront_primary.hip
-#if MCPT_PRIMARY_LISTS
-hipError_t launch_wavefront_primary_lists(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
-                                          hipStream_t st);   // wavefront_primary.hip
-#endif
 
 #ifdef MCPT_PHASE_TIMING
 void read_lane_use_wf(unsigned long long out[6]) {   // wavefront extend lane-use counters, then reset
@@ -967,7 +635,7 @@ int wavefront_segments(const GpuScene& sc, int cus) {
 }
 // LDS bytes of an LDS-scene extend workgroup: stack + image (or its part from the nodes on) + counters
 size_t wf_lds_extend_bytes(const GpuScene& sc) {
-    return lds_bytes_in_lds(sc.image_bytes, 4) + 32;
+    return lds_bytes_counted_in_lds(sc.image_bytes, 4);
 }
 
 hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, const WfStreams& ws, int cus,
@@ -1052,7 +720,7 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
             // the shade's material table in LDS if it fits beside the extend's
             // workgroups on a CU (MCPT_WF_GEO_LDS)
             const size_t ext_lds = in_lds ? wf_lds_extend_bytes(kp.scene)
-                                          : (size_t)kWfGlobalSegsPerCu * (MCPT_WF_GLOBAL_S * kGlobalBlock * 16 + 32);
+                                          : kWfGlobalSegsPerCu * lds_bytes_global(MCPT_WF_GLOBAL_S, true);
             const size_t geo_bytes = (MCPT_WF_GEO_LDS && ext_lds + 64 * (size_t)kp.scene.n_geoms + 64 <= kLdsPerCu)
                                          ? 64 * (size_t)kp.scene.n_geoms : 0;
             // LDS scenes: one 8x8 tile of one sample per group; global-memory
@@ -1091,9 +759,8 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
                 } else if (in_lds) {
                     e = launch_extend<kLayLds, 4, kLdsBlock>(kb, wf, (int)nseg, llds, bs);
                 } else
-                    e = launch_extend<kLayGlobal, MCPT_WF_GLOBAL_S, kGlobalBlock>(kb, wf, (int)nseg,
-                                                                            (size_t)MCPT_WF_GLOBAL_S * kGlobalBlock * 16 + 32,
-                                                              bs);
+                    e = launch_extend<kLayGlobal, MCPT_WF_GLOBAL_S, kGlobalBlock>(
+                        kb, wf, (int)nseg, lds_bytes_global(MCPT_WF_GLOBAL_S, true), bs);
                 if (e != hipSuccess) break;
                 const bool sortb = wf.sort != 0;
                 if (in_lds && ns == 1)   // alone on the GPU: 16 waves per segment keep HBM busy
@@ -1134,6 +801,5 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
     if (variant_out) *variant_out = in_lds ? 4 : 5;
     return e;
 }
-#endif  // MCPT_WF_PRIMARY_TU
 
 }  // namespace mcpt

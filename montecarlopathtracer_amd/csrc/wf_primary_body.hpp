@@ -1,5 +1,5 @@
 // wf_primary_body.hpp -- the body of the wavefront's bounce-0 packet extend,
-// included by wavefront.hip into wf_extend_primary (LIST false) and into
+// included by wavefront_primary.hip into wf_extend_primary (LIST false) and into
 // wf_primary_lists (LIST true, COUNT false): the two kernels share the packet
 // walk as source text, so the first one's code is the same with and without
 // the second (an inlined function changed its epilogue).  In scope: S, BLOCK,
@@ -27,12 +27,8 @@
     unsigned char* const lds_image = smem + (size_t)S * BLOCK * 16;
     uint32_t* lgrp = reinterpret_cast<uint32_t*>(lds_image + sc.image_bytes);
     if (tid == 0) *lgrp = 0;
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(sc.image);
-        uint4* dst = reinterpret_cast<uint4*>(lds_image);
-        const uint32_t n16 = sc.image_bytes / 16u;
-        for (uint32_t i = (uint32_t)tid; i < n16; i += BLOCK) dst[i] = src[i];
-    }
+    // (the pointers below as they are: taken from open_scene's view, one kernel's branch compiles differently)
+    MCPT_COPY_SCENE_TO_LDS(lds_image, sc, tid, BLOCK);
     const float4* tris = reinterpret_cast<const float4*>(lds_image + sc.off_tris);
     const uint2* nodes = reinterpret_cast<const uint2*>(lds_image + sc.off_nodes) + 1;
     const uint32_t* leafs = reinterpret_cast<const uint32_t*>(lds_image + sc.off_leafs);
