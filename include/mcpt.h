@@ -298,6 +298,12 @@ int mcpt_scene_get_info(const mcpt_scene* s, mcpt_scene_info* out);
  * other than zero, a non-finite Kd or Ks, no emitter, or more than 8.  (Its own
  * entry: mcpt_scene_info keeps its ABI 9 size.) */
 int mcpt_scene_terminal_cull_boxes(const mcpt_scene* s);
+/* Occluder boxes of the wavefront's miss cull (1..8 fp32 AABBs that together
+ * hold every triangle; lean renders end a path whose new ray misses them all),
+ * or 0 when the scene has none: a box would span the scene bounds, or the
+ * scene is a closed room.  boxes (may be NULL): 6 floats per box, min xyz then
+ * max xyz.  (Its own entry, as the one above; an addition, the ABI stays 9.) */
+int mcpt_scene_miss_cull_boxes(const mcpt_scene* s, float* boxes);
 /* Primary lists of the scene's last render (wavefront, lean CV renders of a
  * scene in LDS with 8x8 tiles): out[0..2] = the owned tiles whose candidate
  * list is empty (no primary ray made), holds 1..K triangles (tested straight

@@ -158,6 +158,7 @@ _SIGS = {
     "mcpt_scene_destroy": (None, [_vp]),
     "mcpt_scene_get_info": (C.c_int, [_vp, C.POINTER(SceneInfo)]),
     "mcpt_scene_terminal_cull_boxes": (C.c_int, [_vp]),
+    "mcpt_scene_miss_cull_boxes": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "mcpt_scene_primary_tile_classes": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "mcpt_scene_copy_kd": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
                                      C.POINTER(C.c_float)]),

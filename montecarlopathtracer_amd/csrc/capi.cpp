@@ -173,6 +173,9 @@ struct mcpt_scene {
     uint32_t n_cull_boxes = 0;
     uint32_t cull_box[mcpt::kMaxCullBoxes][3] = {};
     float cull_gain = 0.0f;             // the largest |Kd| or |Ks| component (finite when there are boxes)
+    // miss cull: occluder boxes {lo xyz, hi xyz}; n_miss_boxes == 0: none for the scene (host_model.hpp)
+    uint32_t n_miss_boxes = 0;
+    float miss_box[mcpt::kMaxMissBoxes][6] = {};
     void* d_image = nullptr;
     void* d_normals = nullptr;
     Workspace ws;
@@ -476,6 +479,7 @@ void build_image(mcpt_scene& s, bool force_global) {
         }
         std::memcpy(s.cull_box[b], hb, 12);
     }
+    s.n_miss_boxes = static_cast<uint32_t>(mcpt::miss_cull_boxes(hs, s.miss_box, mcpt::kMaxMissBoxes));
     s.cull_gain = 0.0f;
     for (const mcpt::Geometry& ge : hs.geoms)
         for (float k : {ge.Kd.x, ge.Kd.y, ge.Kd.z, ge.Ks.x, ge.Ks.y, ge.Ks.z})
@@ -855,6 +859,11 @@ void prepare_wavefront(mcpt_scene& s, const Plan& pl, int sets, mcpt::WfParams* 
 #if MCPT_PRIMARY_LISTS
         w.tile_cand = tiles;
         w.tile_classes = tile_classes(s);
+#endif
+#if MCPT_MISS_CULL
+        // (counting renders walk every ray: their visit counters stay the oracle's)
+        w.n_miss_boxes = pl.kp.lean ? s.n_miss_boxes : 0u;
+        std::memcpy(w.miss_box, s.miss_box, sizeof w.miss_box);
 #endif
     }
 }
@@ -1681,6 +1690,8 @@ static int scene_create_impl(const mcpt_model* m, mcpt_scene** out, bool device,
                 R->n_cull_boxes = s->n_cull_boxes;
                 std::memcpy(R->cull_box, s->cull_box, sizeof s->cull_box);
                 R->cull_gain = s->cull_gain;
+                R->n_miss_boxes = s->n_miss_boxes;
+                std::memcpy(R->miss_box, s->miss_box, sizeof s->miss_box);
                 upload(*R, devs[i], s->image, nrm);
                 HIP_TRY(hipStreamCreateWithFlags(&R->stream, hipStreamNonBlocking));
                 HIP_TRY(hipEventCreateWithFlags(&R->done, hipEventDisableTiming));
@@ -1739,6 +1750,12 @@ int mcpt_scene_primary_tile_classes(mcpt_scene* s, uint32_t out[4]) {
 
 int mcpt_scene_terminal_cull_boxes(const mcpt_scene* s) {
     return s && MCPT_TERMINAL_CULL ? static_cast<int>(s->n_cull_boxes) : 0;
+}
+
+int mcpt_scene_miss_cull_boxes(const mcpt_scene* s, float* boxes) {
+    if (!s) return 0;
+    if (boxes) std::memcpy(boxes, s->miss_box, sizeof(float) * 6 * s->n_miss_boxes);
+    return static_cast<int>(s->n_miss_boxes);
 }
 
 int mcpt_scene_copy_kd(const mcpt_scene* s, uint32_t* nodes, uint32_t* leaf_ids, int32_t* kd_tris, float* geoms) {

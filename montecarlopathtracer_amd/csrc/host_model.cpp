@@ -19,6 +19,7 @@
 #include <cstring>
 #include <deque>
 #include <fstream>
+#include <map>
 #include <numeric>
 #include <sstream>
 
@@ -495,6 +496,168 @@ int terminal_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes) {
             }
     }
     return n;
+}
+
+// ---------------------------------------------------------------------------
+// Miss cull: occluder boxes.  A secondary ray whose segment misses the box of
+// every triangle has no hit, so the shade that creates it may end the path at
+// once (trace_device.hpp may_hit_scene).  The boxes need no material
+// knowledge: bottom-up clustering from one box per triangle, always merging
+// the pair whose union adds the least volume (then the least surface area,
+// then the lower indices: deterministic), until max_boxes or fewer are left
+// and no merge is free.  Coplanar wall triangles merge at zero cost and stay
+// flat; a mesh ends as one box or a few.
+// Cost: every box keeps its cheapest partner, so a merge rescans only the
+// boxes that pointed at the merged pair -- O(n^2) pair costs up front, O(n)
+// per merge after that.  Above kMissCullExact triangles (C4's 70k mesh) the
+// triangles are pre-bucketed first: an axis-flat triangle by its plane (axis,
+// coordinate), any other by the cell of its centroid in an 8^3 grid over the
+// scene bounds, one box per bucket; should the planes alone exceed the limit
+// (a voxel mesh), flat triangles go to the grid too.
+namespace {
+
+constexpr size_t kMissCullExact = 2048;
+
+struct CBox {
+    float lo[3], hi[3];
+    void add(const CBox& b) {
+        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], b.lo[a]); hi[a] = std::max(hi[a], b.hi[a]); }
+    }
+    double vol() const {
+        return (double(hi[0]) - lo[0]) * (double(hi[1]) - lo[1]) * (double(hi[2]) - lo[2]);
+    }
+    double area() const {
+        const double x = double(hi[0]) - lo[0], y = double(hi[1]) - lo[1], z = double(hi[2]) - lo[2];
+        return x * y + y * z + z * x;
+    }
+};
+
+struct PairCost {
+    double dv, da;
+    size_t j;
+    bool operator<(const PairCost& o) const {
+        if (dv != o.dv) return dv < o.dv;
+        if (da != o.da) return da < o.da;
+        return j < o.j;
+    }
+    bool free() const { return dv <= 0.0 && da <= 0.0; }
+};
+
+PairCost pair_cost(const std::vector<CBox>& bx, size_t i, size_t j) {
+    CBox u = bx[i];
+    u.add(bx[j]);
+    return {u.vol() - bx[i].vol() - bx[j].vol(), u.area() - bx[i].area() - bx[j].area(), j};
+}
+
+void cluster_boxes(std::vector<CBox>& bx, size_t max_boxes) {
+    const size_t n = bx.size();
+    const PairCost none{INFINITY, INFINITY, n};
+    std::vector<char> live(n, 1);
+    std::vector<PairCost> best(n, none);
+    auto rescan = [&](size_t i) {
+        best[i] = none;
+        for (size_t j = 0; j < n; ++j)
+            if (j != i && live[j]) best[i] = std::min(best[i], pair_cost(bx, i, j));
+    };
+    for (size_t i = 0; i < n; ++i) rescan(i);
+    for (size_t alive = n; alive > 1; --alive) {
+        size_t i = n;
+        for (size_t k = 0; k < n; ++k)
+            if (live[k] && (i == n || best[k] < best[i])) i = k;
+        if (alive <= max_boxes && !best[i].free()) break;
+        size_t j = best[i].j;
+        if (j < i) std::swap(i, j);                    // the union stays in the lower slot
+        bx[i].add(bx[j]);
+        live[j] = 0;
+        rescan(i);
+        for (size_t k = 0; k < n; ++k) {
+            if (!live[k] || k == i) continue;
+            if (best[k].j == i || best[k].j == j) rescan(k);
+            else best[k] = std::min(best[k], pair_cost(bx, k, i));
+        }
+    }
+    size_t m = 0;
+    for (size_t k = 0; k < n; ++k)
+        if (live[k]) bx[m++] = bx[k];
+    bx.resize(m);
+}
+
+}  // namespace
+
+int miss_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes) {
+    const size_t nt = hs.kd_verts.size() / 9;
+    if (!nt || max_boxes < 1) return 0;
+    for (float v : hs.kd_verts)
+        if (!std::isfinite(v)) return 0;
+    std::vector<CBox> tb(nt);
+    CBox all{{INFINITY, INFINITY, INFINITY}, {-INFINITY, -INFINITY, -INFINITY}};
+    for (size_t k = 0; k < nt; ++k) {
+        const float* v = &hs.kd_verts[9 * k];
+        CBox b{{v[0], v[1], v[2]}, {v[0], v[1], v[2]}};
+        for (int j = 1; j < 3; ++j) b.add(CBox{{v[3 * j], v[3 * j + 1], v[3 * j + 2]}, {v[3 * j], v[3 * j + 1], v[3 * j + 2]}});
+        tb[k] = b;
+        all.add(b);
+    }
+    std::vector<CBox> bx;
+    if (nt <= kMissCullExact) {
+        bx = tb;
+    } else {
+        // buckets in key order (std::map): planes first, then grid cells
+        for (int with_planes = 1; with_planes >= 0; --with_planes) {
+            std::map<std::pair<int, uint32_t>, CBox> buckets;
+            for (const CBox& b : tb) {
+                std::pair<int, uint32_t> key{3, 0u};
+                for (int a = 0; a < 3 && with_planes; ++a)
+                    if (b.lo[a] == b.hi[a] && key.first == 3) {
+                        const float c = b.lo[a] + 0.0f;            // (-0 and +0: one plane)
+                        uint32_t bits;
+                        std::memcpy(&bits, &c, 4);
+                        key = {a, bits};
+                    }
+                if (key.first == 3) {
+                    for (int a = 0; a < 3; ++a) {
+                        const double ext = double(all.hi[a]) - all.lo[a];
+                        const double c = (double(b.lo[a]) + b.hi[a]) * 0.5 - all.lo[a];
+                        const int cell = ext > 0.0 ? std::min(7, std::max(0, int(c / ext * 8.0))) : 0;
+                        key.second = key.second * 8u + uint32_t(cell);
+                    }
+                }
+                auto it = buckets.find(key);
+                if (it == buckets.end()) buckets.emplace(key, b);
+                else it->second.add(b);
+            }
+            bx.clear();
+            for (const auto& kv : buckets) bx.push_back(kv.second);
+            if (bx.size() <= kMissCullExact) break;
+        }
+    }
+    // the free merges first: they leave every wall as one flat box, which is
+    // what tells a closed room (the test could only cost there)
+    cluster_boxes(bx, bx.size());
+    bool face[3][2] = {};
+    for (const CBox& b : bx) {
+        for (int a = 0; a < 3; ++a) {
+            if (b.lo[a] != b.hi[a]) continue;
+            bool covers = true;
+            for (int c = 0; c < 3; ++c)
+                if (c != a) covers = covers && b.lo[c] <= all.lo[c] && b.hi[c] >= all.hi[c];
+            if (covers && b.lo[a] == all.lo[a]) face[a][0] = true;
+            if (covers && b.lo[a] == all.hi[a]) face[a][1] = true;
+        }
+    }
+    if (face[0][0] && face[0][1] && face[1][0] && face[1][1] && face[2][0] && face[2][1]) return 0;
+    cluster_boxes(bx, static_cast<size_t>(max_boxes));
+    for (const CBox& b : bx) {   // a box over the whole scene: every ray that can hit anything passes
+        bool spans = true;
+        for (int a = 0; a < 3; ++a) spans = spans && b.lo[a] <= all.lo[a] && b.hi[a] >= all.hi[a];
+        if (spans) return 0;
+    }
+    for (size_t k = 0; k < bx.size(); ++k)
+        for (int a = 0; a < 3; ++a) {
+            boxes[k][a] = bx[k].lo[a];
+            boxes[k][3 + a] = bx[k].hi[a];
+        }
+    return static_cast<int>(bx.size());
 }
 
 // ---------------------------------------------------------------------------

@@ -85,6 +85,13 @@ void build_host_scene(const ObjModel& m, HostScene& out, const char* kd_cache_di
 // every non-emitter has Ka == 0 exactly, every Kd and Ks is finite, and there
 // are 1..max_boxes emitter geometries -- else 0.
 int terminal_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes);
+// Miss cull (render_launch.hpp MCPT_MISS_CULL): at most max_boxes fp32 AABBs
+// (min xyz, max xyz; bounds are vertex coordinates, unrounded) such that every
+// KD triangle lies inside at least one of them, clustered bottom-up from one
+// box per triangle by least added volume (host_model.cpp).  0 = no cull for
+// the scene: a non-finite vertex, a box that spans the scene bounds, or a
+// closed room (each face of the scene bounds covered by a flat box).
+int miss_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes);
 // on-disk KD cache (kd_cache.cpp): load returns false unless a valid file exists
 // (files are keyed by the vertices and the build rule)
 bool kd_cache_load(const std::string& dir, const std::vector<float>& tri_verts, std::vector<KdNode>& nodes,

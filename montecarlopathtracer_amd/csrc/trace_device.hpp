@@ -324,10 +324,9 @@ __device__ __forceinline__ float h2f(uint32_t bits16) {
 // rare branch: 14 VALU more per descent step; C4 +4.0% with this one,
 // PERFLOG round 6.)  Equal decisions for every box with lo <= hi; an
 // inverted (empty-node) box is always culled.
-__device__ __forceinline__ bool box_hit(const RayState& r, uint32_t b0, uint32_t b1, uint32_t b2) {
-    const float lx = h2f(b0 & 0xFFFFu), hx = h2f(b1 >> 16);
-    const float ly = h2f(b0 >> 16), hy = h2f(b2 & 0xFFFFu);
-    const float lz = h2f(b1 & 0xFFFFu), hz = h2f(b2 >> 16);
+// (slab_hit: the test on fp32 bounds; box_hit decodes a packed fp16 box for it)
+__device__ __forceinline__ bool slab_hit(const RayState& r, float lx, float ly, float lz, float hx, float hy,
+                                         float hz) {
     const bool nx = __float_as_uint(r.d.x) >> 31, ny = __float_as_uint(r.d.y) >> 31, nz = __float_as_uint(r.d.z) >> 31;
     const float tx0 = ((nx ? hx : lx) - r.o.x) * r.ix, tx1 = ((nx ? lx : hx) - r.o.x) * r.ix;
     const float ty0 = ((ny ? hy : ly) - r.o.y) * r.iy, ty1 = ((ny ? ly : hy) - r.o.y) * r.iy;
@@ -336,6 +335,42 @@ __device__ __forceinline__ bool box_hit(const RayState& r, uint32_t b0, uint32_t
     const float hi = min_qnan(min3_qnan(r.best, tx1, ty1), tz1);
     return !(lo * kEpsLo > hi * kEpsHi);
 }
+__device__ __forceinline__ bool box_hit(const RayState& r, uint32_t b0, uint32_t b1, uint32_t b2) {
+    const float lx = h2f(b0 & 0xFFFFu), hx = h2f(b1 >> 16);
+    const float ly = h2f(b0 >> 16), hy = h2f(b2 & 0xFFFFu);
+    const float lz = h2f(b1 & 0xFFFFu), hz = h2f(b2 >> 16);
+    return slab_hit(r, lx, ly, lz, hx, hy, hz);
+}
+
+#if MCPT_MISS_CULL
+// Miss cull (render_launch.hpp MCPT_MISS_CULL): can ray (o, d) hit anything?
+// slab_hit on the segment (0, best_init] against each of the scene's n
+// occluder boxes, fp32 bounds taken from the vertices unrounded (kernel
+// arguments: scalar operands, n wave-uniform, the loop rolled).  A hit the
+// walk could accept lies on a triangle, hence inside the box that holds the
+// triangle, and the margins cover the rounding -- a ray that
+// fails every box has no hit.  inv: the IEEE reciprocals of d, as begin_ray
+// computes them.
+__device__ __forceinline__ bool may_hit_scene(V3 o, V3 d, V3 inv, float best_init,
+                                              const float (&boxes)[kMaxMissBoxes][6], uint32_t n) {
+    // slab_hit with the slab ends ordered after the products instead of before:
+    // the same operations on the same operands, so the same decisions, but the
+    // bounds stay scalar operands of the subtractions (a select of two scalars
+    // needs both copied to vector registers first: 7 instructions per box less)
+    const bool nx = __float_as_uint(d.x) >> 31, ny = __float_as_uint(d.y) >> 31, nz = __float_as_uint(d.z) >> 31;
+    bool hit = false;
+#pragma unroll 1
+    for (uint32_t i = 0; i < n; i++) {
+        const float ax = (boxes[i][0] - o.x) * inv.x, bx = (boxes[i][3] - o.x) * inv.x;
+        const float ay = (boxes[i][1] - o.y) * inv.y, by = (boxes[i][4] - o.y) * inv.y;
+        const float az = (boxes[i][2] - o.z) * inv.z, bz = (boxes[i][5] - o.z) * inv.z;
+        const float lo = max_qnan(max3_qnan(0.0f, nx ? bx : ax, ny ? by : ay), nz ? bz : az);
+        const float hi = min_qnan(min3_qnan(best_init, nx ? ax : bx, ny ? ay : by), nz ? az : bz);
+        hit |= !(lo * kEpsLo > hi * kEpsHi);
+    }
+    return hit;
+}
+#endif
 
 // Terminal cull (render_launch.hpp MCPT_TERMINAL_CULL): can the closest hit of
 // ray (o, d) lie on an emitter?  box_hit itself, on the segment (0, best_init]

@@ -19,7 +19,9 @@
 //               the next free slot of the segment's queue b+1 (per-bounce
 //               compaction by one LDS atomic per wave); with the material sort
 //               (wf_sort = 1) each block is first sorted by material in LDS, so
-//               a wave runs one material branch
+//               a wave runs one material branch; lean renders: a new ray that
+//               misses every occluder box of the scene is not enqueued, its
+//               path gets the zero its miss would store (may_hit_scene)
 //   cull        lean renders, before the last extend: the terminal query's rays
 //               that can reach no emitter leave the queue (wf_cull_terminal)
 //   candidates  lean CV renders of an LDS scene, once per call: per 8x8 tile, the
@@ -417,6 +419,22 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
                     else scatter<false>(gm, sc.normals, htri, h.y, h.z, h.x, kp.fresnel_kd, sd, color, o, d);
                     cont = true;
                     c.rays++;
+#if MCPT_MISS_CULL
+                    // miss cull (lean renders: n_miss_boxes != 0): the new ray misses every
+                    // occluder box, so its walk would return no hit and the next shade would
+                    // store this zero; the ray stays counted and is not enqueued
+                    // (o and d settled: only they, the throughput, the RNG state and pid are
+                    // live here, but with the test's operations free to move up into scatter
+                    // the queue-order shade took 81 VGPRs, one over its budget; 79 with this)
+                    o = v3(opaque(o.x), opaque(o.y), opaque(o.z));
+                    d = v3(opaque(d.x), opaque(d.y), opaque(d.z));
+                    if (wf.n_miss_boxes &&
+                        !may_hit_scene(o, d, v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), kp.best_init, wf.miss_box,
+                                       wf.n_miss_boxes)) {
+                        stq(&wf.radiance[pid], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+                        cont = false;
+                    }
+#endif
                 }
             }
             if (term) stq(&wf.radiance[pid], make_float4(L.x, L.y, L.z, 0.0f));   // (kNoRay slots: 0)

@@ -302,7 +302,15 @@ class Scene:
         d = {n: int(getattr(i, n)) for n, _ in i._fields_}
         # emitter boxes of the wavefront's terminal cull; 0: the scene does not allow it
         d["terminal_cull_boxes"] = int(lib().mcpt_scene_terminal_cull_boxes(self.handle))
+        # occluder boxes of the wavefront's miss cull; 0: the scene has none
+        d["miss_cull_boxes"] = int(lib().mcpt_scene_miss_cull_boxes(self.handle, None))
         return d
+
+    def miss_cull_boxes(self) -> np.ndarray:
+        """(n, 6) float32 occluder boxes of the miss cull: min xyz, max xyz."""
+        b = np.zeros((16, 6), np.float32)
+        n = int(lib().mcpt_scene_miss_cull_boxes(self.handle, _fptr(b)))
+        return b[:n]
 
     def primary_tile_classes(self):
         """The last render's primary lists: owned 8x8 tiles by candidate count --
