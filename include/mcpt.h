@@ -304,6 +304,25 @@ int mcpt_scene_terminal_cull_boxes(const mcpt_scene* s);
  * scene is a closed room.  boxes (may be NULL): 6 floats per box, min xyz then
  * max xyz.  (Its own entry, as the one above; an addition, the ABI stays 9.) */
 int mcpt_scene_miss_cull_boxes(const mcpt_scene* s, float* boxes);
+/* Direct lists of the wavefront (lean renders of a scene in LDS with occluder
+ * boxes): every triangle is assigned to one occluder box that holds it, and a
+ * box with 1..K triangles is small -- a secondary ray whose segment hits that
+ * box alone is resolved from the box's triangles without a tree walk, same hit.
+ * Returns K (0: built without the lists).  Each pointer may be NULL:
+ * tri_box[n_triangles] = kd id -> box index (as mcpt_scene_miss_cull_boxes
+ * orders them); box_tris[8] = triangles assigned to each box; lists[8 * K] =
+ * per small box its triangles' record indices (3 x the image triangle slot:
+ * the hit ids' and leaf references' unit) in image order, zeros for the other
+ * boxes; list_kd[8 * K] = the same entries as kd ids, -1 where a list has
+ * none.  (Its own entry, as the ones above; an addition, the ABI stays 9.) */
+int mcpt_scene_direct_lists(const mcpt_scene* s, int32_t* tri_box, uint32_t* box_tris, uint32_t* lists,
+                            int32_t* list_kd);
+/* The direct rays of the stats record last read from the scene (mcpt_render's,
+ * mcpt_render_stats_read's): secondary rays the shades marked for their box's
+ * list, summed over devices.  0 wherever the lists are off: counting renders,
+ * the megakernel, a scene in global memory or without boxes.  They are counted
+ * in mcpt_render_stats::rays like every other ray. */
+uint64_t mcpt_scene_direct_rays(const mcpt_scene* s);
 /* Primary lists of the scene's last render (wavefront, lean CV renders of a
  * scene in LDS with 8x8 tiles): out[0..2] = the owned tiles whose candidate
  * list is empty (no primary ray made), holds 1..K triangles (tested straight

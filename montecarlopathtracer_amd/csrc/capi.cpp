@@ -176,6 +176,13 @@ struct mcpt_scene {
     // miss cull: occluder boxes {lo xyz, hi xyz}; n_miss_boxes == 0: none for the scene (host_model.hpp)
     uint32_t n_miss_boxes = 0;
     float miss_box[mcpt::kMaxMissBoxes][6] = {};
+    // direct lists: kd id -> its box; triangles per box; the small boxes' counts
+    // (4 bits each) and lists as the kernels take them (render_launch.hpp WfParams)
+    std::vector<int32_t> tri_box;
+    uint32_t box_tris[mcpt::kMaxMissBoxes] = {};
+    uint32_t direct_counts = 0;
+    uint32_t direct_list[mcpt::kMaxMissBoxes * 16] = {};
+    uint64_t direct_rays = 0;           // of the stats record last read
     void* d_image = nullptr;
     void* d_normals = nullptr;
     Workspace ws;
@@ -480,6 +487,26 @@ void build_image(mcpt_scene& s, bool force_global) {
         std::memcpy(s.cull_box[b], hb, 12);
     }
     s.n_miss_boxes = static_cast<uint32_t>(mcpt::miss_cull_boxes(hs, s.miss_box, mcpt::kMaxMissBoxes));
+    // direct lists: every triangle to one box that holds it; a box with 1..kDirectK
+    // triangles is small and gets their record indices (the leaf refs' unit) in
+    // image order.  (Kept for every scene with boxes; direct_lists_fit and the
+    // render's kind decide whether a render uses them.)
+    mcpt::direct_list_assign(hs, s.miss_box, static_cast<int>(s.n_miss_boxes), s.tri_box);
+    s.direct_counts = 0;
+    std::memset(s.direct_list, 0, sizeof s.direct_list);
+    std::memset(s.box_tris, 0, sizeof s.box_tris);
+#if MCPT_DIRECT_LISTS
+    for (uint32_t slot = 0; slot < nt && s.n_miss_boxes; ++slot) {
+        const int32_t b = s.tri_box[s.tri_order[slot]];
+        if (b < 0) throw mcpt::Error{MCPT_E_INVALID, "a triangle outside every occluder box"};
+        if (s.box_tris[b] < mcpt::kDirectK) s.direct_list[size_t(b) * mcpt::kDirectK + s.box_tris[b]] = 3u * slot;
+        s.box_tris[b]++;
+    }
+    for (uint32_t b = 0; b < s.n_miss_boxes; ++b) {
+        if (s.box_tris[b] >= 1 && s.box_tris[b] <= mcpt::kDirectK) s.direct_counts |= s.box_tris[b] << (4u * b);
+        else std::memset(&s.direct_list[size_t(b) * mcpt::kDirectK], 0, 4 * mcpt::kDirectK);
+    }
+#endif
     s.cull_gain = 0.0f;
     for (const mcpt::Geometry& ge : hs.geoms)
         for (float k : {ge.Kd.x, ge.Kd.y, ge.Kd.z, ge.Ks.x, ge.Ks.y, ge.Ks.z})
@@ -865,6 +892,13 @@ void prepare_wavefront(mcpt_scene& s, const Plan& pl, int sets, mcpt::WfParams* 
         w.n_miss_boxes = pl.kp.lean ? s.n_miss_boxes : 0u;
         std::memcpy(w.miss_box, s.miss_box, sizeof w.miss_box);
 #endif
+#if MCPT_DIRECT_LISTS
+        // (where the miss cull runs in front of the lean LDS extend and the table
+        // fits behind the image; launch_wavefront checks the same)
+        const bool direct = w.n_miss_boxes && mcpt::direct_lists_fit(s.gpu.image_bytes, s.gpu.node_boxes);
+        w.direct_counts = direct ? s.direct_counts : 0u;
+        std::memcpy(w.direct_list, s.direct_list, sizeof w.direct_list);
+#endif
     }
 }
 
@@ -972,6 +1006,7 @@ void read_stats(mcpt_scene& s, mcpt_render_stats* out) {
         s.free_timing.push_back(t);
     }
     s.pending.clear();
+    s.direct_rays = 0;
     if (s.ws.small) {
         unsigned long long st[16];
         HIP_TRY(hipMemcpy(st, static_cast<char*>(s.ws.small) + 64, sizeof st, hipMemcpyDeviceToHost));
@@ -992,6 +1027,7 @@ void read_stats(mcpt_scene& s, mcpt_render_stats* out) {
 #endif
         r.rays = st[0]; r.paths = st[1]; r.inner_visits = st[2]; r.leaf_visits = st[3];
         r.leaf_refs = st[4]; r.tri_tests = st[5]; r.shades = st[6]; r.stack_spills = st[7];
+        s.direct_rays = st[mcpt::kStatDirect];
     }
     r.renders = s.renders;
     r.devices = 1;
@@ -1123,6 +1159,7 @@ void read_stats_all(mcpt_scene& s, mcpt_render_stats* out) {
         r.rays += q.rays; r.paths += q.paths; r.inner_visits += q.inner_visits; r.leaf_visits += q.leaf_visits;
         r.leaf_refs += q.leaf_refs; r.tri_tests += q.tri_tests; r.shades += q.shades;
         r.stack_spills += q.stack_spills;
+        s.direct_rays += R->direct_rays;
         r.kernel_ms = std::max(r.kernel_ms, q.kernel_ms);
         r.reduce_ms = std::max(r.reduce_ms, q.reduce_ms);
     }
@@ -1692,6 +1729,8 @@ static int scene_create_impl(const mcpt_model* m, mcpt_scene** out, bool device,
                 R->cull_gain = s->cull_gain;
                 R->n_miss_boxes = s->n_miss_boxes;
                 std::memcpy(R->miss_box, s->miss_box, sizeof s->miss_box);
+                R->direct_counts = s->direct_counts;
+                std::memcpy(R->direct_list, s->direct_list, sizeof s->direct_list);
                 upload(*R, devs[i], s->image, nrm);
                 HIP_TRY(hipStreamCreateWithFlags(&R->stream, hipStreamNonBlocking));
                 HIP_TRY(hipEventCreateWithFlags(&R->done, hipEventDisableTiming));
@@ -1757,6 +1796,24 @@ int mcpt_scene_miss_cull_boxes(const mcpt_scene* s, float* boxes) {
     if (boxes) std::memcpy(boxes, s->miss_box, sizeof(float) * 6 * s->n_miss_boxes);
     return static_cast<int>(s->n_miss_boxes);
 }
+
+int mcpt_scene_direct_lists(const mcpt_scene* s, int32_t* tri_box, uint32_t* box_tris, uint32_t* lists,
+                            int32_t* list_kd) {
+    if (!s || !MCPT_DIRECT_LISTS) return 0;
+    if (list_kd)
+        for (uint32_t b = 0; b < mcpt::kMaxMissBoxes; ++b)
+            for (uint32_t j = 0; j < mcpt::kDirectK; ++j) {
+                const bool have = j < ((s->direct_counts >> (4u * b)) & 15u);
+                list_kd[b * mcpt::kDirectK + j] =
+                    have ? static_cast<int32_t>(s->tri_order[s->direct_list[b * mcpt::kDirectK + j] / 3u]) : -1;
+            }
+    if (tri_box && !s->tri_box.empty()) std::memcpy(tri_box, s->tri_box.data(), 4 * s->tri_box.size());
+    if (box_tris) std::memcpy(box_tris, s->box_tris, 4 * mcpt::kMaxMissBoxes);
+    if (lists) std::memcpy(lists, s->direct_list, 4 * mcpt::kDirectTableWords);
+    return static_cast<int>(mcpt::kDirectK);
+}
+
+uint64_t mcpt_scene_direct_rays(const mcpt_scene* s) { return s ? s->direct_rays : 0; }
 
 int mcpt_scene_copy_kd(const mcpt_scene* s, uint32_t* nodes, uint32_t* leaf_ids, int32_t* kd_tris, float* geoms) {
     if (!s) return fail(MCPT_E_INVALID, "NULL scene");

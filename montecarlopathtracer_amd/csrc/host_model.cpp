@@ -660,6 +660,20 @@ int miss_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes) {
     return static_cast<int>(bx.size());
 }
 
+void direct_list_assign(const HostScene& hs, const float (*boxes)[6], int n_boxes, std::vector<int32_t>& tri_box) {
+    const size_t nt = hs.kd_verts.size() / 9;
+    tri_box.assign(nt, -1);
+    for (size_t k = 0; k < nt; ++k) {
+        const float* v = &hs.kd_verts[9 * k];
+        for (int b = 0; b < n_boxes && tri_box[k] < 0; ++b) {
+            bool in = true;
+            for (int j = 0; j < 3; ++j)
+                for (int a = 0; a < 3; ++a) in = in && v[3 * j + a] >= boxes[b][a] && v[3 * j + a] <= boxes[b][3 + a];
+            if (in) tri_box[k] = b;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------
 // KD build (KDTree.hpp:58-287). Literal std::min/std::max forms keep the
 // signed-zero/NaN behaviour of the reference; float expressions keep its

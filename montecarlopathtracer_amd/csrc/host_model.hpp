@@ -92,6 +92,12 @@ int terminal_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes);
 // the scene: a non-finite vertex, a box that spans the scene bounds, or a
 // closed room (each face of the scene bounds covered by a flat box).
 int miss_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes);
+// Direct lists (render_launch.hpp MCPT_DIRECT_LISTS): kd id -> the first of
+// miss_cull_boxes' boxes that holds the triangle's three vertices.  One always
+// does (the boxes are unions of triangle boxes); -1 only for no boxes.  Which
+// of several holding boxes a triangle goes to does not matter: a hit on it lies
+// in every one of them, so the ray hits them all.
+void direct_list_assign(const HostScene& hs, const float (*boxes)[6], int n_boxes, std::vector<int32_t>& tri_box);
 // on-disk KD cache (kd_cache.cpp): load returns false unless a valid file exists
 // (files are keyed by the vertices and the build rule)
 bool kd_cache_load(const std::string& dir, const std::vector<float>& tri_verts, std::vector<KdNode>& nodes,

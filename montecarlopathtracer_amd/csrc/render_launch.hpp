@@ -93,6 +93,42 @@ constexpr uint32_t kListMaxTris = 4096;
 // 86.5 / 88% of the escaping rays (five walls, the light and two boxes over
 // the spheres and the block make 8)
 constexpr int kMaxMissBoxes = 8;
+// Direct lists (wavefront, lean renders of a scene in LDS with occluder boxes):
+// the shade's box test also tells which boxes the new ray's segment hits.  A
+// hit the walk could accept lies inside the box its triangle was assigned to
+// (host_model.cpp direct_list_assign: every triangle goes to one box that holds
+// it), so a ray that hits exactly one box can only hit that box's triangles,
+// and the closest hit is the minimum of (t, rank) over the triangles tested:
+// when that box is small (1..kDirectK triangles; scene01's five walls hold two
+// each) the extend tests the box's list with its own leaf branch instead of
+// walking the tree -- same hit id, bit for bit.  The shade stores the selector
+// with the ray, in the top four bits of the {d, depth} word: 0 = walk, 1 + box
+// index = that box's list (kNoRay, all ones, stays unique).
+// 0: the pipeline without it, the same kernels as before it (A/B builds).
+#ifndef MCPT_DIRECT_LISTS
+#define MCPT_DIRECT_LISTS MCPT_MISS_CULL
+#endif
+#if MCPT_DIRECT_LISTS && !MCPT_MISS_CULL
+#error "MCPT_DIRECT_LISTS needs MCPT_MISS_CULL (its box test)"
+#endif
+// triangles a box may hold and keep its list: the smallest K that loses nothing.
+// Priced on the CPU oracle (scripts/price_direct_lists.py,
+// profiles/direct_lists/pricing.txt): K = 2, 4 and 8 list the same boxes on
+// scene01, scene02 and the 70k mesh -- flat two-triangle walls; the next larger
+// boxes hold 12 triangles (the lights) -- so the same rays are direct
+#ifndef MCPT_DIRECT_K
+#define MCPT_DIRECT_K 2
+#endif
+constexpr uint32_t kDirectK = MCPT_DIRECT_K;
+static_assert(kDirectK >= 1 && kDirectK <= 15, "a box's count is carried in 4 bits");
+constexpr uint32_t kDirectShift = 28, kDepthMask = (1u << kDirectShift) - 1u;
+// the extend's LDS copy of the table: kMaxMissBoxes x kDirectK record indices
+// and one 16-B unit more (the leaf branch reads its refs in pairs)
+constexpr uint32_t kDirectTableWords = kMaxMissBoxes * kDirectK;
+constexpr size_t kDirectLdsBytes = (size_t(kDirectTableWords) * 4 + 16 + 15) & ~size_t(15);
+// the render's direct rays, counted by the shades: a slot of KernelParams::stats
+// behind the eight counters (and the diagnostic builds' five)
+constexpr int kStatDirect = 13;
 
 struct GpuGeom {
     float Ka[3], Kd[3], Ks[3];
@@ -257,6 +293,15 @@ struct WfParams {
     uint32_t n_miss_boxes;
     float miss_box[kMaxMissBoxes][6];
 #endif
+    // direct lists: per occluder box, 4 bits of direct_counts -- the triangles of
+    // its list, 0 = the box's rays walk -- and kDirectK words of direct_list, their
+    // record indices (the unit of the image's leaf refs) in image order.
+    // direct_counts == 0: no ray carries a selector (the feature is off for the
+    // render).  Behind everything else in the kernel arguments
+#if MCPT_DIRECT_LISTS
+    uint32_t direct_counts;
+    uint32_t direct_list[kDirectTableWords];
+#endif
 };
 
 // LDS need of the in-LDS variant for a scene image of `image_bytes`: the
@@ -269,6 +314,14 @@ constexpr size_t kLdsCounterBytes = 32;
 inline size_t lds_bytes_counted_in_lds(uint32_t image_bytes, int S) {
     return lds_bytes_in_lds(image_bytes, S) + kLdsCounterBytes;
 }
+#if MCPT_DIRECT_LISTS
+// direct lists: the lean LDS extend keeps its table behind the counter block.
+// The table never decides where a scene lives: if it does not fit beside the
+// image the scene stays in LDS and its renders carry no selectors
+inline bool direct_lists_fit(uint32_t image_bytes, uint32_t node_boxes) {
+    return !node_boxes && lds_bytes_counted_in_lds(image_bytes, 4) + kDirectLdsBytes <= kMaxLds;
+}
+#endif
 constexpr size_t lds_bytes_global(int S, bool counted) {
     return (size_t)S * kGlobalBlock * 16 + (counted ? kLdsCounterBytes : 0);
 }

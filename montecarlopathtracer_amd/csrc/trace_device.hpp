@@ -370,6 +370,28 @@ __device__ __forceinline__ bool may_hit_scene(V3 o, V3 d, V3 inv, float best_ini
     }
     return hit;
 }
+#if MCPT_DIRECT_LISTS
+// Direct lists (render_launch.hpp MCPT_DIRECT_LISTS): may_hit_scene's tests, and
+// which boxes passed, in one accumulator -- box i adds 256 + i, so the result is
+// 0 when the ray fails every box (may_hit_scene's false), its high part is the
+// number of boxes hit and, when that is 1, its low byte is the box
+// (kMaxMissBoxes x 7 < 256: the index sum never carries into the count)
+__device__ __forceinline__ uint32_t scene_box_hits(V3 o, V3 d, V3 inv, float best_init,
+                                                   const float (&boxes)[kMaxMissBoxes][6], uint32_t n) {
+    const bool nx = __float_as_uint(d.x) >> 31, ny = __float_as_uint(d.y) >> 31, nz = __float_as_uint(d.z) >> 31;
+    uint32_t acc = 0;
+#pragma unroll 1
+    for (uint32_t i = 0; i < n; i++) {
+        const float ax = (boxes[i][0] - o.x) * inv.x, bx = (boxes[i][3] - o.x) * inv.x;
+        const float ay = (boxes[i][1] - o.y) * inv.y, by = (boxes[i][4] - o.y) * inv.y;
+        const float az = (boxes[i][2] - o.z) * inv.z, bz = (boxes[i][5] - o.z) * inv.z;
+        const float lo = max_qnan(max3_qnan(0.0f, nx ? bx : ax, ny ? by : ay), nz ? bz : az);
+        const float hi = min_qnan(min3_qnan(best_init, nx ? ax : bx, ny ? ay : by), nz ? az : bz);
+        acc += !(lo * kEpsLo > hi * kEpsHi) ? 256u + i : 0u;
+    }
+    return acc;
+}
+#endif
 #endif
 
 // Terminal cull (render_launch.hpp MCPT_TERMINAL_CULL): can the closest hit of

@@ -123,6 +123,21 @@ wf_extend(const KernelParams kp, const WfParams wf) {
     uint32_t* const lslot = reinterpret_cast<uint32_t*>(lds_image + (IN_LDS ? sc.image_bytes : 0u));
     if (tid == 0) *lslot = 0;
     const SceneView sv = open_scene<IN_LDS, BLOCK>(lds_image, sc, tid);
+#if MCPT_DIRECT_LISTS
+    // direct lists (lean renders, scene in LDS): the boxes' triangle lists behind
+    // the counter block, read by the leaf branch as leaf refs -- dtab is the
+    // table's word offset from sv.leafs; its last 16 B are zeros (the branch reads
+    // the ref after a list's last one: record 0, in bounds, unused)
+    constexpr bool DIRECT = LAY == kLayLds && !COUNT;
+    uint32_t dtab = 0, dcnt = 0;
+    if constexpr (DIRECT) {
+        // (asm results, as the refill threshold below: not kernel-argument reads in the loop)
+        asm volatile("s_mov_b32 %0, %1" : "=s"(dcnt) : "s"(wf.direct_counts));
+        asm volatile("s_mov_b32 %0, %1" : "=s"(dtab) : "s"((sc.image_bytes + (uint32_t)kLdsCounterBytes - sc.off_leafs) / 4u));
+        if (dcnt && tid < (int)(kDirectLdsBytes / 4))
+            (lslot + kLdsCounterBytes / 4)[tid] = tid < (int)kDirectTableWords ? wf.direct_list[tid] : 0u;
+    }
+#endif
     __syncthreads();
     uint4* st = reinterpret_cast<uint4*>(smem) + tid;
     uint4* spill = kp.spill + (blockIdx.x * BLOCK + (uint32_t)tid);
@@ -156,6 +171,17 @@ wf_extend(const KernelParams kp, const WfParams wf) {
         // (no branch: an empty slot's walk is set up and dropped; begin_ray
         // leaves htri = -1, its miss)
         const bool live = begin_ray(r, sc, kp.best_init);
+#if MCPT_DIRECT_LISTS
+        // a direct ray: the leaf branch runs over its box's list, and the pop on
+        // the empty stack ends it (no descent; sel is 14 for kNoRay)
+        if constexpr (DIRECT) {
+            const uint32_t sel = (depth >> kDirectShift) - 1u;
+            const bool dr = sel < (uint32_t)kMaxMissBoxes;
+            const uint32_t lp = dtab + sel * kDirectK;
+            r.lpos = dr ? lp : 0u;
+            r.lend = dr ? lp + ((dcnt >> (4u * sel)) & 15u) : 0u;
+        }
+#endif
         mode = (depth != kNoRay && live) ? kTrav : kReady;
     };
 #ifdef MCPT_PHASE_TIMING
@@ -324,6 +350,9 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
     const bool imp = wf.bounce == 0 && implicit0(kp, wf);
     const int lane = (int)(threadIdx.x & 63u);
     Counters c = {0, 0, 0, 0, 0, 0, 0, 0};
+#if MCPT_DIRECT_LISTS
+    uint32_t ndirect = 0;                                       // this wave's direct rays
+#endif
     uint32_t par = 0;
     for (uint32_t base = 0; base < total; base += BLOCK) {      // block-uniform trip count
         uint32_t i = base + threadIdx.x;
@@ -360,6 +389,9 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
             par ^= 1u;
         }
         bool cont = false;
+#if MCPT_DIRECT_LISTS
+        bool direct = false;                                    // the new ray goes by a box's list
+#endif
         uint32_t pid = 0, depth = kNoRay, sd = 0;
         V3 o = v3(0, 0, 0), d = v3(0, 0, 0), color = v3(0, 0, 0);
         if (i < total) {
@@ -389,7 +421,7 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
                 ps = ldq(&qb[qf(js, kQPS, qs)]);
             }
             pid = __float_as_uint(o4.w);
-            depth = __float_as_uint(d4.w);
+            depth = ray_depth(__float_as_uint(d4.w));
             color = xyz(ps);
             sd = __float_as_uint(ps.w);
             // CV: miss -> 0; emitter -> color*Ka*ILLUM (:111-113); terminal query
@@ -428,6 +460,22 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
                     // the queue-order shade took 81 VGPRs, one over its budget; 79 with this)
                     o = v3(opaque(o.x), opaque(o.y), opaque(o.z));
                     d = v3(opaque(d.x), opaque(d.y), opaque(d.z));
+#if MCPT_DIRECT_LISTS
+                    // direct lists: the same tests also say which boxes the ray hits; one
+                    // box, and a small one (direct_counts: 4 bits per box, 0 = walk), and the
+                    // ray carries 1 + its index in the top bits of its depth word
+                    if (wf.n_miss_boxes) {
+                        const uint32_t acc = scene_box_hits(o, d, v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), kp.best_init,
+                                                            wf.miss_box, wf.n_miss_boxes);
+                        if (!acc) {
+                            stq(&wf.radiance[pid], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+                            cont = false;
+                        }
+                        const uint32_t box = acc & 255u;
+                        direct = (acc >> 8) == 1u && ((wf.direct_counts >> (4u * box)) & 15u) != 0u;
+                        if (direct) depth |= (box + 1u) << kDirectShift;
+                    }
+#else
                     if (wf.n_miss_boxes &&
                         !may_hit_scene(o, d, v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), kp.best_init, wf.miss_box,
                                        wf.n_miss_boxes)) {
@@ -435,10 +483,14 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
                         cont = false;
                     }
 #endif
+#endif
                 }
             }
             if (term) stq(&wf.radiance[pid], make_float4(L.x, L.y, L.z, 0.0f));   // (kNoRay slots: 0)
         }
+#if MCPT_DIRECT_LISTS
+        ndirect += (uint32_t)__popcll(__ballot(direct));        // (wave-uniform: a scalar register)
+#endif
         // next ray: the wave's continuing lanes take consecutive slots of queue b+1
         const uint64_t m = __ballot(cont);
         if (m) {
@@ -455,6 +507,9 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
         }
     }
     flush_counters(c, kp.stats);
+#if MCPT_DIRECT_LISTS
+    if (lane == 0 && ndirect) atomicAdd(kp.stats + kStatDirect, (unsigned long long)ndirect);
+#endif
     __syncthreads();
     if (threadIdx.x == 0) nx->queued = lnext;
 }
@@ -735,9 +790,19 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
             wf.v0 = v0;
             wf.nb = (kp.npix_local - v0) < nb_max ? (kp.npix_local - v0) : nb_max;
             const uint32_t n = wf.nb * wf.ns;
+#if MCPT_DIRECT_LISTS
+            // direct lists: where the miss cull runs in front of the lean LDS extend,
+            // and the table fits behind the image; else no ray carries a selector
+            const bool direct = in_lds && kp.lean && wf.n_miss_boxes && wf.direct_counts &&
+                                direct_lists_fit(img, kp.scene.node_boxes);
+            if (!direct) wf.direct_counts = 0;
+            const size_t direct_lds = direct ? kDirectLdsBytes : 0;
+#else
+            const size_t direct_lds = 0;
+#endif
             // the shade's material table in LDS if it fits beside the extend's
             // workgroups on a CU (MCPT_WF_GEO_LDS)
-            const size_t ext_lds = in_lds ? wf_lds_extend_bytes(kp.scene)
+            const size_t ext_lds = in_lds ? wf_lds_extend_bytes(kp.scene) + direct_lds
                                           : kWfGlobalSegsPerCu * lds_bytes_global(MCPT_WF_GLOBAL_S, true);
             const size_t geo_bytes = (MCPT_WF_GEO_LDS && ext_lds + 64 * (size_t)kp.scene.n_geoms + 64 <= kLdsPerCu)
                                          ? 64 * (size_t)kp.scene.n_geoms : 0;
@@ -775,7 +840,7 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
                 if (packet && b == 0) {
                     e = launch_wavefront_primary(kb, wf, (int)nseg, llds, bs);
                 } else if (in_lds) {
-                    e = launch_extend<kLayLds, 4, kLdsBlock>(kb, wf, (int)nseg, llds, bs);
+                    e = launch_extend<kLayLds, 4, kLdsBlock>(kb, wf, (int)nseg, llds + direct_lds, bs);
                 } else
                     e = launch_extend<kLayGlobal, MCPT_WF_GLOBAL_S, kGlobalBlock>(
                         kb, wf, (int)nseg, lds_bytes_global(MCPT_WF_GLOBAL_S, true), bs);

@@ -35,6 +35,15 @@ namespace {
 // queue slot without a ray (pixel outside the image): it ends as a miss with
 // zero radiance and is counted nowhere, like the megakernel's empty units.
 constexpr uint32_t kNoRay = 0xFFFFFFFFu;
+// Direct lists (render_launch.hpp MCPT_DIRECT_LISTS): the word's top four bits
+// carry the ray's selector (0 walk, 1 + box its list); the depth is the rest
+__device__ __forceinline__ uint32_t ray_depth(uint32_t w) {
+#if MCPT_DIRECT_LISTS
+    return w == kNoRay ? w : (w & kDepthMask);
+#else
+    return w;
+#endif
+}
 
 __device__ __forceinline__ float4 pack(V3 v, uint32_t w) { return make_float4(v.x, v.y, v.z, __uint_as_float(w)); }
 

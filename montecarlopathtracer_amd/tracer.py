@@ -304,6 +304,11 @@ class Scene:
         d["terminal_cull_boxes"] = int(lib().mcpt_scene_terminal_cull_boxes(self.handle))
         # occluder boxes of the wavefront's miss cull; 0: the scene has none
         d["miss_cull_boxes"] = int(lib().mcpt_scene_miss_cull_boxes(self.handle, None))
+        # the wavefront's direct lists: triangles a small box may hold (0: built without), and the small boxes
+        bt = np.zeros(8, np.uint32)
+        k = int(lib().mcpt_scene_direct_lists(self.handle, None, bt.ctypes.data_as(C.POINTER(C.c_uint32)), None, None))
+        d["direct_list_k"] = k
+        d["direct_list_boxes"] = int(((bt >= 1) & (bt <= k)).sum()) if k else 0
         return d
 
     def miss_cull_boxes(self) -> np.ndarray:
@@ -311,6 +316,34 @@ class Scene:
         b = np.zeros((16, 6), np.float32)
         n = int(lib().mcpt_scene_miss_cull_boxes(self.handle, _fptr(b)))
         return b[:n]
+
+    def direct_lists(self) -> dict:
+        """The wavefront's direct lists: {"k", "tri_box" (kd id -> occluder box), "box_tris"
+        (triangles per box), "lists" ((boxes, k) record indices of the small boxes' triangles,
+        image order), "list_kd" (the same as kd ids, -1 past a list's end), "counts" (per box:
+        the length of its list, 0 = its rays walk)}; k is 0 for a library built without them."""
+        n = int(lib().mcpt_scene_miss_cull_boxes(self.handle, None))
+        nt = self.info()["n_triangles"]
+        tri_box = np.full(max(nt, 1), -1, np.int32)
+        box_tris = np.zeros(8, np.uint32)
+        lists = np.zeros(8 * 16, np.uint32)
+        list_kd = np.full(8 * 16, -1, np.int32)
+        k = int(lib().mcpt_scene_direct_lists(self.handle, tri_box.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              box_tris.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              lists.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              list_kd.ctypes.data_as(C.POINTER(C.c_int32))))
+        box_tris = box_tris[:n] if k else box_tris[:0]
+        counts = np.where(box_tris <= k, box_tris, 0).astype(np.uint32)
+        return {"k": k, "tri_box": tri_box[:nt] if k else tri_box[:0], "box_tris": box_tris,
+                "lists": lists[: 8 * k].reshape(8, k)[: len(box_tris)] if k else lists[:0].reshape(0, 0),
+                "list_kd": list_kd[: 8 * k].reshape(8, k)[: len(box_tris)] if k else list_kd[:0].reshape(0, 0),
+                "counts": counts}
+
+    def _render_stats(self, st) -> dict:
+        d = st.as_dict()
+        # secondary rays resolved from a box's list instead of a walk (lean wavefront renders)
+        d["direct_rays"] = int(lib().mcpt_scene_direct_rays(self.handle))
+        return d
 
     def primary_tile_classes(self):
         """The last render's primary lists: owned 8x8 tiles by candidate count --
@@ -342,7 +375,7 @@ class Scene:
             raise McptError(-1, "fb must be a C-contiguous float32 array with 3 floats per output pixel")
         st = RenderStats()
         check(lib().mcpt_render(self.handle, C.byref(params.to_c()), _fptr(fb), C.byref(st)))
-        return fb, st.as_dict()
+        return fb, self._render_stats(st)
 
     def intersect(self, o: np.ndarray, d: np.ndarray, t_max: float = 3.402823466e38):
         """Closest hits of rays (origins o, directions d: (n, 3) float32) on the
@@ -467,7 +500,7 @@ class Scene:
             raise McptError(-1, "var must be a C-contiguous float32 array with 4 floats per pixel")
         st = RenderStats()
         check(lib().mcpt_render_var(self.handle, C.byref(params.to_c()), _fptr(fb), _fptr(var), C.byref(st)))
-        return fb, var, st.as_dict()
+        return fb, var, self._render_stats(st)
 
     def render_var_device(self, params: RenderParams, d_fb_rgba_ptr: int, d_var_rgba_ptr: int, stream_ptr: int = 0):
         """Asynchronous render and variance into two device RGBA float buffers (mcpt_render_var_device)."""
@@ -495,7 +528,7 @@ class Scene:
         check(lib().mcpt_render_adaptive(self.handle, C.byref(params.to_c()),
                                          C.byref(adaptive) if adaptive is not None else None, _fptr(fb), _fptr(var),
                                          count.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st)))
-        return fb, var, count, st.as_dict()
+        return fb, var, count, self._render_stats(st)
 
     def render_adaptive_device(self, params: RenderParams, adaptive, d_fb_rgba_ptr: int, d_var_rgba_ptr: int,
                                d_count_ptr: int, stream_ptr: int = 0):
@@ -519,7 +552,7 @@ class Scene:
     def stats(self) -> dict:
         st = RenderStats()
         check(lib().mcpt_render_stats_read(self.handle, C.byref(st)))
-        return st.as_dict()
+        return self._render_stats(st)
 
 
 def denoise_params(width: int, height: int, iterations: int = 0, normal_power_log2: int = 0, sigma_z: float = 0.0,
