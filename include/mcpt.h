@@ -323,6 +323,12 @@ int mcpt_scene_direct_lists(const mcpt_scene* s, int32_t* tri_box, uint32_t* box
  * the megakernel, a scene in global memory or without boxes.  They are counted
  * in mcpt_render_stats::rays like every other ray. */
 uint64_t mcpt_scene_direct_rays(const mcpt_scene* s);
+/* The rays the wavefront's secondary extends (bounce >= 1) took, of the same
+ * stats record, summed over devices: every secondary ray but the direct ones
+ * (the shade that makes them resolves them) and those the miss cull and the
+ * terminal cull answer.  0 for the megakernel and in a build without the direct
+ * resolve.  (An addition, as the one above; the ABI stays 9.) */
+uint64_t mcpt_scene_extend_rays(const mcpt_scene* s);
 /* Primary lists of the scene's last render (wavefront, lean CV renders of a
  * scene in LDS with 8x8 tiles): out[0..2] = the owned tiles whose candidate
  * list is empty (no primary ray made), holds 1..K triangles (tested straight

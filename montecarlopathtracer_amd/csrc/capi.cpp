@@ -183,6 +183,7 @@ struct mcpt_scene {
     uint32_t direct_counts = 0;
     uint32_t direct_list[mcpt::kMaxMissBoxes * 16] = {};
     uint64_t direct_rays = 0;           // of the stats record last read
+    uint64_t extend_rays = 0;           // likewise: the rays the secondary extends took
     void* d_image = nullptr;
     void* d_normals = nullptr;
     Workspace ws;
@@ -1007,6 +1008,7 @@ void read_stats(mcpt_scene& s, mcpt_render_stats* out) {
     }
     s.pending.clear();
     s.direct_rays = 0;
+    s.extend_rays = 0;
     if (s.ws.small) {
         unsigned long long st[16];
         HIP_TRY(hipMemcpy(st, static_cast<char*>(s.ws.small) + 64, sizeof st, hipMemcpyDeviceToHost));
@@ -1028,6 +1030,7 @@ void read_stats(mcpt_scene& s, mcpt_render_stats* out) {
         r.rays = st[0]; r.paths = st[1]; r.inner_visits = st[2]; r.leaf_visits = st[3];
         r.leaf_refs = st[4]; r.tri_tests = st[5]; r.shades = st[6]; r.stack_spills = st[7];
         s.direct_rays = st[mcpt::kStatDirect];
+        s.extend_rays = st[mcpt::kStatExtend];
     }
     r.renders = s.renders;
     r.devices = 1;
@@ -1160,6 +1163,7 @@ void read_stats_all(mcpt_scene& s, mcpt_render_stats* out) {
         r.leaf_refs += q.leaf_refs; r.tri_tests += q.tri_tests; r.shades += q.shades;
         r.stack_spills += q.stack_spills;
         s.direct_rays += R->direct_rays;
+        s.extend_rays += R->extend_rays;
         r.kernel_ms = std::max(r.kernel_ms, q.kernel_ms);
         r.reduce_ms = std::max(r.reduce_ms, q.reduce_ms);
     }
@@ -1814,6 +1818,7 @@ int mcpt_scene_direct_lists(const mcpt_scene* s, int32_t* tri_box, uint32_t* box
 }
 
 uint64_t mcpt_scene_direct_rays(const mcpt_scene* s) { return s ? s->direct_rays : 0; }
+uint64_t mcpt_scene_extend_rays(const mcpt_scene* s) { return s ? s->extend_rays : 0; }
 
 int mcpt_scene_copy_kd(const mcpt_scene* s, uint32_t* nodes, uint32_t* leaf_ids, int32_t* kd_tris, float* geoms) {
     if (!s) return fail(MCPT_E_INVALID, "NULL scene");

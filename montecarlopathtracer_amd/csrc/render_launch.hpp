@@ -129,6 +129,32 @@ constexpr size_t kDirectLdsBytes = (size_t(kDirectTableWords) * 4 + 16 + 15) & ~
 // the render's direct rays, counted by the shades: a slot of KernelParams::stats
 // behind the eight counters (and the diagnostic builds' five)
 constexpr int kStatDirect = 13;
+// Direct resolve (where the direct lists are active): the shade that makes a
+// direct ray also finds its hit -- begin_ray's root clip and test_tri_pair over
+// the box's list, the extend's own operations -- and writes ray and hit id to
+// the far end of the segment's next queue: a queue's head [0, queued) holds the
+// rays its extend walks, its tail [seg - resolved, seg) the resolved ones, and
+// the next shade takes both.  A resolved ray without a hit ends as the miss
+// cull's rays do, and one made for the terminal query gets the radiance the
+// last shade would store (its hit's emission), so the last queue has no tail
+// and the terminal cull keeps its code.  No selector reaches an extend, whose
+// direct code (LDS table, selector lines) compiles out.
+// 0: the pipeline without it, the same kernels as before it (A/B builds).
+#ifndef MCPT_DIRECT_RESOLVE
+#define MCPT_DIRECT_RESOLVE MCPT_DIRECT_LISTS
+#endif
+#if MCPT_DIRECT_RESOLVE && !MCPT_DIRECT_LISTS
+#error "MCPT_DIRECT_RESOLVE needs MCPT_DIRECT_LISTS (its boxes and lists)"
+#endif
+// The shade reads the lists' records (at most 16 x 48 B) and their indices from
+// a copy in its own LDS, kDirectShadeLds bytes counted beside the co-resident
+// extend: the reads are a dependent round trip behind the box test (from the
+// L2-resident global image the C2 frame gained 1.2% instead of 5.0%, row 179)
+constexpr size_t kDirectShadeLds = MCPT_DIRECT_RESOLVE ? size_t(kDirectTableWords) * (48 + 4) : 0;
+static_assert(kDirectTableWords * 3 <= 256, "the shade's smallest workgroup copies one record part per thread");
+// the rays the secondary extends (bounce >= 1) took, one atomic per workgroup
+// (MCPT_DIRECT_RESOLVE builds): the next slot of KernelParams::stats
+constexpr int kStatExtend = 14;
 
 struct GpuGeom {
     float Ka[3], Kd[3], Ks[3];
@@ -252,7 +278,9 @@ struct QueryParams {
 struct WfCounters {                      // per (bounce, segment), 8 words
     uint32_t queued;                     // rays in this segment's queue (written by its producer)
     uint32_t hits;                       // slots whose hit id extend wrote (= queued; shade's count)
-    uint32_t pad[6];
+    uint32_t resolved;                   // rays in the queue's tail [seg - resolved, seg), hit ids written by
+                                         // the shade that made them (MCPT_DIRECT_RESOLVE; else 0)
+    uint32_t pad[5];
 };
 struct WfParams {
     // ray queue b: three float4 streams of slot_stride entries (SoA),
@@ -318,8 +346,11 @@ inline size_t lds_bytes_counted_in_lds(uint32_t image_bytes, int S) {
 // direct lists: the lean LDS extend keeps its table behind the counter block.
 // The table never decides where a scene lives: if it does not fit beside the
 // image the scene stays in LDS and its renders carry no selectors
+// (direct resolve with the records in the shade's LDS: the shade's static LDS --
+// its copy and 64 B of counters -- must fit beside the extend's workgroup instead)
 inline bool direct_lists_fit(uint32_t image_bytes, uint32_t node_boxes) {
-    return !node_boxes && lds_bytes_counted_in_lds(image_bytes, 4) + kDirectLdsBytes <= kMaxLds;
+    const size_t need = kDirectShadeLds + 64 > kDirectLdsBytes ? kDirectShadeLds + 64 : kDirectLdsBytes;
+    return !node_boxes && lds_bytes_counted_in_lds(image_bytes, 4) + need <= kMaxLds;
 }
 #endif
 constexpr size_t lds_bytes_global(int S, bool counted) {

@@ -37,8 +37,9 @@ namespace {
 constexpr uint32_t kNoRay = 0xFFFFFFFFu;
 // Direct lists (render_launch.hpp MCPT_DIRECT_LISTS): the word's top four bits
 // carry the ray's selector (0 walk, 1 + box its list); the depth is the rest
+// (MCPT_DIRECT_RESOLVE: the shade resolves a direct ray itself, no word carries a selector)
 __device__ __forceinline__ uint32_t ray_depth(uint32_t w) {
-#if MCPT_DIRECT_LISTS
+#if MCPT_DIRECT_LISTS && !MCPT_DIRECT_RESOLVE
     return w == kNoRay ? w : (w & kDepthMask);
 #else
     return w;

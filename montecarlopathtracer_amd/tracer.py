@@ -343,6 +343,8 @@ class Scene:
         d = st.as_dict()
         # secondary rays resolved from a box's list instead of a walk (lean wavefront renders)
         d["direct_rays"] = int(lib().mcpt_scene_direct_rays(self.handle))
+        # rays the wavefront's secondary extends walked (0: megakernel, or built without the direct resolve)
+        d["extend_rays"] = int(lib().mcpt_scene_extend_rays(self.handle))
         return d
 
     def primary_tile_classes(self):

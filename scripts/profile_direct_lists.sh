@@ -1,6 +1,7 @@
 #!/bin/bash
-# Where the direct lists' gain is (PERFLOG row 178), for A = libmcpt_a.so (this
-# tree built with -DMCPT_DIRECT_LISTS=0) and B = libmcpt.so: a kernel trace of
+# Where a compile switch's gain is (direct lists, PERFLOG row 178; direct
+# resolve, row 179), for A = libmcpt_a.so (this tree built with the switch
+# at 0, e.g. -DMCPT_DIRECT_RESOLVE=0) and B = libmcpt.so: a kernel trace of
 # one C2 frame on one stream (extend and shade per bounce,
 # scripts/wf_bounce_times.py), then, in runs of their own with no tracing
 # alongside, SQ_INSTS_VALU per kernel class (scripts/valu_by_class.py); then the

@@ -1,0 +1,272 @@
+"""The wavefront's direct resolve on the GPU (render_launch.hpp MCPT_DIRECT_RESOLVE):
+where the direct lists are active -- lean renders of a scene in LDS with occluder
+boxes -- the shade that makes a direct ray also finds its hit and writes ray and
+hit id to the far end of the segment's next queue; no direct ray reaches an
+extend.  The image stays the oracle's bit for bit.
+
+The oracle (which walks every ray) is the reference everywhere: every lean
+render must give its image and its `rays`, and the counting render (no culls, no
+lists) the same.
+
+Counters (`scene.render(...)[1]`): S = rays - paths is the secondary rays made;
+`direct_rays` the ones the shades resolved, `extend_rays` the ones the secondary
+extends (bounce >= 1) took.  A counting render has neither culls nor lists:
+    extend_rays == S,  direct_rays == 0.
+A lean render's other secondary rays are the ones the miss cull and the terminal
+cull answered; the library does not count those, so what is asserted is
+    extend_rays + direct_rays <= S          (the rest: the culls', >= 0).
+That no direct ray is among `extend_rays` is checked against the lean render of
+the same scene in the global layout, which has the same miss cull and the same
+terminal cull but no lists, so its extends walk the direct rays too: with T the
+direct rays its terminal cull removes (0 <= T <= direct_rays),
+    extend_rays(global) == extend_rays(lds) + direct_rays(lds) - T,
+asserted as extend_rays(lds) <= extend_rays(global) <= extend_rays(lds) +
+direct_rays(lds), strictly on the left at depth >= 2, where direct rays below
+the terminal depth exist.  (T itself is not a counter, so this bounds the direct
+rays an LDS extend could have taken; that it takes none is the mechanism's: an
+extend runs over the queue's head, and resolved rays are only ever in the tail.)
+
+A shade block that straddles the head / tail boundary of a queue is covered by
+construction, the counters being per render and not per segment: every frame
+here but `big` leaves each segment at most 256 slots, fewer than the shade's
+block, so wherever a segment has both walked and resolved rays one block holds
+the head's end and the tail; `big` (256 x 256, 5 spp: 1280 slots per segment of
+a 256-CU device) runs the shade's loop over several blocks, the boundary inside
+one of them.
+"""
+import numpy as np
+import pytest
+
+from test_direct_lists import KQUADS_CAM, SEAM_CAM, dl_scenes  # noqa: F401  (dl_scenes: a fixture)
+from test_miss_cull import INSIDE, _same
+
+CHUNK = 2
+# width, height, spp, samples per chunk
+FRAMES = {"a": (64, 64, 5, CHUNK), "b": (48, 64, 5, CHUNK), "big": (256, 256, 5, CHUNK),
+          # whole 64-slot groups per segment, one batch: 64, 256 and 1024 groups
+          "g1": (64, 64, 1, 1), "g4": (64, 64, 4, 4), "g16": (64, 64, 16, 16)}
+DEPTHS = (0, 1, 2, 7)
+
+
+@pytest.fixture(scope="session")
+def dr_oracle(oracle_mod, dl_scenes):  # noqa: F811
+    """(scene, frame, depth, camera, mode) -> the oracle's (image, counters), rendered once and read-only"""
+    have, scenes = {}, {}
+
+    def get(name, frame, depth, cam=None, qe=False):
+        key = (name, frame, depth, tuple(sorted((cam or {}).items())), qe)
+        if key not in have:
+            if name not in scenes:
+                scenes[name] = oracle_mod.Scene(dl_scenes[name])
+            w, h, spp, chunk = FRAMES[frame]
+            kw = dict(cam or {})
+            if qe:
+                kw.update(mode=oracle_mod.MODE_QE, seed=0x5EED, illum=1.0, fov=45.0, fresnel_kd=0)
+            img, cnt = scenes[name].render(oracle_mod.RenderParams(
+                width=w, height=h, spp=spp, spp_chunk=chunk, max_depth=depth, threads=16, **kw))
+            img.setflags(write=False)
+            have[key] = (img, cnt)
+        return have[key]
+
+    return get
+
+
+def _params(mcpt, frame, depth, lean=True, sort=False, cam=None, **kw):
+    w, h, spp, chunk = FRAMES[frame]
+    return mcpt.RenderParams(width=w, height=h, spp=spp, spp_chunk=chunk, tile=kw.pop("tile", 8), max_depth=depth,
+                             pipeline="wavefront", wf_sort=sort, lean=lean, **(cam or {}), **kw)
+
+
+def _check(mcpt, scene, ref, rc, frame, depth, sort=False, cam=None, **kw):
+    """lean = counting = oracle: image bits and ray count, and the counters' identities; -> the lean stats"""
+    lean, ls = scene.render(_params(mcpt, frame, depth, sort=sort, cam=cam, **kw))
+    full, fs = scene.render(_params(mcpt, frame, depth, lean=False, sort=sort, cam=cam, **kw))
+    assert _same(lean, ref) and _same(full, ref)
+    assert ls["rays"] == rc["rays"] and fs["rays"] == rc["rays"]
+    assert ls["paths"] == rc["paths"] and ls["shades"] == rc["shades"]
+    secondary = rc["rays"] - rc["paths"]
+    assert fs["direct_rays"] == 0 and fs["extend_rays"] == secondary
+    assert ls["extend_rays"] + ls["direct_rays"] <= secondary
+    return ls
+
+
+def _scene01(mcpt, dl_scenes):  # noqa: F811
+    scene = mcpt.Scene(mcpt.ObjModel(dl_scenes["scene01"]))
+    assert scene.info()["direct_list_boxes"] == 5
+    return scene
+
+
+# ---- without a GPU ---------------------------------------------------------------------------
+
+def test_stats_report_extend_rays(mcpt, dl_scenes):  # noqa: F811
+    """the C accessor exists and a scene that has not rendered reports none"""
+    s = mcpt.Scene(mcpt.ObjModel(dl_scenes["kquads"]), host_only=True)
+    from montecarlopathtracer_amd._capi import lib
+    assert int(lib().mcpt_scene_extend_rays(s.handle)) == 0 and int(lib().mcpt_scene_extend_rays(None)) == 0
+
+
+# ---- on the GPU ------------------------------------------------------------------------------
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sort", [False, True], ids=["queue", "sorted"])
+@pytest.mark.parametrize("depth", DEPTHS)
+@pytest.mark.parametrize("frame", ["a", "b"])
+def test_scene01_matches_oracle(mcpt, dr_oracle, dl_scenes, frame, depth, sort):  # noqa: F811
+    """partial waves in head and tail; depth 0 has no secondary ray, depth 1 puts the terminal cull on a
+    queue with a tail"""
+    scene = _scene01(mcpt, dl_scenes)
+    ref, rc = dr_oracle("scene01", frame, depth)
+    ls = _check(mcpt, scene, ref, rc, frame, depth, sort=sort)
+    if depth == 0:
+        assert ls["direct_rays"] == 0 and ls["extend_rays"] == 0
+        return
+    assert ls["direct_rays"] > 0
+    # no direct ray among the extends' rays: the global layout walks them too
+    glob = mcpt.Scene(mcpt.ObjModel(dl_scenes["scene01"]), layout="global")
+    gi, gs = glob.render(_params(mcpt, frame, depth, sort=sort))
+    assert _same(gi, ref) and gs["direct_rays"] == 0
+    assert ls["extend_rays"] <= gs["extend_rays"] <= ls["extend_rays"] + ls["direct_rays"]
+    if depth >= 2:
+        assert 0 < ls["extend_rays"] < gs["extend_rays"]
+    if depth == 7:                                             # (priced: two thirds of the walked rays)
+        assert ls["direct_rays"] > 0.3 * (rc["rays"] - rc["paths"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sort", [False, True], ids=["queue", "sorted"])
+@pytest.mark.parametrize("frame", ["g1", "g4", "g16"])
+def test_head_and_tail_meet_in_full_queues(mcpt, dr_oracle, dl_scenes, frame, sort):  # noqa: F811
+    """a camera inside the box looking at walls, path counts that are whole 64-slot groups per segment:
+    where every path of a segment continues, its queue 1 has no free slot between head and tail"""
+    scene = _scene01(mcpt, dl_scenes)
+    ref, rc = dr_oracle("scene01", frame, 7, cam=INSIDE)
+    ls = _check(mcpt, scene, ref, rc, frame, 7, sort=sort, cam=INSIDE)
+    assert ls["direct_rays"] > 0 and ls["extend_rays"] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sort", [False, True], ids=["queue", "sorted"])
+def test_shade_loop_over_several_blocks(mcpt, dr_oracle, dl_scenes, sort):  # noqa: F811
+    """segments longer than the shade's block: the tail's indices start in a later block of the loop"""
+    scene = _scene01(mcpt, dl_scenes)
+    ref, rc = dr_oracle("scene01", "big", 2)
+    ls = _check(mcpt, scene, ref, rc, "big", 2, sort=sort)
+    assert ls["direct_rays"] > 0 and ls["extend_rays"] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sort", [False, True], ids=["queue", "sorted"])
+@pytest.mark.parametrize("depth", [1, 3])
+def test_quad_of_k_is_resolved_and_of_k_plus_1_walked(mcpt, dr_oracle, dl_scenes, depth, sort):  # noqa: F811
+    scene = mcpt.Scene(mcpt.ObjModel(dl_scenes["kquads"]))
+    assert sorted(scene.direct_lists()["counts"]) == [0, 2, 2]
+    ref, rc = dr_oracle("kquads", "a", depth, cam=KQUADS_CAM)
+    assert float(ref.max()) > 0.0 and rc["shades"] > 0
+    ls = _check(mcpt, scene, ref, rc, "a", depth, sort=sort, cam=KQUADS_CAM)
+    assert ls["direct_rays"] > 0
+    if depth == 3:
+        assert ls["extend_rays"] > 0                           # the wall's rays towards the floor walk
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sort", [False, True], ids=["queue", "sorted"])
+@pytest.mark.parametrize("depth", [1, 3])
+def test_rays_along_a_seam(mcpt, dr_oracle, dl_scenes, depth, sort):  # noqa: F811
+    """rays that start a hair off one quad and run close to the other: resolved rays that miss both
+    triangles of their box end there"""
+    scene = mcpt.Scene(mcpt.ObjModel(dl_scenes["seam"]))
+    ref, rc = dr_oracle("seam", "b", depth, cam=SEAM_CAM)
+    assert float(ref.max()) > 0.0 and rc["shades"] > 0
+    ls = _check(mcpt, scene, ref, rc, "b", depth, sort=sort, cam=SEAM_CAM)
+    assert 0 < ls["direct_rays"] < rc["rays"] - rc["paths"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sort", [False, True], ids=["queue", "sorted"])
+def test_tile_4(mcpt, dr_oracle, dl_scenes, sort):  # noqa: F811
+    scene = _scene01(mcpt, dl_scenes)
+    ref, rc = dr_oracle("scene01", "b", 7)
+    assert _check(mcpt, scene, ref, rc, "b", 7, sort=sort, tile=4)["direct_rays"] > 0
+
+
+@pytest.mark.gpu
+def test_two_packed_shards_reassemble(mcpt, dr_oracle, dl_scenes):  # noqa: F811
+    scene = _scene01(mcpt, dl_scenes)
+    w, h = FRAMES["b"][:2]
+    got = np.full((h, w, 3), -1.0, np.float32)
+    tot = {"rays": 0, "direct_rays": 0, "extend_rays": 0}
+    for r in range(2):
+        p = _params(mcpt, "b", 7, shard_count=2, shard_index=r)
+        part, st = scene.render(p)
+        assert st["direct_rays"] > 0
+        for k in tot:
+            tot[k] += st[k]
+        xy = p.shard_pixels()
+        ok = xy[:, 0] >= 0
+        got[xy[ok, 1], xy[ok, 0]] = part[ok]
+    ref, rc = dr_oracle("scene01", "b", 7)
+    assert _same(got, ref) and tot["rays"] == rc["rays"]
+    # the shards' counters are the whole frame's: what becomes of a ray depends on the ray alone
+    whole = scene.render(_params(mcpt, "b", 7))[1]
+    assert tot["direct_rays"] == whole["direct_rays"] and tot["extend_rays"] == whole["extend_rays"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sort", [False, True], ids=["queue", "sorted"])
+def test_quinengine_lean(mcpt, dr_oracle, dl_scenes, sort):  # noqa: F811
+    depth = 2
+    ref, rc = dr_oracle("scene01", "a", depth, qe=True)
+    assert float(ref.max()) > 0.0
+    scene = _scene01(mcpt, dl_scenes)
+    w, h, spp, chunk = FRAMES["a"]
+    for lean in (True, False):
+        img, st = scene.render(mcpt.RenderParams.for_quinengine(
+            width=w, height=h, spp=spp, spp_chunk=chunk, tile=8, max_depth=depth, seed=0x5EED, pipeline="wavefront",
+            wf_sort=sort, lean=lean))
+        assert _same(img, ref) and st["rays"] == rc["rays"], lean
+        assert (st["direct_rays"] > 0) == lean
+        secondary = st["rays"] - st["paths"]
+        assert st["extend_rays"] + st["direct_rays"] <= secondary
+        if not lean:
+            assert st["extend_rays"] == secondary
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,cam", [("closed", dict(eye=(0.0, 5.0, 4.0))),
+                                      ("lone", dict(eye=(0.0, 4.0, 9.0)))])
+def test_scene_without_boxes(mcpt, dr_oracle, dl_scenes, name, cam):  # noqa: F811
+    scene = mcpt.Scene(mcpt.ObjModel(dl_scenes[name]))
+    assert scene.info()["miss_cull_boxes"] == 0
+    ref, rc = dr_oracle(name, "a", 2, cam=cam)
+    assert float(ref.max()) > 0.0
+    assert _check(mcpt, scene, ref, rc, "a", 2, cam=cam)["direct_rays"] == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("depth", [1, 7])
+def test_global_layout_keeps_the_walk(mcpt, dr_oracle, dl_scenes, depth):  # noqa: F811
+    scene = mcpt.Scene(mcpt.ObjModel(dl_scenes["scene01"]), layout="global")
+    assert scene.info()["node_boxes"] == 1 and scene.info()["miss_cull_boxes"] == 8
+    ref, rc = dr_oracle("scene01", "a", depth)
+    assert _check(mcpt, scene, ref, rc, "a", depth)["direct_rays"] == 0
+
+
+@pytest.mark.gpu
+def test_megakernel_unchanged(mcpt, dr_oracle, dl_scenes):  # noqa: F811
+    scene = _scene01(mcpt, dl_scenes)
+    w, h, spp, chunk = FRAMES["a"]
+    ref, rc = dr_oracle("scene01", "a", 2)
+    img, st = scene.render(mcpt.RenderParams(width=w, height=h, spp=spp, spp_chunk=chunk, max_depth=2, lean=True))
+    assert _same(img, ref) and st["rays"] == rc["rays"] and st["direct_rays"] == 0 and st["extend_rays"] == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sort", [False, True], ids=["queue", "sorted"])
+def test_two_renders_are_bit_identical(mcpt, dl_scenes, sort):  # noqa: F811
+    """queue order (which slots of head and tail a ray gets) depends on scheduling; nothing reads it"""
+    scene = _scene01(mcpt, dl_scenes)
+    a, sa = scene.render(_params(mcpt, "g16", 7, sort=sort, cam=INSIDE))
+    b, sb = scene.render(_params(mcpt, "g16", 7, sort=sort, cam=INSIDE))
+    assert _same(a, b)
+    assert {k: sa[k] for k in ("rays", "direct_rays", "extend_rays")} == {k: sb[k] for k in
+                                                                          ("rays", "direct_rays", "extend_rays")}
