@@ -329,6 +329,12 @@ uint64_t mcpt_scene_direct_rays(const mcpt_scene* s);
  * terminal cull answer.  0 for the megakernel and in a build without the direct
  * resolve.  (An addition, as the one above; the ABI stays 9.) */
 uint64_t mcpt_scene_extend_rays(const mcpt_scene* s);
+/* Of those, the rays an extend started with a selector (the clip walk: a ray
+ * through at least one box without a list and at most one with a list walks
+ * only inside its unlisted boxes' slab interval, its listed box's triangles
+ * tested first).  0 wherever the direct lists are off, and in a build without
+ * the clip walk.  (An addition, as the ones above; the ABI stays 9.) */
+uint64_t mcpt_scene_clipped_rays(const mcpt_scene* s);
 /* Primary lists of the scene's last render (wavefront, lean CV renders of a
  * scene in LDS with 8x8 tiles): out[0..2] = the owned tiles whose candidate
  * list is empty (no primary ray made), holds 1..K triangles (tested straight

@@ -184,6 +184,7 @@ struct mcpt_scene {
     uint32_t direct_list[mcpt::kMaxMissBoxes * 16] = {};
     uint64_t direct_rays = 0;           // of the stats record last read
     uint64_t extend_rays = 0;           // likewise: the rays the secondary extends took
+    uint64_t clipped_rays = 0;          // likewise: the rays an extend started with a selector (clip walk)
     void* d_image = nullptr;
     void* d_normals = nullptr;
     Workspace ws;
@@ -615,7 +616,7 @@ Plan make_plan(const mcpt_scene& s, const mcpt_render_params* p) {
     if (!p) throw mcpt::Error{MCPT_E_INVALID, "params is NULL"};
     if (p->width <= 0 || p->height <= 0) throw mcpt::Error{MCPT_E_INVALID, "width/height must be positive"};
     if (p->spp == 0) throw mcpt::Error{MCPT_E_INVALID, "spp must be > 0"};
-    if (p->max_depth < 0 || p->max_depth > 1000) throw mcpt::Error{MCPT_E_INVALID, "max_depth out of range"};
+    if (p->max_depth < 0 || p->max_depth > mcpt::kMaxDepthParam) throw mcpt::Error{MCPT_E_INVALID, "max_depth out of range"};
     if (p->wf_streams < 0 || p->wf_streams > mcpt::kMaxWfStreams)
         throw mcpt::Error{MCPT_E_INVALID, "wf_streams must be 0 (automatic) or 1..4"};
     if (p->wf_refill < 0 || p->wf_refill > 64 || p->ready_thresh < 0 || p->ready_thresh > 64)
@@ -1009,6 +1010,7 @@ void read_stats(mcpt_scene& s, mcpt_render_stats* out) {
     s.pending.clear();
     s.direct_rays = 0;
     s.extend_rays = 0;
+    s.clipped_rays = 0;
     if (s.ws.small) {
         unsigned long long st[16];
         HIP_TRY(hipMemcpy(st, static_cast<char*>(s.ws.small) + 64, sizeof st, hipMemcpyDeviceToHost));
@@ -1031,6 +1033,7 @@ void read_stats(mcpt_scene& s, mcpt_render_stats* out) {
         r.leaf_refs = st[4]; r.tri_tests = st[5]; r.shades = st[6]; r.stack_spills = st[7];
         s.direct_rays = st[mcpt::kStatDirect];
         s.extend_rays = st[mcpt::kStatExtend];
+        s.clipped_rays = st[mcpt::kStatClipped];
     }
     r.renders = s.renders;
     r.devices = 1;
@@ -1164,6 +1167,7 @@ void read_stats_all(mcpt_scene& s, mcpt_render_stats* out) {
         r.stack_spills += q.stack_spills;
         s.direct_rays += R->direct_rays;
         s.extend_rays += R->extend_rays;
+        s.clipped_rays += R->clipped_rays;
         r.kernel_ms = std::max(r.kernel_ms, q.kernel_ms);
         r.reduce_ms = std::max(r.reduce_ms, q.reduce_ms);
     }
@@ -1819,6 +1823,7 @@ int mcpt_scene_direct_lists(const mcpt_scene* s, int32_t* tri_box, uint32_t* box
 
 uint64_t mcpt_scene_direct_rays(const mcpt_scene* s) { return s ? s->direct_rays : 0; }
 uint64_t mcpt_scene_extend_rays(const mcpt_scene* s) { return s ? s->extend_rays : 0; }
+uint64_t mcpt_scene_clipped_rays(const mcpt_scene* s) { return s ? s->clipped_rays : 0; }
 
 int mcpt_scene_copy_kd(const mcpt_scene* s, uint32_t* nodes, uint32_t* leaf_ids, int32_t* kd_tris, float* geoms) {
     if (!s) return fail(MCPT_E_INVALID, "NULL scene");

@@ -121,7 +121,7 @@ constexpr int kMaxMissBoxes = 8;
 #endif
 constexpr uint32_t kDirectK = MCPT_DIRECT_K;
 static_assert(kDirectK >= 1 && kDirectK <= 15, "a box's count is carried in 4 bits");
-constexpr uint32_t kDirectShift = 28, kDepthMask = (1u << kDirectShift) - 1u;
+// (kDirectShift, kDepthMask: below, behind MCPT_CLIP_WALK, which moves them)
 // the extend's LDS copy of the table: kMaxMissBoxes x kDirectK record indices
 // and one 16-B unit more (the leaf branch reads its refs in pairs)
 constexpr uint32_t kDirectTableWords = kMaxMissBoxes * kDirectK;
@@ -155,6 +155,38 @@ static_assert(kDirectTableWords * 3 <= 256, "the shade's smallest workgroup copi
 // the rays the secondary extends (bounce >= 1) took, one atomic per workgroup
 // (MCPT_DIRECT_RESOLVE builds): the next slot of KernelParams::stats
 constexpr int kStatExtend = 14;
+// Clip walk (where the direct resolve is active): the rays the secondary extends
+// still walk are almost all rays through a large box (scene01: one of the two
+// 420-triangle objects, usually with one wall behind it).  The shade's box test
+// already knows which boxes the new ray's segment hits; a ray that is not direct
+// and hits at least one box without a list and at most one box with a list carries
+// that 8-bit box mask as its selector, in the top byte of the {d, depth} word (0:
+// the full walk; kNoRay, all ones, stays unique: a depth is < 2^24).  The lean LDS
+// extend starts such a ray with the root interval cut to the union of its
+// unlisted boxes' slab intervals -- the shade's test again, [min lo * kEpsLo,
+// max hi * kEpsHi] -- and tests the listed box's triangles first, through the
+// leaf branch; the pop behind the list starts the clipped walk or ends the ray
+// by the walk's own rule.  Every triangle is in exactly one box, and one the ray
+// can pass tri_accept on lies in a box the ray's slab test passes, with its t
+// inside that box's interval: the list plus the leaves the walk reaches inside
+// the interval are a superset of what the ray can hit, and the closest hit is
+// the minimum of (t, rank) over the triangles tested.
+// 0: the pipeline without it, the same kernels as before it (A/B builds).
+#ifndef MCPT_CLIP_WALK
+#define MCPT_CLIP_WALK MCPT_DIRECT_RESOLVE
+#endif
+#if MCPT_CLIP_WALK && !MCPT_DIRECT_RESOLVE
+#error "MCPT_CLIP_WALK needs MCPT_DIRECT_RESOLVE (the direct selector's bits)"
+#endif
+// the selector's place in the depth word: a direct ray's 1 + box in the top four
+// bits, or (clip walk) the box mask in the top byte
+constexpr uint32_t kDirectShift = MCPT_CLIP_WALK ? 24 : 28, kDepthMask = (1u << kDirectShift) - 1u;
+// a ray's depth is at most 3 * max_depth + 1 (QuinEngine), max_depth <= kMaxDepthParam
+constexpr int kMaxDepthParam = 1000;
+static_assert(3u * kMaxDepthParam + 1u < kDepthMask, "a ray's depth must fit under its selector");
+static_assert(!MCPT_CLIP_WALK || kMaxMissBoxes <= 8, "the clip walk's selector is one byte of box bits");
+// the rays an extend started with a selector: the last slot of KernelParams::stats
+constexpr int kStatClipped = 15;
 
 struct GpuGeom {
     float Ka[3], Kd[3], Ks[3];
@@ -349,7 +381,12 @@ inline size_t lds_bytes_counted_in_lds(uint32_t image_bytes, int S) {
 // (direct resolve with the records in the shade's LDS: the shade's static LDS --
 // its copy and 64 B of counters -- must fit beside the extend's workgroup instead)
 inline bool direct_lists_fit(uint32_t image_bytes, uint32_t node_boxes) {
+#if MCPT_CLIP_WALK
+    // (clip walk: the extend holds the table again, beside the shade's copy)
+    const size_t need = kDirectShadeLds + 64 + kDirectLdsBytes;
+#else
     const size_t need = kDirectShadeLds + 64 > kDirectLdsBytes ? kDirectShadeLds + 64 : kDirectLdsBytes;
+#endif
     return !node_boxes && lds_bytes_counted_in_lds(image_bytes, 4) + need <= kMaxLds;
 }
 #endif

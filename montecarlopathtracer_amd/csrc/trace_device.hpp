@@ -387,10 +387,30 @@ __device__ __forceinline__ uint32_t scene_box_hits(V3 o, V3 d, V3 inv, float bes
         const float az = (boxes[i][2] - o.z) * inv.z, bz = (boxes[i][5] - o.z) * inv.z;
         const float lo = max_qnan(max3_qnan(0.0f, nx ? bx : ax, ny ? by : ay), nz ? bz : az);
         const float hi = min_qnan(min3_qnan(best_init, nx ? ax : bx, ny ? ay : by), nz ? az : bz);
+#if MCPT_CLIP_WALK
+        // (clip walk: the boxes that passed as a bit mask -- bit i box i -- whose
+        // popcount is the number of boxes hit; 0 as before when the ray fails all)
+        acc |= !(lo * kEpsLo > hi * kEpsHi) ? 1u << i : 0u;
+#else
         acc += !(lo * kEpsLo > hi * kEpsHi) ? 256u + i : 0u;
+#endif
     }
     return acc;
 }
+#if MCPT_CLIP_WALK
+// Clip walk (render_launch.hpp MCPT_CLIP_WALK): the slab interval [lo, hi] of ray
+// (o, d) in one occluder box, scene_box_hits' operations on the same operands
+// (the extend runs them again for the unlisted boxes of a ray's selector)
+__device__ __forceinline__ void box_interval(V3 o, V3 d, V3 inv, float best_init, const float (&b)[6], float& lo,
+                                             float& hi) {
+    const bool nx = __float_as_uint(d.x) >> 31, ny = __float_as_uint(d.y) >> 31, nz = __float_as_uint(d.z) >> 31;
+    const float ax = (b[0] - o.x) * inv.x, bx = (b[3] - o.x) * inv.x;
+    const float ay = (b[1] - o.y) * inv.y, by = (b[4] - o.y) * inv.y;
+    const float az = (b[2] - o.z) * inv.z, bz = (b[5] - o.z) * inv.z;
+    lo = max_qnan(max3_qnan(0.0f, nx ? bx : ax, ny ? by : ay), nz ? bz : az);
+    hi = min_qnan(min3_qnan(best_init, nx ? ax : bx, ny ? ay : by), nz ? az : bz);
+}
+#endif
 #endif
 #endif
 

@@ -25,6 +25,9 @@
 //               that hits a single small box is resolved from that box's
 //               triangles here and goes, with its hit id, to the far end of
 //               queue b+1, which the extend does not visit (MCPT_DIRECT_RESOLVE)
+//               and one that walks through a box without a list carries the mask
+//               of the boxes it hits, so that extend b+1 walks it only inside those
+//               boxes' slab interval (MCPT_CLIP_WALK)
 //   cull        lean renders, before the last extend: the terminal query's rays
 //               that can reach no emitter leave the queue (wf_cull_terminal)
 //   candidates  lean CV renders of an LDS scene, once per call: per 8x8 tile, the
@@ -133,14 +136,22 @@ wf_extend(const KernelParams kp, const WfParams wf) {
     // the ref after a list's last one: record 0, in bounds, unused)
     // (MCPT_DIRECT_RESOLVE: the shade resolves those rays, none reaches an extend)
     constexpr bool DIRECT = LAY == kLayLds && !COUNT && !MCPT_DIRECT_RESOLVE;
+    // (MCPT_CLIP_WALK: the table is here again, for the listed box of a clipped ray's selector)
+    constexpr bool CLIP = LAY == kLayLds && !COUNT && MCPT_CLIP_WALK;
     uint32_t dtab = 0, dcnt = 0;
-    if constexpr (DIRECT) {
+    if constexpr (DIRECT || CLIP) {
         // (asm results, as the refill threshold below: not kernel-argument reads in the loop)
         asm volatile("s_mov_b32 %0, %1" : "=s"(dcnt) : "s"(wf.direct_counts));
         asm volatile("s_mov_b32 %0, %1" : "=s"(dtab) : "s"((sc.image_bytes + (uint32_t)kLdsCounterBytes - sc.off_leafs) / 4u));
         if (dcnt && tid < (int)(kDirectLdsBytes / 4))
             (lslot + kLdsCounterBytes / 4)[tid] = tid < (int)kDirectTableWords ? wf.direct_list[tid] : 0u;
     }
+#if MCPT_CLIP_WALK
+    // clip walk: the boxes without a list (a selector's other bit, if any, is its
+    // listed box), and this wave's rays started with a selector
+    uint32_t unl = 0, nclip = 0, csel = 0;
+    if constexpr (CLIP) asm volatile("s_mov_b32 %0, %1" : "=s"(unl) : "s"(unlisted_boxes(wf.direct_counts)));
+#endif
 #endif
     __syncthreads();
     uint4* st = reinterpret_cast<uint4*>(smem) + tid;
@@ -186,6 +197,49 @@ wf_extend(const KernelParams kp, const WfParams wf) {
             r.lend = dr ? lp + ((dcnt >> (4u * sel)) & 15u) : 0u;
         }
 #endif
+#if MCPT_CLIP_WALK
+        // a clipped ray (selector: the mask of the boxes its segment hits): the root
+        // interval cut to the union of its unlisted boxes' slab intervals -- the
+        // shade's test again, box by box, boxes no lane carries skipped -- and its
+        // listed box's triangles, if it has one, tested first by the leaf branch: the
+        // root then waits on the stack as the one entry, and the pop behind the list
+        // starts the walk or ends the ray (best <= tmin * kEpsLo); an empty interval
+        // starts no walk
+        if constexpr (CLIP) {
+            csel = depth == kNoRay ? 0u : depth >> kDirectShift;
+            const uint32_t um = csel & unl;
+            const V3 inv = v3(r.ix, r.iy, r.iz);
+            float clo = kFltMax, chi = 0.0f;
+#pragma unroll 1
+            for (uint32_t i = 0; i < wf.n_miss_boxes; i++) {
+                const bool mine = ((um >> i) & 1u) != 0u;
+                if (((unl >> i) & 1u) != 0u && __ballot(mine)) {
+                    float lo, hi;
+                    box_interval(r.o, r.d, inv, kp.best_init, wf.miss_box[i], lo, hi);
+                    clo = mine ? min_qnan(clo, lo) : clo;
+                    chi = mine ? max_qnan(chi, hi) : chi;
+                }
+            }
+            const bool sel = csel != 0u;
+            const float t0 = max_qnan(r.tmin, clo * kEpsLo);
+            const float t1 = min_qnan(r.tmax, (chi * kEpsHi) * kEpsHi);   // (r.tmax: the far end times kEpsHi)
+            const bool walk = !(t0 > t1);
+            const uint32_t lm = csel & ~unl;                               // the listed box's bit, or 0
+            const bool hasl = lm != 0u;
+            const uint32_t lb = (uint32_t)(__ffs((int)lm) - 1) & 7u;
+            const uint32_t lp = dtab + lb * kDirectK;
+            r.lpos = hasl ? lp : 0u;
+            r.lend = hasl ? lp + ((dcnt >> (4u * lb)) & 15u) : 0u;
+            r.tmin = sel ? t0 : r.tmin;
+            r.tmax = sel ? t1 : r.tmax;
+            if (hasl & walk) {
+                st4(slot_of<S>(st, BLOCK, 0), make_uint4(r.nw0, r.nw1, __float_as_uint(t0), __float_as_uint(t1)));
+                r.sp = BLOCK * 16;
+            }
+            mode = (depth != kNoRay && live && (!sel | hasl | walk)) ? kTrav : kReady;
+            return;
+        }
+#endif
         mode = (depth != kNoRay && live) ? kTrav : kReady;
     };
 #ifdef MCPT_PHASE_TIMING
@@ -206,6 +260,9 @@ wf_extend(const KernelParams kp, const WfParams wf) {
     const float4 eye4 = make_float4(kp.eye[0], kp.eye[1], kp.eye[2], 0.0f);
     auto ld_o = [&](uint32_t sl) { return eye0 ? eye4 : ldq(&qb[qf(seg0 + sl, kQO, qs)]); };
     if (slot < count) start(ld_o(slot), ldq(&qb[qf(seg0 + slot, kQD, qs)]));
+#if MCPT_CLIP_WALK
+    if constexpr (CLIP) nclip += (uint32_t)__popcll(__ballot(slot < count && csel != 0u));
+#endif
     if (PF && nslot < count) { no4 = ld_o(nslot); nd4 = ldq(&qb[qf(seg0 + nslot, kQD, qs)]); }
     WF_STAMP(tm_setup);
     for (;;) {
@@ -251,6 +308,9 @@ wf_extend(const KernelParams kp, const WfParams wf) {
         const bool fin = mode == kReady;
         const uint32_t ns0 = PF ? 0u : cur_chunk.take(fin, lslot);   // (collective: every lane)
         const uint32_t fslot = slot;
+#if MCPT_CLIP_WALK
+        csel = 0u;
+#endif
         if (fin) {
             const int32_t hid = r.htri;
             // (the next ray set up unconditionally: no branch in the hand-off; a
@@ -268,6 +328,10 @@ wf_extend(const KernelParams kp, const WfParams wf) {
             // (r holds the next ray by now: the id saved before)
             reinterpret_cast<int32_t*>(qb + qf(0, kQHIT, qs))[seg0 + fslot] = hid;
         }
+#if MCPT_CLIP_WALK
+        // (wave-uniform: a scalar register; a lane past the segment's end started no ray)
+        if constexpr (CLIP) nclip += (uint32_t)__popcll(__ballot(fin && mode != kDead && csel != 0u));
+#endif
         // ---- prefetch the next ray of every lane that just started one -------
         if constexpr (PF) {
             const bool want = fin && mode != kDead;
@@ -303,6 +367,10 @@ wf_extend(const KernelParams kp, const WfParams wf) {
 #if MCPT_DIRECT_RESOLVE
     // the rays the secondary extends took (queues past 0 hold no empty slot)
     if (tid == 0 && wf.bounce > 0) atomicAdd(kp.stats + kStatExtend, (unsigned long long)count);
+#endif
+#if MCPT_CLIP_WALK
+    if constexpr (CLIP)
+        if ((tid & 63) == 0 && nclip) atomicAdd(kp.stats + kStatClipped, (unsigned long long)nclip);
 #endif
     if (tid == 0) cn->hits = count;                        // every slot's hit id is written
 }
@@ -378,6 +446,10 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
         ldrec[threadIdx.x] = open_scene<false, BLOCK>(nullptr, sc, 0).tris[k + (threadIdx.x - 3u * e)];
         if (threadIdx.x == 3u * e) ldk[e] = k;
     }
+#endif
+#if MCPT_CLIP_WALK
+    // clip walk: the boxes without a list, bit i box i (0 where the render has no lists: no selector)
+    const uint32_t unlisted = unlisted_boxes(wf.direct_counts);
 #endif
     __syncthreads();
     const SceneView sv = open_scene<false, BLOCK>(nullptr, sc, 0);
@@ -515,8 +587,14 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
                             stq(&wf.radiance[pid], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
                             cont = false;
                         }
+#if MCPT_CLIP_WALK
+                        // (acc: the mask of the boxes hit)
+                        const uint32_t box = (uint32_t)(__ffs((int)acc) - 1) & 7u;
+                        direct = acc != 0u && (acc & (acc - 1u)) == 0u && ((wf.direct_counts >> (4u * box)) & 15u) != 0u;
+#else
                         const uint32_t box = acc & 255u;
                         direct = (acc >> 8) == 1u && ((wf.direct_counts >> (4u * box)) & 15u) != 0u;
+#endif
 #if MCPT_DIRECT_RESOLVE
                         // direct resolve: the extend's answer for a direct ray, operation for
                         // operation -- begin_ray (its reciprocals are the box test's), then
@@ -562,6 +640,15 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
                             } else if (rhit < 0)
                                 stq(&wf.radiance[pid], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
                         }
+#if MCPT_CLIP_WALK
+                        // clip walk: a walking ray through at least one box without a list and
+                        // at most one with a list carries its box mask (never a direct ray, whose
+                        // one box has a list, nor a culled one, whose mask is 0)
+                        {
+                            const uint32_t lm = acc & ~unlisted;
+                            if ((acc & unlisted) != 0u && (lm & (lm - 1u)) == 0u) depth |= acc << kDirectShift;
+                        }
+#endif
 #else
                         if (direct) depth |= (box + 1u) << kDirectShift;
 #ifdef MCPT_PRICE_DIRECT
@@ -916,8 +1003,9 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
             const bool direct = in_lds && kp.lean && wf.n_miss_boxes && wf.direct_counts &&
                                 direct_lists_fit(img, kp.scene.node_boxes);
             if (!direct) wf.direct_counts = 0;
-            // (direct resolve: the same renders, but the extend holds no table)
-            const size_t direct_lds = direct && !MCPT_DIRECT_RESOLVE ? kDirectLdsBytes : 0;
+            // (direct resolve: the same renders, but the extend holds no table -- unless the
+            // clip walk tests a clipped ray's listed box from it)
+            const size_t direct_lds = direct && (!MCPT_DIRECT_RESOLVE || MCPT_CLIP_WALK) ? kDirectLdsBytes : 0;
 #else
             const size_t direct_lds = 0;
 #endif

@@ -37,14 +37,27 @@ namespace {
 constexpr uint32_t kNoRay = 0xFFFFFFFFu;
 // Direct lists (render_launch.hpp MCPT_DIRECT_LISTS): the word's top four bits
 // carry the ray's selector (0 walk, 1 + box its list); the depth is the rest
-// (MCPT_DIRECT_RESOLVE: the shade resolves a direct ray itself, no word carries a selector)
+// (MCPT_DIRECT_RESOLVE: the shade resolves a direct ray itself, no word carries a selector;
+// MCPT_CLIP_WALK: the top byte carries a walking ray's box mask, 0 = the full walk)
 __device__ __forceinline__ uint32_t ray_depth(uint32_t w) {
-#if MCPT_DIRECT_LISTS && !MCPT_DIRECT_RESOLVE
+#if (MCPT_DIRECT_LISTS && !MCPT_DIRECT_RESOLVE) || MCPT_CLIP_WALK
     return w == kNoRay ? w : (w & kDepthMask);
 #else
     return w;
 #endif
 }
+
+#if MCPT_CLIP_WALK
+// Clip walk: the occluder boxes without a list as a mask, bit i box i, from
+// WfParams::direct_counts (wave-uniform: scalar operations); 0 for a render
+// without lists, whose shades then make no selector
+__device__ __forceinline__ uint32_t unlisted_boxes(uint32_t direct_counts) {
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < (uint32_t)kMaxMissBoxes; b++) m |= ((direct_counts >> (4u * b)) & 15u) ? 0u : 1u << b;
+    return direct_counts ? m : 0u;
+}
+#endif
 
 __device__ __forceinline__ float4 pack(V3 v, uint32_t w) { return make_float4(v.x, v.y, v.z, __uint_as_float(w)); }
 

@@ -345,6 +345,8 @@ class Scene:
         d["direct_rays"] = int(lib().mcpt_scene_direct_rays(self.handle))
         # rays the wavefront's secondary extends walked (0: megakernel, or built without the direct resolve)
         d["extend_rays"] = int(lib().mcpt_scene_extend_rays(self.handle))
+        # of those, the rays an extend started with a box selector (0: built without the clip walk)
+        d["clipped_rays"] = int(lib().mcpt_scene_clipped_rays(self.handle))
         return d
 
     def primary_tile_classes(self):
