@@ -98,9 +98,9 @@ def _kd_rank(osc):
 
 # ---- the builder --------------------------------------------------------------------------
 
-@pytest.mark.parametrize("name", SCENES)
-def test_builder_invariants(mcpt, name):
-    s, v = _kd_verts(mcpt, mcpt.scene_path(name))
+def check_builder_invariants(mcpt, name, path):
+    """the assignment and the lists of one scene (shared with the scene zoo, tests/test_zoo_cpu.py)"""
+    s, v = _kd_verts(mcpt, path)
     boxes = s.miss_cull_boxes()
     dl = s.direct_lists()
     k = dl["k"]
@@ -129,9 +129,14 @@ def test_builder_invariants(mcpt, name):
     if name == "scene01":                                  # the five walls, two triangles each
         assert len(small) == 5 and (dl["counts"][small] == 2).all()
     # the miss cull's report is what it was: the boxes do not depend on the lists
-    again = mcpt.Scene(mcpt.ObjModel(mcpt.scene_path(name)), host_only=True)
+    again = mcpt.Scene(mcpt.ObjModel(path), host_only=True)
     assert again.miss_cull_boxes().tobytes() == boxes.tobytes()
     assert again.direct_lists()["lists"].tobytes() == dl["lists"].tobytes()
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_builder_invariants(mcpt, name):
+    check_builder_invariants(mcpt, name, mcpt.scene_path(name))
 
 
 @pytest.mark.parametrize("name", SCENES)
