@@ -588,6 +588,63 @@ int mcpt_trace_stats_read(mcpt_scene*, mcpt_render_stats* out);
 /* allocate what ray queries need (above), so that the device entries allocate nothing afterwards */
 int mcpt_scene_reserve_rays(mcpt_scene*);
 
+/* ---- device radiance queries: path-traced radiance over ray buffers ---------- */
+/* The third query kind: for every ray of a device buffer, the mean of spp
+ * path-traced samples of the radiance arriving along it -- the renders' path
+ * loop (CVMCTracer mode: max_depth scatters and the terminal query), samplers,
+ * RNG and traversal, started from the caller's rays instead of the pinhole
+ * camera.  Directions are used exactly as given (not re-normalized; the BSDF
+ * arithmetic assumes unit length).  Preconditions as mcpt_trace_device.
+ * Ray i has the stream id id_i = d_stream[i], or i without d_stream.  Sample s
+ * (global index spp_offset + s) starts from rng_init(id_i, TEA16(seed),
+ * spp_offset + s), draws and drops the two uniforms a render spends on its
+ * primary ray's jitter, then runs the render's loop: a ray that is the primary
+ * ray of sample spp_offset + s of pixel id_i traces that render's path, draw
+ * for draw.  Samples are summed in sample order inside chunks of spp_chunk, the
+ * chunk sums in chunk order, divided by (float)spp; prev_count > 0 applies the
+ * renders' linear running mean to the old content of the output.  Scheduling
+ * (workgroups, ready_thresh, the layout) never changes a result.
+ * The mode is a render parameter, not the scene's: a scene that also serves
+ * QuinEngine renders answers radiance queries in CVMCTracer mode like any other.
+ * Checks, before anything is launched or allocated and in this order:
+ * MCPT_E_INVALID for a NULL scene, n < 0, a NULL required pointer with n > 0, a
+ * field of the params out of range (the message names it); MCPT_E_UNSUPPORTED
+ * for n >= 2^31 / 3 or n x chunks >= 2^31; MCPT_E_INVALID for a host-only scene
+ * and for an output that overlaps an input.  n = 0 is a no-op.  A multi-device
+ * scene runs the query on devices[0].  Not offered:
+ * QuinEngine mode, a wavefront form, batches sharded over devices.
+ * Workspace, the scene's: the renders' stack spill area (run the queries on the
+ * stream of the scene's renders, or synchronize), 16 B per (ray, chunk) of
+ * partial sums, the tail samples' buffer and a work-unit counter.  After
+ * mcpt_scene_reserve_radiance(p, n) or a first call, a call that needs no more
+ * allocates nothing; growth on a capturing stream is MCPT_E_NOMEM.           */
+typedef struct {
+    uint32_t spp;          /* samples per ray this call; >= 1 */
+    uint32_t spp_offset;   /* first global sample index; spp_offset + spp <= 2^32 */
+    uint32_t spp_chunk;    /* samples per partial sum, 0 = spp */
+    int32_t  max_depth;    /* scatter events, 0..1000 */
+    float    illum;        /* emitter scale (ILLUM), finite */
+    int32_t  fresnel_kd;   /* as mcpt_render_params */
+    uint64_t seed;
+    uint32_t prev_count;   /* running mean over calls; the output is read when > 0 */
+    int32_t  lean;         /* 1: rays only are counted */
+    int32_t  workgroups;   /* scheduling only: 0 = automatic, > 0 = at most this many */
+    int32_t  ready_thresh; /* scheduling only: 0 = the megakernel's default for the layout, else 1..64 */
+} mcpt_radiance_params;
+void mcpt_radiance_params_default(mcpt_radiance_params*);   /* spp 1, max_depth 7, illum 10, fresnel_kd 1, the renders' seed */
+
+/* d_o, d_d: n*3 floats each; d_stream: n stream ids or NULL; d_radiance: n*4 floats (r, g, b, 0), read first
+ * when p->prev_count > 0.  Asynchronous on hip_stream.  p may be NULL (the defaults).  The eight counters of
+ * the call (paths and shades among them) are added to the block mcpt_trace_stats_read reports. */
+int mcpt_radiance_device(mcpt_scene*, const mcpt_radiance_params* p, int64_t n, const float* d_o, const float* d_d,
+                         const uint32_t* d_stream, float* d_radiance, void* hip_stream);
+/* host arrays, synchronous; radiance: n*3 floats (read first when p->prev_count > 0); stats may be NULL (the
+ * counters of this call; the block mcpt_trace_stats_read reports and the render stats are not touched) */
+int mcpt_radiance(mcpt_scene*, const mcpt_radiance_params* p, int64_t n, const float* o, const float* d,
+                  const uint32_t* stream, float* radiance, mcpt_render_stats* stats);
+/* allocate what a radiance query of n rays with these params needs (above) */
+int mcpt_scene_reserve_radiance(mcpt_scene*, const mcpt_radiance_params* p, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

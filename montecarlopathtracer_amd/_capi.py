@@ -111,6 +111,13 @@ class TraceParamsC(C.Structure):
                 ("refill", C.c_int32)]
 
 
+class RadianceParamsC(C.Structure):
+    _fields_ = [("spp", C.c_uint32), ("spp_offset", C.c_uint32), ("spp_chunk", C.c_uint32),
+                ("max_depth", C.c_int32), ("illum", C.c_float), ("fresnel_kd", C.c_int32), ("seed", C.c_uint64),
+                ("prev_count", C.c_uint32), ("lean", C.c_int32), ("workgroups", C.c_int32),
+                ("ready_thresh", C.c_int32)]
+
+
 TRACE_CLOSEST = 0
 TRACE_ANY = 1
 OBJ_CVMCTRACER = 0
@@ -204,6 +211,12 @@ _SIGS = {
                                 C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(RenderStats)]),
     "mcpt_trace_stats_read": (C.c_int, [_vp, C.POINTER(RenderStats)]),
     "mcpt_scene_reserve_rays": (C.c_int, [_vp]),
+    "mcpt_radiance_params_default": (None, [C.POINTER(RadianceParamsC)]),
+    "mcpt_radiance_device": (C.c_int, [_vp, C.POINTER(RadianceParamsC), C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "mcpt_radiance": (C.c_int, [_vp, C.POINTER(RadianceParamsC), C.c_int64, C.POINTER(C.c_float),
+                                C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                                C.POINTER(RenderStats)]),
+    "mcpt_scene_reserve_radiance": (C.c_int, [_vp, C.POINTER(RadianceParamsC), C.c_int64]),
 }
 
 _lib = None

@@ -239,6 +239,13 @@ struct mcpt_scene {
     // entries' (mcpt_trace_stats_read) and the synchronous host entry's
     void* rq_order = nullptr;
     void* rq_stats = nullptr;
+    // device radiance queries (mcpt_radiance_device): partial sums [chunk][ray],
+    // the tail samples and the work-unit counter (counters: rq_stats)
+    void* rad_partial = nullptr;
+    size_t rad_partial_bytes = 0;
+    void* rad_tail = nullptr;
+    size_t rad_tail_bytes = 0;
+    void* rad_small = nullptr;
 
     ~mcpt_scene() {
         if (!on_device) return;
@@ -255,7 +262,7 @@ struct mcpt_scene {
             (void)hipSetDevice(device);
         }
         for (void* p : {d_image, d_normals, ws.partial, ws.small, ws.spill, ws.fb, ws.wf, ws.tail, gather, gather_send, ad_list, ad_flags,
-                        ad_blocks, rq_order, rq_stats})
+                        ad_blocks, rq_order, rq_stats, rad_partial, rad_tail, rad_small})
             if (p) (void)hipFree(p);
         if (ad_host_n) (void)hipHostFree(ad_host_n);
         for (void* p : retired) (void)hipFree(p);
@@ -821,6 +828,9 @@ void prepare_workspace(mcpt_scene& s, Plan& pl, bool tail_split = false, int spi
     if (!s.ws.small) {
         HIP_TRY(hipMalloc(&s.ws.small, 256));
         HIP_TRY(hipMemset(s.ws.small, 0, 256));
+        // (the fill may still be in flight on the null stream, which a replica's
+        // non-blocking stream does not wait for: its kernel's counters must land after it)
+        HIP_TRY(hipStreamSynchronize(nullptr));
     }
     const size_t lanes = static_cast<size_t>(mcpt::total_lanes_for(s.gpu.image_bytes, s.cus));
     // (the wavefront's streams run extends concurrently: one spill area each)
@@ -1015,6 +1025,7 @@ void read_stats(mcpt_scene& s, mcpt_render_stats* out) {
         unsigned long long st[16];
         HIP_TRY(hipMemcpy(st, static_cast<char*>(s.ws.small) + 64, sizeof st, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemset(static_cast<char*>(s.ws.small) + 64, 0, sizeof st));
+        HIP_TRY(hipStreamSynchronize(nullptr));   // (as in prepare_workspace: before a render on a non-blocking stream)
         if (st[8] | st[9] | st[10] | st[11])   // diagnostic builds (-DMCPT_PHASE_TIMING) only
             std::fprintf(stderr, "mcpt phase cycles (sum over waves): units %llu trav %llu shade %llu burst_iters %llu "
                          "scatter %llu\n", st[8], st[9], st[10], st[11], st[12]);
@@ -1330,6 +1341,122 @@ void stats_from_counters(const unsigned long long c[8], mcpt_render_stats& st) {
     st.devices = 1;
     st.rays = c[0]; st.inner_visits = c[2]; st.leaf_visits = c[3]; st.leaf_refs = c[4];
     st.tri_tests = c[5]; st.stack_spills = c[7];
+    st.paths = c[1]; st.shades = c[6];   // (radiance queries; the hit queries leave them 0)
+}
+
+// ---- device radiance queries (render.hip radiance_kernel) -----------------------
+struct Radiance {
+    mcpt_radiance_params q;
+    uint32_t chunk;
+    uint64_t nchunks;
+};
+// The checks of a radiance query that need no device, in the header's order; p
+// resolved (NULL = the defaults)
+Radiance radiance_resolve(const mcpt_scene* s, const mcpt_radiance_params* p, int64_t n, bool ptrs) {
+    if (!s) throw mcpt::Error{MCPT_E_INVALID, "NULL scene"};
+    if (n < 0) throw mcpt::Error{MCPT_E_INVALID, "n must be >= 0"};
+    if (n && !ptrs) throw mcpt::Error{MCPT_E_INVALID, "NULL ray or result buffer"};
+    Radiance R;
+    mcpt_radiance_params& q = R.q;
+    mcpt_radiance_params_default(&q);
+    if (p) q = *p;
+    if (q.spp == 0) throw mcpt::Error{MCPT_E_INVALID, "spp must be >= 1"};
+    if (q.max_depth < 0 || q.max_depth > mcpt::kMaxDepthParam)
+        throw mcpt::Error{MCPT_E_INVALID, "max_depth must be 0..1000"};
+    if (!std::isfinite(q.illum)) throw mcpt::Error{MCPT_E_INVALID, "illum must be finite"};
+    if (q.lean != 0 && q.lean != 1) throw mcpt::Error{MCPT_E_INVALID, "lean must be 0 or 1"};
+    if (q.fresnel_kd != 0 && q.fresnel_kd != 1) throw mcpt::Error{MCPT_E_INVALID, "fresnel_kd must be 0 or 1"};
+    if (q.workgroups < 0) throw mcpt::Error{MCPT_E_INVALID, "workgroups must be >= 0"};
+    if (q.ready_thresh < 0 || q.ready_thresh > 64)
+        throw mcpt::Error{MCPT_E_INVALID, "ready_thresh must be 0 (default) or 1..64"};
+    if (uint64_t(q.spp_offset) + uint64_t(q.spp) > (uint64_t(1) << 32))
+        throw mcpt::Error{MCPT_E_INVALID, "spp_offset + spp must not pass 2^32"};
+    R.chunk = q.spp_chunk ? (q.spp_chunk < q.spp ? q.spp_chunk : q.spp) : q.spp;
+    R.nchunks = (uint64_t(q.spp) + R.chunk - 1) / R.chunk;
+    if (n >= (int64_t(1) << 31) / 3) throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many rays for one call"};
+    if (uint64_t(n) * R.nchunks >= (uint64_t(1) << 31))
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many work units (rays x chunks) for one call"};
+    if (!s->on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
+    return R;
+}
+
+// The kernel parameters of a query: a packed frame of n rays (no pixel decode
+// is run), its chunks, and the tail split of the megakernel -- the last units
+// per lane handed out one sample at a time; the workspace pointers come later
+mcpt::KernelParams radiance_plan(const mcpt_scene& s, const Radiance& R, int64_t n, uint64_t* tail_out) {
+    const mcpt_radiance_params& q = R.q;
+    mcpt::KernelParams k;
+    std::memset(&k, 0, sizeof k);
+    k.scene = s.gpu;
+    k.width = static_cast<int32_t>(n); k.height = 1;
+    k.tile = 1; k.tiles_x = static_cast<int32_t>(std::max<int64_t>(n, 1));
+    k.shard_count = 1; k.packed = 1;
+    k.npix_local = static_cast<uint32_t>(n);
+    k.spp = q.spp; k.spp_offset = q.spp_offset; k.chunk = R.chunk;
+    k.nchunks = static_cast<uint32_t>(R.nchunks);
+    k.total_units = static_cast<uint32_t>(uint64_t(n) * R.nchunks);
+    k.div_npix = mcpt::FastDiv::make(std::max<uint32_t>(k.npix_local, 1));
+    k.div_tt = mcpt::FastDiv::make(1);
+    k.div_tiles_x = mcpt::FastDiv::make(static_cast<uint32_t>(k.tiles_x));
+    k.div_tile = mcpt::FastDiv::make(1);
+    k.div_chunk = mcpt::FastDiv::make(R.chunk);
+    k.max_depth = q.max_depth;
+    k.lean = q.lean;
+    k.illum = q.illum;
+    k.fresnel_kd = q.fresnel_kd;
+    k.prev_count = q.prev_count;
+    k.mode = MCPT_MODE_CVMCTRACER;
+    k.best_init = FLT_MAX;
+    k.key = tea16(static_cast<uint32_t>(q.seed), static_cast<uint32_t>(q.seed >> 32));
+    k.ready_thresh = q.ready_thresh > 0 ? q.ready_thresh : (s.gpu.node_boxes == 1 ? 40 : 32);   // make_plan's
+    // tail split: make_plan's 4 units per lane; item indices and tail slots stay below 2^31
+    uint64_t tail = 0;
+    if (k.chunk > 1) {
+        tail = std::min<uint64_t>(4 * static_cast<uint64_t>(mcpt::total_lanes_for(s.gpu.image_bytes, s.cus)),
+                                  k.total_units);
+        while (tail && uint64_t(k.total_units - tail) + tail * k.chunk >= (uint64_t(1) << 31)) tail >>= 1;
+    }
+    k.tail_units = k.total_units - static_cast<uint32_t>(tail);
+    k.total_items = k.tail_units + static_cast<uint32_t>(tail * k.chunk);
+    *tail_out = tail;
+    return k;
+}
+
+// The query's workspace on the scene's (current) device, grown to what k needs:
+// the ray queries' counter blocks and the renders' spill area (ensure_rays),
+// the partial sums, the tail samples, the work-unit counter
+void ensure_radiance(mcpt_scene& s, mcpt::KernelParams& k, uint64_t tail, bool host_block, bool capturing) {
+    if (capturing && (!s.rq_order || !s.rq_stats || !s.rad_small))
+        throw mcpt::Error{MCPT_E_NOMEM, "the first radiance query of a scene allocates: call "
+                                        "mcpt_scene_reserve_radiance before capturing a graph"};
+    ensure_rays(s, capturing);
+    if (!s.rad_small) {
+        void* t = nullptr;
+        HIP_TRY(hipMalloc(&t, 64));
+        hipError_t e = hipMemset(t, 0, 64);
+        if (e == hipSuccess) e = mcpt::prepare_radiance(s.gpu);   // (the kernels' code object loaded now)
+        if (e != hipSuccess) {
+            (void)hipFree(t);
+            HIP_TRY(e);
+        }
+        s.rad_small = t;
+    }
+    grow_ws(s, s.rad_partial, s.rad_partial_bytes, size_t(k.total_units) * 16, capturing);
+    if (tail) grow_ws(s, s.rad_tail, s.rad_tail_bytes, size_t(tail) * k.chunk * 16, capturing);
+    k.partial = static_cast<float4*>(s.rad_partial);
+    k.tail_buf = tail ? static_cast<float4*>(s.rad_tail) : nullptr;
+    k.counter = static_cast<uint32_t*>(s.rad_small);
+    k.stats = static_cast<unsigned long long*>(s.rq_stats) + (host_block ? 8 : 0);
+    k.spill = static_cast<uint4*>(s.ws.spill);
+}
+
+void radiance_async(mcpt_scene& s, const Radiance& R, int64_t n, const float* d_o, const float* d_d,
+                    const uint32_t* d_stream, float* d_out, bool host_block, hipStream_t st) {
+    uint64_t tail = 0;
+    mcpt::KernelParams k = radiance_plan(s, R, n, &tail);
+    ensure_radiance(s, k, tail, host_block, stream_capturing(st));
+    const mcpt::RayInputs ri{d_o, d_d, d_stream};
+    HIP_TRY(mcpt::launch_radiance(k, ri, s.cus, R.q.workgroups, reinterpret_cast<float4*>(d_out), st));
 }
 
 // What mcpt_render_var[_device] asks of a render beyond mcpt_render's own
@@ -2438,6 +2565,88 @@ int mcpt_scene_reserve_rays(mcpt_scene* s) {
         DeviceGuard guard;
         set_device(*s);
         ensure_rays(*s, false);
+        return MCPT_OK;
+    });
+}
+
+void mcpt_radiance_params_default(mcpt_radiance_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof *p);
+    p->spp = 1;
+    p->max_depth = 7;                                 // CUTracer.cu:212
+    p->illum = 10.0f;                                 // ILLUM
+    p->fresnel_kd = 1;
+    p->seed = 0x4D435054ull;                          // mcpt_render_params_default's
+}
+
+int mcpt_radiance_device(mcpt_scene* s, const mcpt_radiance_params* p, int64_t n, const float* d_o, const float* d_d,
+                         const uint32_t* d_stream, float* d_radiance, void* hip_stream) {
+    return guarded([&]() -> int {
+        const Radiance R = radiance_resolve(s, p, n, d_o && d_d && d_radiance);
+        const size_t N = static_cast<size_t>(n);
+        if (ranges_overlap(d_radiance, N * 16, d_o, N * 12) || ranges_overlap(d_radiance, N * 16, d_d, N * 12) ||
+            ranges_overlap(d_radiance, N * 16, d_stream, d_stream ? N * 4 : 0))
+            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+        if (!n) return MCPT_OK;
+        set_device(*s);                   // (a multi-device scene: devices[0], the primary)
+        radiance_async(*s, R, n, d_o, d_d, d_stream, d_radiance, false, static_cast<hipStream_t>(hip_stream));
+        return MCPT_OK;
+    });
+}
+
+// rays, stream ids and the result are staged in the scene's host-render buffer
+int mcpt_radiance(mcpt_scene* s, const mcpt_radiance_params* p, int64_t n, const float* o, const float* d,
+                  const uint32_t* stream, float* radiance, mcpt_render_stats* stats) {
+    return guarded([&]() -> int {
+        const Radiance R = radiance_resolve(s, p, n, o && d && radiance);
+        const size_t N = static_cast<size_t>(n);
+        if (ranges_overlap(radiance, N * 12, o, N * 12) || ranges_overlap(radiance, N * 12, d, N * 12) ||
+            ranges_overlap(radiance, N * 12, stream, stream ? N * 4 : 0))
+            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+        mcpt_render_stats st;
+        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (n) {
+            set_device(*s);
+            ensure_buf(s->ws.fb, s->ws.fb_bytes, N * 44);
+            float* d_out = static_cast<float*>(s->ws.fb);   // (16-B aligned: first)
+            float* d_o = d_out + 4 * N;
+            float* d_d = d_o + 3 * N;
+            uint32_t* d_s = reinterpret_cast<uint32_t*>(d_d + 3 * N);
+            HIP_TRY(hipMemcpy(d_o, o, N * 12, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_d, d, N * 12, hipMemcpyHostToDevice));
+            if (stream) HIP_TRY(hipMemcpy(d_s, stream, N * 4, hipMemcpyHostToDevice));
+            std::vector<float> rgba(N * 4, 0.0f);
+            if (R.q.prev_count) {
+                for (size_t i = 0; i < N; ++i)
+                    for (int k = 0; k < 3; ++k) rgba[4 * i + k] = radiance[3 * i + k];
+                HIP_TRY(hipMemcpy(d_out, rgba.data(), N * 16, hipMemcpyHostToDevice));
+            }
+            uint64_t tail = 0;
+            mcpt::KernelParams k = radiance_plan(*s, R, n, &tail);
+            ensure_radiance(*s, k, tail, true, false);
+            HIP_TRY(hipMemset(k.stats, 0, 64));
+            const mcpt::RayInputs ri{d_o, d_d, stream ? d_s : nullptr};
+            HIP_TRY(mcpt::launch_radiance(k, ri, s->cus, R.q.workgroups, reinterpret_cast<float4*>(d_out), nullptr));
+            HIP_TRY(hipStreamSynchronize(nullptr));
+            HIP_TRY(hipMemcpy(rgba.data(), d_out, N * 16, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(c, k.stats, 64, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < N; ++i)
+                for (int k3 = 0; k3 < 3; ++k3) radiance[3 * i + k3] = rgba[4 * i + k3];
+        }
+        stats_from_counters(c, st);
+        if (stats) *stats = st;
+        return MCPT_OK;
+    });
+}
+
+int mcpt_scene_reserve_radiance(mcpt_scene* s, const mcpt_radiance_params* p, int64_t n) {
+    return guarded([&]() -> int {
+        const Radiance R = radiance_resolve(s, p, n, true);
+        DeviceGuard guard;
+        set_device(*s);
+        uint64_t tail = 0;
+        mcpt::KernelParams k = radiance_plan(*s, R, n, &tail);
+        ensure_radiance(*s, k, tail, false, false);
         return MCPT_OK;
     });
 }

@@ -59,8 +59,14 @@ __device__ __forceinline__ void store_part(const KernelParams& kp, uint32_t id, 
 // kp by value: by reference the inlined body compiled to 2 to 23 instructions
 // more or fewer in the LDS variants of path_kernel; by value every path_kernel keeps
 // its instruction count, instruction mix and registers (scripts/isa_diff.py).
-template <bool IN_LDS, int S, int BLOCK, bool DBG, bool QE, bool COUNT, bool LIST>
-__device__ __forceinline__ void path_body(const KernelParams kp) {
+// RAYS: the radiance query (mcpt_radiance_device) -- a unit's index v is a ray of
+// the caller's buffers ri (kept in px), a frame of kp.npix_local rays: a lane
+// starting a path loads its ray and stream id instead of forming a primary ray,
+// and still spends the two uniforms of a render's jitter (CVMCTracer mode).
+// ri by value and unused without RAYS: every other kernel keeps its code.
+template <bool IN_LDS, int S, int BLOCK, bool DBG, bool QE, bool COUNT, bool LIST, bool RAYS = false>
+__device__ __forceinline__ void path_body(const KernelParams kp, const RayInputs ri = RayInputs{nullptr, nullptr, nullptr}) {
+    static_assert(!RAYS || (!QE && !LIST && !DBG), "the radiance query is CVMCTracer mode over the caller's rays");
     static_assert((BLOCK & (BLOCK - 1)) == 0, "stack slot addresses (slot_of) mask by a power-of-two block");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = (int)threadIdx.x;
@@ -230,7 +236,7 @@ __device__ __forceinline__ void path_body(const KernelParams kp) {
                     part = v3(0, 0, 0);
                     if (s >= s_end) {
                         // sample past spp in a ragged last chunk: nothing to do, take another item
-                    } else if (unit_pixel(kp, LIST ? kp.pixel_list[v] : v, px, py)) {
+                    } else if (RAYS ? (px = (int)v, true) : unit_pixel(kp, LIST ? kp.pixel_list[v] : v, px, py)) {
                         newp = true;
                         mode = kReady;
                     } else {
@@ -253,7 +259,18 @@ __device__ __forceinline__ void path_body(const KernelParams kp) {
             }
         } else {
             const bool fres = scat && geoms[gi].Tr > 0;
-            if (newp) sd = path_seed(kp, (uint32_t)py * (uint32_t)kp.width + (uint32_t)px, s);
+            if constexpr (RAYS) {
+                // the caller's ray, used as given, and its stream id in the pixel's place
+                if (newp) {
+                    const uint32_t v = (uint32_t)px;
+                    const uint32_t id = ri.stream ? ri.stream[v] : v;
+                    r.o = v3(ri.o[3 * v], ri.o[3 * v + 1], ri.o[3 * v + 2]);
+                    r.d = v3(ri.d[3 * v], ri.d[3 * v + 1], ri.d[3 * v + 2]);
+                    sd = path_seed(kp, id, s);
+                }
+            } else {
+                if (newp) sd = path_seed(kp, (uint32_t)py * (uint32_t)kp.width + (uint32_t)px, s);
+            }
             // the lane's next two uniforms (a Fresnel scatter consumes only the first):
             // the primary ray's jitter (CUTracer.cu:189-190) or the sampler's draws
             float u1 = 0.0f, u2 = 0.0f;
@@ -266,11 +283,17 @@ __device__ __forceinline__ void path_body(const KernelParams kp) {
             }
             V3 vec = v3(0, 0, 0);
             if (scat) vec = shading_normal_raw(sc.normals, r.htri, r.hbeta, r.hgamma);
-            if (newp) vec = primary_dir_raw(kp, px, py, u1, u2);
-            if (scat | newp) normalize_cu(vec);
+            if constexpr (RAYS) {
+                if (scat) normalize_cu(vec);
+            } else {
+                if (newp) vec = primary_dir_raw(kp, px, py, u1, u2);
+                if (scat | newp) normalize_cu(vec);
+            }
             if (newp) {
-                r.d = vec;
-                r.o = eye;
+                if constexpr (!RAYS) {
+                    r.d = vec;
+                    r.o = eye;
+                }
                 color = v3(1, 1, 1);
                 depth = 0;
                 if constexpr (COUNT) c.paths++;
@@ -340,6 +363,15 @@ __global__ void __launch_bounds__(BLOCK, (!IN_LDS && COUNT) ? 4 : 1) list_kernel
     path_body<IN_LDS, S, BLOCK, false, false, COUNT, true>(kp);
 }
 
+// Radiance queries (mcpt_radiance_device): the same body over the rays of a
+// device buffer, CVMCTracer mode, lean and counting; the LDS layout with S = 4
+// (every image that fits in LDS fits beside four stack entries per lane)
+template <bool IN_LDS, int S, int BLOCK, bool COUNT>
+__global__ void __launch_bounds__(BLOCK, (!IN_LDS && COUNT) ? 4 : 1) radiance_kernel(const KernelParams kp,
+                                                                                   const RayInputs ri) {
+    path_body<IN_LDS, S, BLOCK, false, false, COUNT, false, true>(kp, ri);
+}
+
 // running mean of a pixel (CUTracer.cu:214-217; QE gamma-space, rtx.hlsl:401-402):
 // the old framebuffer value pv (read only when prev_count > 0) and this call's mean
 __device__ __forceinline__ float4 running_mean(float4 pv, V3 mean, uint32_t prev_count, int32_t mode) {
@@ -382,6 +414,31 @@ __global__ void __launch_bounds__(256) reduce_kernel(const KernelParams kp, floa
     }
     const bool old = kp.prev_count != 0;
     fb[idx] = running_mean(old ? fb[idx] : make_float4(0, 0, 0, 0), mean, kp.prev_count, kp.mode);
+}
+
+// the radiance query's reduction: ray v's partial sums in chunk order -> mean ->
+// linear running mean -> out[v] (reduce_kernel without the pixel decode)
+__global__ void __launch_bounds__(256) radiance_reduce_kernel(const KernelParams kp, float4* __restrict__ out) {
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= kp.npix_local) return;
+    V3 sum = v3(0, 0, 0);
+    for (uint32_t c = 0; c < kp.nchunks; c++) {
+        const uint32_t u = c * kp.npix_local + v;
+        V3 pc;
+        if (u >= kp.tail_units) {   // tail split: the unit's samples, in sample order
+            const float4* tb = kp.tail_buf + (size_t)(u - kp.tail_units) * kp.chunk;
+            const uint32_t n = min(kp.chunk, kp.spp - c * kp.chunk);
+            pc = v3(0, 0, 0);
+            for (uint32_t j = 0; j < n; j++) pc = vadd(pc, v3(tb[j].x, tb[j].y, tb[j].z));
+        } else {
+            const float4 p = kp.partial[u];
+            pc = v3(p.x, p.y, p.z);
+        }
+        sum = vadd(sum, pc);
+    }
+    const V3 mean = vdiv(sum, (float)kp.spp);
+    const bool old = kp.prev_count != 0;
+    out[v] = running_mean(old ? out[v] : make_float4(0, 0, 0, 0), mean, kp.prev_count, 0);
 }
 
 // multi-device gather: shard r's packed means -> row-major running mean
@@ -506,6 +563,60 @@ hipError_t launch_render_list(const KernelParams& kp_in, int cus, hipStream_t st
     if (ev1 && (e = hipEventRecord(ev1, st)) != hipSuccess) return e;
     if (variant_out) *variant_out = v.variant;
     return e;
+}
+
+namespace {
+template <bool IN_LDS, int S, int BLOCK>
+hipError_t launch_rad(const KernelParams& kp, const RayInputs& ri, uint32_t grid, size_t lds, hipStream_t st) {
+    auto kern = kp.lean ? radiance_kernel<IN_LDS, S, BLOCK, false> : radiance_kernel<IN_LDS, S, BLOCK, true>;
+    return launch_dyn_lds(kern, dim3(grid), dim3(BLOCK), lds, st, kp, ri);
+}
+template <bool IN_LDS, int S, int BLOCK>
+hipError_t prepare_rad(size_t lds) {
+    hipError_t e = set_dyn_lds(radiance_kernel<IN_LDS, S, BLOCK, false>, lds);
+    if (e == hipSuccess) e = set_dyn_lds(radiance_kernel<IN_LDS, S, BLOCK, true>, lds);
+    return e;
+}
+constexpr int kRadLdsS = 4;
+}  // namespace
+
+// The scene's two radiance kernels resolved on the current device (part of the
+// reserve: the runtime loads a code object at the first use of one of its kernels)
+hipError_t prepare_radiance(const GpuScene& sc) {
+    if (sc.node_boxes || lds_bytes_in_lds(sc.image_bytes, kRadLdsS) > kMaxLds)
+        return prepare_rad<false, 8, kGlobalBlock>(lds_bytes_global(8, false));
+    return prepare_rad<true, kRadLdsS, kLdsBlock>(lds_bytes_in_lds(sc.image_bytes, kRadLdsS));
+}
+
+// Persistent workgroups as the megakernel's, but no more than the work feeds:
+// at least kRadMinUnits work items each (the ray queries' measured floor)
+uint32_t radiance_grid(const GpuScene& sc, uint64_t items, int cus, int max_workgroups) {
+    const bool in_lds = !sc.node_boxes && lds_bytes_in_lds(sc.image_bytes, kRadLdsS) <= kMaxLds;
+    uint64_t wg = in_lds ? (uint64_t)cus : (uint64_t)cus * kGlobalBlocksPerCu;   // (the spill area's lanes)
+    if (max_workgroups > 0 && (uint64_t)max_workgroups < wg) wg = (uint64_t)max_workgroups;
+    const uint64_t fed = (items + kRadMinUnits - 1) / kRadMinUnits;
+    if (fed < wg) wg = fed;
+    return (uint32_t)(wg < 1 ? 1 : wg);
+}
+
+// memset counter, radiance kernel, the query's reduce kernel; kp as make_plan's
+// for a frame of n = kp.npix_local rays (total_units = n x nchunks)
+hipError_t launch_radiance(const KernelParams& kp_in, const RayInputs& ri, int cus, int max_workgroups,
+                           float4* out, hipStream_t st) {
+    KernelParams kp = kp_in;
+    if (!kp.npix_local) return hipSuccess;
+    if (kp.mode != 0 || kp.unit_counters || kp.pixel_list || !ri.o || !ri.d) return hipErrorInvalidValue;
+    kp.total_lanes = (uint32_t)total_lanes_for(kp.scene.image_bytes, cus);
+    hipError_t e = hipMemsetAsync(kp.counter, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    const uint32_t grid = radiance_grid(kp.scene, kp.total_items, cus, max_workgroups);
+    if (kp.scene.node_boxes || lds_bytes_in_lds(kp.scene.image_bytes, kRadLdsS) > kMaxLds)
+        e = launch_rad<false, 8, kGlobalBlock>(kp, ri, grid, lds_bytes_global(8, false), st);
+    else
+        e = launch_rad<true, kRadLdsS, kLdsBlock>(kp, ri, grid, lds_bytes_in_lds(kp.scene.image_bytes, kRadLdsS), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(radiance_reduce_kernel, dim3((kp.npix_local + 255u) / 256u), dim3(256), 0, st, kp, out);
+    return hipGetLastError();
 }
 
 #ifdef MCPT_PHASE_TIMING

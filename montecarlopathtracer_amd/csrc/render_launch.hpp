@@ -271,6 +271,19 @@ struct KernelParams {
     const uint32_t* pixel_list;
 };
 
+// Radiance queries (mcpt_radiance_device, render.hip radiance_kernel): the
+// caller's rays, origins / directions as 3 floats each (QueryParams' layout),
+// and the optional RNG stream id of each ray (NULL: the ray's index).  A kernel
+// argument of its own, behind KernelParams: no field an existing kernel reads moves.
+struct RayInputs {
+    const float* o;
+    const float* d;
+    const uint32_t* stream;
+};
+// fewest work items (ray, chunk) a workgroup of the automatic grid gets, so the
+// grid shrinks with the work (the ray queries' floor, rayquery_launch.hpp)
+constexpr uint32_t kRadMinUnits = 64;
+
 // Multi-device gather (capi.cpp render_multi): shard r of `nshards` wrote the
 // plain means of its owned tiles, packed tile-major, to src[r * slot ...]
 // (peer-copied to the primary device); gather_kernel unpermutes them into the
@@ -424,6 +437,12 @@ hipError_t launch_render(const KernelParams& kp, int cus, hipStream_t st, hipEve
 hipError_t launch_render_list(const KernelParams& kp, int cus, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
                               int* variant_out);
 hipError_t launch_reduce(const KernelParams& kp, float4* fb, hipStream_t st);
+// radiance query: memset counter, radiance kernel over kp.npix_local rays, the
+// query's own reduce into out[ray]; workgroups as radiance_grid says
+hipError_t prepare_radiance(const GpuScene& sc);
+uint32_t radiance_grid(const GpuScene& sc, uint64_t items, int cus, int max_workgroups);
+hipError_t launch_radiance(const KernelParams& kp, const RayInputs& ri, int cus, int max_workgroups, float4* out,
+                           hipStream_t st);
 hipError_t launch_gather(const GatherParams& g, hipStream_t st);
 hipError_t launch_query(const QueryParams& q, hipStream_t st);
 #ifdef MCPT_PHASE_TIMING

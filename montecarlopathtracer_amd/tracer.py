@@ -450,6 +450,46 @@ class Scene:
         """Allocate what the ray queries need (mcpt_scene_reserve_rays): later queries allocate nothing."""
         check(lib().mcpt_scene_reserve_rays(self.handle))
 
+    def radiance_device(self, n: int, o_ptr: int, d_ptr: int, out_ptr: int, stream_ids_ptr: int = 0,
+                        stream_ptr: int = 0, **params):
+        """Path-traced radiance along n rays in device memory (mcpt_radiance_device), asynchronous
+        on the stream: o / d (n, 3) float32, used as given; out (n, 4) float32 = the mean of spp
+        samples (r, g, b, 0), read first when prev_count > 0; stream ids (n,) uint32, optional
+        (the ray's index): the id takes the pixel's place in the RNG seed, so a render's primary
+        rays with their pixel indices give that render's samples.  CVMCTracer mode.  params: the
+        fields of ``radiance_params``.  Counted in ``trace_stats``.  Run it on the stream of the
+        scene's renders, or synchronize."""
+        check(lib().mcpt_radiance_device(self.handle, C.byref(radiance_params(**params)), int(n), C.c_void_p(o_ptr),
+                                         C.c_void_p(d_ptr), C.c_void_p(stream_ids_ptr), C.c_void_p(out_ptr),
+                                         C.c_void_p(stream_ptr)))
+
+    def radiance(self, o: np.ndarray, d: np.ndarray, stream_ids=None, prev=None, **params):
+        """Radiance along host rays (mcpt_radiance), synchronous: ((n, 3) float32, counters of this
+        call).  prev: the earlier mean the running mean continues (with prev_count > 0)."""
+        o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise McptError(-1, "o and d must have the same shape")
+        n = o.shape[0]
+        ids = None
+        if stream_ids is not None:
+            ids = np.ascontiguousarray(stream_ids, np.uint32).reshape(-1)
+            if ids.shape[0] != n:
+                raise McptError(-1, "stream_ids must hold one value per ray")
+        out = np.zeros((n, 3), np.float32)
+        if prev is not None:
+            out[...] = np.asarray(prev, np.float32).reshape(n, 3)
+        st = RenderStats()
+        check(lib().mcpt_radiance(self.handle, C.byref(radiance_params(**params)), n, _fptr(o), _fptr(d),
+                                  ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None,
+                                  _fptr(out), C.byref(st)))
+        return out, st.as_dict()
+
+    def reserve_radiance(self, n: int, **params):
+        """Allocate what a radiance query of n rays with these params needs
+        (mcpt_scene_reserve_radiance): a later query that needs no more allocates nothing."""
+        check(lib().mcpt_scene_reserve_radiance(self.handle, C.byref(radiance_params(**params)), int(n)))
+
     def render_unit_counters(self, params: RenderParams):
         """Synchronous render returning (fb, per-unit counters (units, 4): rays, inner, leaf, tests)."""
         n = params.output_pixels()
@@ -601,6 +641,19 @@ def adaptive_params(max_passes: int = 0, min_passes: int = 0, threshold: float =
 
 
 TRACE_KINDS = {"closest": _capi.TRACE_CLOSEST, "any": _capi.TRACE_ANY}
+
+
+def radiance_params(**kw) -> "_capi.RadianceParamsC":
+    """mcpt_radiance_params: the library's defaults (spp 1, max_depth 7, illum 10, fresnel_kd 1,
+    the renders' seed), then the fields given by name."""
+    p = _capi.RadianceParamsC()
+    lib().mcpt_radiance_params_default(C.byref(p))
+    names = {n for n, _ in _capi.RadianceParamsC._fields_}
+    for k, v in kw.items():
+        if k not in names:
+            raise McptError(-1, f"unknown radiance parameter {k!r}")
+        setattr(p, k, float(v) if k == "illum" else int(v))
+    return p
 
 
 def trace_params(kind="closest", t_max: float = 0.0, lean: bool = False, workgroups: int = 0,
