@@ -16,7 +16,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, os.environ.get("MCPT_LIB_NAME", "libmcpt.so"))
-SOURCES = ["host_model.cpp", "kd_cache.cpp", "capi.cpp", "render.hip", "wavefront.hip", "wavefront_primary.hip",
+SOURCES = ["host_model.cpp", "kd_cache.cpp", "capi.cpp", "scene_image.cpp", "plan.cpp", "render_host.cpp", "queries.cpp",
+           "render.hip", "wavefront.hip", "wavefront_primary.hip",
            "aov.hip", "denoise.hip", "variance.hip", "denoise_var.hip", "adaptive.hip", "rayquery.hip"]
 # per-source code generation (wavefront_primary.hip: the bounce-0 packet extend's
 # wave-uniform control flow as scalar branches; render.hip: GVN hoisting,
@@ -32,7 +33,7 @@ SOURCE_FLAGS = {"wavefront_primary.hip": ["-mllvm", "-structurizecfg-skip-unifor
                 # the ray queries' kernel is the extend's loop: it starts from the extend's flags
                 "rayquery.hip": _WF_FLAGS,
                 "render.hip": ["-mllvm", "-enable-gvn-hoist", "-mllvm", "-unroll-threshold=2000"]}
-HEADERS = ["host_model.hpp", "mcpt_device.hpp", "render_launch.hpp", "trace_device.hpp", "half_box.hpp",
+HEADERS = ["capi_internal.hpp", "staging.hpp", "host_model.hpp", "mcpt_device.hpp", "render_launch.hpp", "trace_device.hpp", "half_box.hpp",
            "aov_device.hpp", "aov_launch.hpp", "variance_launch.hpp", "adaptive_launch.hpp", "partial_sum.hpp", "rayquery_launch.hpp",
            "wf_device.hpp", "wf_primary_body.hpp"]
 ARCH = os.environ.get("MCPT_OFFLOAD_ARCH", "gfx950")

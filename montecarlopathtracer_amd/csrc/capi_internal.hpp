@@ -1,0 +1,249 @@
+// capi_internal.hpp -- what the host translation units of the C ABI share
+// (include/mcpt.h): the opaque handles, the render plan and workspace, the error
+// plumbing and the functions one unit defines and another calls.
+//   capi.cpp          init, errors, parameter defaults, the denoisers
+//   scene_image.cpp   models, the device image, scene creation and teardown
+//   plan.cpp          the render plan, its workspace, mcpt_plan_query, shards
+//   render_host.cpp   renders: one device, several, reserve, variance, adaptive, feature buffers
+//   queries.cpp       ray and radiance queries
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>   // types and prototypes only: librccl is loaded on first use (render_host.cpp rccl())
+
+#include <cstdint>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/mcpt.h"
+#include "host_model.hpp"
+#include "render_launch.hpp"
+#include "staging.hpp"
+
+struct mcpt_model {
+    mcpt::ObjModel m;
+};
+
+namespace mcpt::host {
+
+// the calling thread's last error (mcpt_last_error); returns code
+int fail(int code, const std::string& msg);
+// mcpt_init's device list for scenes created later on this thread (empty: the
+// current device only), and whether peer access is enabled between every pair
+// of its distinct devices
+extern thread_local std::vector<int> g_devices;
+extern thread_local bool g_peer_ok;
+
+#define HIP_TRY(expr)                                                                   \
+    do {                                                                                \
+        hipError_t e_ = (expr);                                                         \
+        if (e_ != hipSuccess)                                                           \
+            throw mcpt::Error{e_ == hipErrorOutOfMemory ? MCPT_E_NOMEM : MCPT_E_DEVICE,   \
+                              std::string(#expr) + ": " + hipGetErrorString(e_)};       \
+    } while (0)
+
+template <typename F>
+int guarded(F&& f) {
+    try {
+        return f();
+    } catch (const mcpt::Error& e) {
+        return fail(e.code, e.msg);
+    } catch (const std::bad_alloc&) {
+        return fail(MCPT_E_NOMEM, "out of host memory");
+    } catch (const std::exception& e) {
+        return fail(MCPT_E_INVALID, e.what());
+    }
+}
+
+// a device allocation a scene owns, and how much of it there is
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+// a device allocation freed on every exit path unless released to an owner
+struct TempDev {
+    void* p = nullptr;
+    TempDev() = default;
+    explicit TempDev(size_t bytes) { alloc(bytes); }
+    TempDev(const TempDev&) = delete;
+    TempDev& operator=(const TempDev&) = delete;
+    ~TempDev() {
+        if (p) (void)hipFree(p);
+    }
+    void alloc(size_t bytes) { HIP_TRY(hipMalloc(&p, bytes ? bytes : 16)); }
+    void* release() {
+        void* q = p;
+        p = nullptr;
+        return q;
+    }
+};
+
+struct Workspace {
+    DevBuf partial;
+    DevBuf small;        // counter (16 B) + stats (64 B)
+    DevBuf spill;
+    DevBuf fb;           // mcpt_render staging framebuffer
+    DevBuf wf;           // wavefront queues / path state (one allocation)
+    DevBuf tail;         // megakernel tail split: one float4 per tail sample
+};
+
+struct Timing {
+    hipEvent_t e[3];
+};
+
+// Restores the calling thread's current HIP device on every exit path
+struct DeviceGuard {
+    int prev = -1;
+    DeviceGuard() { (void)hipGetDevice(&prev); }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+}  // namespace mcpt::host
+
+struct mcpt_scene {
+    mcpt::HostScene hs;
+    bool on_device = false;
+    int device = -1;
+    int cus = 0;
+    std::vector<unsigned char> image;   // host copy of the device image
+    std::vector<uint32_t> tri_order;    // image triangle slot -> kd id
+    mcpt::GpuScene gpu{};
+    // terminal cull: emitter boxes as box_hit reads them (fp16 rounded outward);
+    // n_cull_boxes == 0: the scene does not allow the cull (host_model.hpp)
+    uint32_t n_cull_boxes = 0;
+    uint32_t cull_box[mcpt::kMaxCullBoxes][3] = {};
+    float cull_gain = 0.0f;             // the largest |Kd| or |Ks| component (finite when there are boxes)
+    // miss cull: occluder boxes {lo xyz, hi xyz}; n_miss_boxes == 0: none for the scene (host_model.hpp)
+    uint32_t n_miss_boxes = 0;
+    float miss_box[mcpt::kMaxMissBoxes][6] = {};
+    // direct lists: kd id -> its box; triangles per box; the small boxes' counts
+    // (4 bits each) and lists as the kernels take them (render_launch.hpp WfParams)
+    std::vector<int32_t> tri_box;
+    uint32_t box_tris[mcpt::kMaxMissBoxes] = {};
+    uint32_t direct_counts = 0;
+    uint32_t direct_list[mcpt::kMaxMissBoxes * 16] = {};
+    uint64_t direct_rays = 0;           // of the stats record last read
+    uint64_t extend_rays = 0;           // likewise: the rays the secondary extends took
+    uint64_t clipped_rays = 0;          // likewise: the rays an extend started with a selector (clip walk)
+    mcpt::host::DevBuf d_image, d_normals;
+    mcpt::host::Workspace ws;
+    std::vector<mcpt::host::Timing> pending, free_timing;
+    // events of renders captured into a graph: recorded by the graph's replays,
+    // never read (a captured render has no time of its own) nor recycled
+    // (created once, mcpt_scene_reserve)
+    mcpt::host::Timing capture_timing{};
+    bool has_capture_timing = false;
+    int last_variant = 0;
+    uint64_t renders = 0;
+    // wavefront queue bytes set aside by mcpt_scene_reserve: later renders with a
+    // default batch never grow past them (no hipMalloc inside a stream capture)
+    size_t wf_reserved = 0;
+    // set by mcpt_scene_reserve: from then on a workspace buffer that has to grow
+    // is retired (kept until the scene is destroyed), never freed, so a HIP graph
+    // captured against the reservation keeps valid pointers (grow_ws)
+    bool reserved = false;
+    std::vector<void*> retired;
+    // multi-device scene (mcpt_init with n > 1): the primary (this object, on
+    // devices[0]) owns one replica per further device -- the same image and
+    // normals, its own workspace, a non-blocking stream and a completion event --
+    // and the gather buffer its shards are peer-copied into
+    std::vector<std::unique_ptr<mcpt_scene>> replicas;
+    hipStream_t stream = nullptr;       // replicas: the shard's stream
+    hipEvent_t done = nullptr;          // replicas: shard rendered and copied
+    hipEvent_t start = nullptr;         // primary: inputs ready on the caller's stream
+    mcpt::host::DevBuf gather;
+    // wavefront: a second stream for every other batch, forked from and joined
+    // back into the caller's stream (created on first use)
+    hipStream_t wf_stream[mcpt::kMaxWfStreams] = {};   // [0] unused (the caller's)
+    hipEvent_t wf_fork = nullptr, wf_join[mcpt::kMaxWfStreams] = {};
+    bool peer_access = true;            // multi-device: peer access enabled between every device pair
+    // multi-device, gather = RCCL: one communicator per device of the list
+    // (ncclCommInitAll, rank r = device r of the list) and rank 0's send buffer
+    std::vector<ncclComm_t> comms;
+    mcpt::host::DevBuf gather_send;
+    // adaptive sampling (mcpt_render_adaptive): the pixel list, the `over` flags,
+    // the compaction's block counts and wave ballots, and the pinned word the
+    // list's length is copied to each pass
+    mcpt::host::DevBuf ad_list, ad_flags, ad_blocks;
+    uint32_t* ad_host_n = nullptr;
+    // device ray queries (mcpt_trace_device, mcpt_occluded_device): tri_order on
+    // the device, and the queries' own counters -- two 64-B blocks, the device
+    // entries' (mcpt_trace_stats_read) and the synchronous host entry's
+    mcpt::host::DevBuf rq_order, rq_stats;
+    // device radiance queries (mcpt_radiance_device): partial sums [chunk][ray],
+    // the tail samples and the work-unit counter (counters: rq_stats)
+    mcpt::host::DevBuf rad_partial, rad_tail, rad_small;
+
+    // every device buffer of the scene: what the destructor frees (a new buffer
+    // is declared above and listed here)
+    std::vector<mcpt::host::DevBuf*> buffers() {
+        return {&d_image, &d_normals, &ws.partial, &ws.small, &ws.spill, &ws.fb, &ws.wf, &ws.tail, &gather, &gather_send,
+                &ad_list, &ad_flags, &ad_blocks, &rq_order, &rq_stats, &rad_partial, &rad_tail, &rad_small};
+    }
+    ~mcpt_scene();   // scene_image.cpp
+};
+
+namespace mcpt::host {
+
+struct Plan {
+    mcpt::KernelParams kp;
+    size_t out_pixels;
+    bool capturing = false;      // the render's stream is capturing a graph: nothing may be allocated
+    int pipeline;
+    int wf_streams;              // wavefront streams (wavefront_streams)
+    uint32_t wf_capacity;        // paths per wavefront batch
+    bool wf_batch_explicit;      // the caller asked for this batch (not shrunk to fit memory)
+    int32_t wf_sort;             // wavefront material sort (mcpt_render_params::wf_sort)
+    int32_t wf_refill;           // idle lanes before an extend wave refills
+    uint32_t wf_group_shift;     // global-memory scenes: paths dealt to segments in groups of 2^k
+    int64_t tail_per_lane;       // megakernel tail split: units per lane (< 0 off)
+    int64_t tail_exact;          // megakernel tail split: exact units (> 0 overrides)
+    uint64_t wf_mem_limit;       // mcpt_render_params::wf_mem_limit
+    uint64_t work;               // paths of the render
+    // streams whose extends run concurrently: one spill area and one queue set each
+    int sets() const { return pipeline == MCPT_PIPELINE_WAVEFRONT ? wf_streams : 1; }
+};
+
+// a render planned with its workspace in place (prepare_render): wf[0 .. pl.sets())
+// are the wavefront's per-stream parameters, unused by the megakernel
+struct Prepared {
+    Plan pl;
+    mcpt::WfParams wf[mcpt::kMaxWfStreams];
+};
+
+inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + nb && y < x + na;
+}
+
+// ---- plan.cpp ---------------------------------------------------------------
+void ensure_buf(DevBuf& b, size_t need);
+void grow_ws(mcpt_scene& s, DevBuf& b, size_t need, bool capturing);
+void set_device(const mcpt_scene& s);
+bool stream_capturing(hipStream_t st);
+uint32_t tea16(uint32_t v0, uint32_t v1);
+int ready_thresh_for(const mcpt_scene& s, int32_t asked);
+// lanes the persistent kernels launch on the scene's device: they index the spill area
+size_t launched_lanes(const mcpt_scene& s);
+constexpr size_t kSpillEntries = 32;   // stack entries per lane (build_image caps the KD depth at 32), 16 B each
+constexpr int64_t kTailPerLane = 4;    // the tail split's default units per lane (make_plan)
+size_t spill_bytes(const mcpt_scene& s, int sets);
+void grow_spill(mcpt_scene& s, int sets, bool capturing);
+uint64_t tail_split(uint64_t lanes, int64_t per_lane, int64_t exact, uint32_t total_units, uint32_t chunk);
+uint64_t tail_units_for(const mcpt_scene& s, const Plan& pl);
+Plan make_plan(const mcpt_scene& s, const mcpt_render_params* p);
+void fit_wavefront(const mcpt_scene& s, Plan& pl);
+void prepare_workspace(mcpt_scene& s, Plan& pl, bool tail_split = false, int spill_sets = 1);
+uint32_t* tile_classes(const mcpt_scene& s);
+void prepare_render(mcpt_scene& s, const mcpt_render_params* p, bool capturing, bool unit_counters, Prepared& out);
+bool multi_device(const mcpt_scene& s, const mcpt_render_params* p, const uint32_t* d_unit_counters);
+mcpt_render_params shard_params(const mcpt_render_params& p, int n, int r);
+
+// ---- render_host.cpp ----------------------------------------------------------
+void destroy_comms(mcpt_scene& s);
+
+}  // namespace mcpt::host

@@ -89,7 +89,7 @@ void pack(const std::vector<KdNode>& nodes, std::vector<uint32_t>& words) {
     }
 }
 
-// Structure the consumers rely on: capi.cpp device_order/build_image read
+// Structure the consumers rely on: scene_image.cpp device_order/build_image read
 // nodes[left + 1] as the right sibling and write node_new[left + 1]; the
 // traversal's stack spill area holds 32 entries per lane (the builder's depth
 // cap, KDTree.hpp:103-106).  So: every inner node's children are the pair

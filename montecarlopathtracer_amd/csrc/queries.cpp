@@ -1,0 +1,413 @@
+// queries.cpp -- the ray entries of the C ABI (include/mcpt.h): closest-hit and
+// any-hit queries over ray buffers (rayquery.hip), path-traced radiance over
+// ray buffers (render.hip radiance_kernel), and mcpt_intersect on the older
+// closest-hit kernel the ray-query tests compare against.
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+
+#include "capi_internal.hpp"
+#include "rayquery_launch.hpp"
+
+using namespace mcpt::host;
+
+namespace {
+
+// ---- device ray queries (rayquery.hip) ----------------------------------------
+// The checks of a ray query that need no device, in the header's order; p
+// resolved (NULL = the defaults).  `closest`: mcpt_trace_device (kind is read).
+mcpt_trace_params trace_resolve(const mcpt_scene* s, const mcpt_trace_params* p, int64_t n, bool ptrs, bool closest) {
+    if (!s) throw mcpt::Error{MCPT_E_INVALID, "NULL scene"};
+    if (n < 0) throw mcpt::Error{MCPT_E_INVALID, "n must be >= 0"};
+    if (n && !ptrs) throw mcpt::Error{MCPT_E_INVALID, "NULL ray or result buffer"};
+    mcpt_trace_params q;
+    mcpt_trace_params_default(&q);
+    if (p) q = *p;
+    if (closest && q.kind != MCPT_TRACE_CLOSEST && q.kind != MCPT_TRACE_ANY)
+        throw mcpt::Error{MCPT_E_INVALID, "kind must be MCPT_TRACE_CLOSEST or MCPT_TRACE_ANY"};
+    if (!(q.t_max >= 0.0f)) throw mcpt::Error{MCPT_E_INVALID, "t_max must be >= 0 (0 = FLT_MAX)"};
+    if (q.lean != 0 && q.lean != 1) throw mcpt::Error{MCPT_E_INVALID, "lean must be 0 or 1"};
+    if (q.workgroups < 0) throw mcpt::Error{MCPT_E_INVALID, "workgroups must be >= 0"};
+    if (q.refill < 0 || q.refill > 64) throw mcpt::Error{MCPT_E_INVALID, "refill must be 0 (default) or 1..64"};
+    if (n >= (int64_t(1) << 31) / 3) throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many rays for one call"};
+    if (closest && q.kind == MCPT_TRACE_ANY)
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "kind MCPT_TRACE_ANY reports a flag, not a triangle: "
+                                              "call mcpt_occluded_device"};
+    if (!s->on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
+    if (q.t_max == 0.0f) q.t_max = FLT_MAX;
+    return q;
+}
+
+// What the ray queries need on the scene's (current) device: tri_order, the
+// counter blocks and the renders' stack spill area.  Nothing once they exist.
+void ensure_rays(mcpt_scene& s, bool capturing) {
+    if (capturing && (!s.rq_order.p || !s.rq_stats.p))
+        throw mcpt::Error{MCPT_E_NOMEM, "the first ray query of a scene allocates: call mcpt_scene_reserve_rays "
+                                        "before capturing a graph"};
+    grow_spill(s, 1, capturing);
+    if (!s.rq_order.p) {
+        const size_t bytes = s.tri_order.size() * 4;
+        TempDev t(bytes);
+        if (bytes) HIP_TRY(hipMemcpy(t.p, s.tri_order.data(), bytes, hipMemcpyHostToDevice));
+        s.rq_order.p = t.release();
+    }
+    if (!s.rq_stats.p) {
+        TempDev t(128);
+        HIP_TRY(hipMemset(t.p, 0, 128));
+        HIP_TRY(mcpt::prepare_rayquery(s.gpu));   // (the kernels' code object loaded now)
+        s.rq_stats.p = t.release();
+    }
+}
+
+// One query on st: closest hit (d_occ NULL) or any hit.  host_block: count
+// into the host entry's counter block.
+void rays_async(mcpt_scene& s, const mcpt_trace_params& q, int64_t n, const float* d_o, const float* d_d,
+                const float* d_t_max, int32_t* d_tri, float* d_hit, uint8_t* d_occ, bool host_block, hipStream_t st) {
+    ensure_rays(s, stream_capturing(st));
+    mcpt::RayQueryParams rq{};
+    rq.scene = s.gpu;
+    rq.o = d_o;
+    rq.d = d_d;
+    rq.t_max = d_t_max;
+    rq.tri = d_tri;
+    rq.hit = d_hit;
+    rq.occ = d_occ;
+    rq.tri_order = static_cast<const uint32_t*>(s.rq_order.p);
+    rq.spill = static_cast<uint4*>(s.ws.spill.p);
+    rq.spill_stride = static_cast<uint32_t>(launched_lanes(s));
+    rq.stats = static_cast<unsigned long long*>(s.rq_stats.p) + (host_block ? 8 : 0);
+    rq.n = static_cast<uint32_t>(n);
+    rq.refill = q.refill;
+    rq.best_init = q.t_max;
+    HIP_TRY(mcpt::launch_rayquery(rq, d_occ != nullptr, q.lean != 0, s.cus, q.workgroups, st));
+}
+
+void stats_from_counters(const unsigned long long c[8], mcpt_render_stats& st) {
+    std::memset(&st, 0, sizeof st);
+    st.devices = 1;
+    st.rays = c[0]; st.inner_visits = c[2]; st.leaf_visits = c[3]; st.leaf_refs = c[4];
+    st.tri_tests = c[5]; st.stack_spills = c[7];
+    st.paths = c[1]; st.shades = c[6];   // (radiance queries; the hit queries leave them 0)
+}
+
+// ---- device radiance queries (render.hip radiance_kernel) -----------------------
+struct Radiance {
+    mcpt_radiance_params q;
+    uint32_t chunk;
+    uint64_t nchunks;
+};
+// The checks of a radiance query that need no device, in the header's order; p
+// resolved (NULL = the defaults)
+Radiance radiance_resolve(const mcpt_scene* s, const mcpt_radiance_params* p, int64_t n, bool ptrs) {
+    if (!s) throw mcpt::Error{MCPT_E_INVALID, "NULL scene"};
+    if (n < 0) throw mcpt::Error{MCPT_E_INVALID, "n must be >= 0"};
+    if (n && !ptrs) throw mcpt::Error{MCPT_E_INVALID, "NULL ray or result buffer"};
+    Radiance R;
+    mcpt_radiance_params& q = R.q;
+    mcpt_radiance_params_default(&q);
+    if (p) q = *p;
+    if (q.spp == 0) throw mcpt::Error{MCPT_E_INVALID, "spp must be >= 1"};
+    if (q.max_depth < 0 || q.max_depth > mcpt::kMaxDepthParam)
+        throw mcpt::Error{MCPT_E_INVALID, "max_depth must be 0..1000"};
+    if (!std::isfinite(q.illum)) throw mcpt::Error{MCPT_E_INVALID, "illum must be finite"};
+    if (q.lean != 0 && q.lean != 1) throw mcpt::Error{MCPT_E_INVALID, "lean must be 0 or 1"};
+    if (q.fresnel_kd != 0 && q.fresnel_kd != 1) throw mcpt::Error{MCPT_E_INVALID, "fresnel_kd must be 0 or 1"};
+    if (q.workgroups < 0) throw mcpt::Error{MCPT_E_INVALID, "workgroups must be >= 0"};
+    if (q.ready_thresh < 0 || q.ready_thresh > 64)
+        throw mcpt::Error{MCPT_E_INVALID, "ready_thresh must be 0 (default) or 1..64"};
+    if (uint64_t(q.spp_offset) + uint64_t(q.spp) > (uint64_t(1) << 32))
+        throw mcpt::Error{MCPT_E_INVALID, "spp_offset + spp must not pass 2^32"};
+    R.chunk = q.spp_chunk ? (q.spp_chunk < q.spp ? q.spp_chunk : q.spp) : q.spp;
+    R.nchunks = (uint64_t(q.spp) + R.chunk - 1) / R.chunk;
+    if (n >= (int64_t(1) << 31) / 3) throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many rays for one call"};
+    if (uint64_t(n) * R.nchunks >= (uint64_t(1) << 31))
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many work units (rays x chunks) for one call"};
+    if (!s->on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
+    return R;
+}
+
+// The kernel parameters of a query: a packed frame of n rays (no pixel decode
+// is run), its chunks, and the tail split of the megakernel -- the last units
+// per lane handed out one sample at a time; the workspace pointers come later
+mcpt::KernelParams radiance_plan(const mcpt_scene& s, const Radiance& R, int64_t n, uint64_t* tail_out) {
+    const mcpt_radiance_params& q = R.q;
+    mcpt::KernelParams k;
+    std::memset(&k, 0, sizeof k);
+    k.scene = s.gpu;
+    k.width = static_cast<int32_t>(n); k.height = 1;
+    k.tile = 1; k.tiles_x = static_cast<int32_t>(std::max<int64_t>(n, 1));
+    k.shard_count = 1; k.packed = 1;
+    k.npix_local = static_cast<uint32_t>(n);
+    k.spp = q.spp; k.spp_offset = q.spp_offset; k.chunk = R.chunk;
+    k.nchunks = static_cast<uint32_t>(R.nchunks);
+    k.total_units = static_cast<uint32_t>(uint64_t(n) * R.nchunks);
+    k.div_npix = mcpt::FastDiv::make(std::max<uint32_t>(k.npix_local, 1));
+    k.div_tt = mcpt::FastDiv::make(1);
+    k.div_tiles_x = mcpt::FastDiv::make(static_cast<uint32_t>(k.tiles_x));
+    k.div_tile = mcpt::FastDiv::make(1);
+    k.div_chunk = mcpt::FastDiv::make(R.chunk);
+    k.max_depth = q.max_depth;
+    k.lean = q.lean;
+    k.illum = q.illum;
+    k.fresnel_kd = q.fresnel_kd;
+    k.prev_count = q.prev_count;
+    k.mode = MCPT_MODE_CVMCTRACER;
+    k.best_init = FLT_MAX;
+    k.key = tea16(static_cast<uint32_t>(q.seed), static_cast<uint32_t>(q.seed >> 32));
+    k.ready_thresh = ready_thresh_for(s, q.ready_thresh);
+    // the renders' tail split at its default units per lane
+    const uint64_t tail = tail_split(launched_lanes(s), kTailPerLane, 0, k.total_units, k.chunk);
+    k.tail_units = k.total_units - static_cast<uint32_t>(tail);
+    k.total_items = k.tail_units + static_cast<uint32_t>(tail * k.chunk);
+    *tail_out = tail;
+    return k;
+}
+
+// The query's workspace on the scene's (current) device, grown to what k needs:
+// the ray queries' counter blocks and the renders' spill area (ensure_rays),
+// the partial sums, the tail samples, the work-unit counter
+void ensure_radiance(mcpt_scene& s, mcpt::KernelParams& k, uint64_t tail, bool host_block, bool capturing) {
+    if (capturing && (!s.rq_order.p || !s.rq_stats.p || !s.rad_small.p))
+        throw mcpt::Error{MCPT_E_NOMEM, "the first radiance query of a scene allocates: call "
+                                        "mcpt_scene_reserve_radiance before capturing a graph"};
+    ensure_rays(s, capturing);
+    if (!s.rad_small.p) {
+        TempDev t(64);
+        HIP_TRY(hipMemset(t.p, 0, 64));
+        HIP_TRY(mcpt::prepare_radiance(s.gpu));   // (the kernels' code object loaded now)
+        s.rad_small.p = t.release();
+    }
+    grow_ws(s, s.rad_partial, size_t(k.total_units) * 16, capturing);
+    if (tail) grow_ws(s, s.rad_tail, size_t(tail) * k.chunk * 16, capturing);
+    k.partial = static_cast<float4*>(s.rad_partial.p);
+    k.tail_buf = tail ? static_cast<float4*>(s.rad_tail.p) : nullptr;
+    k.counter = static_cast<uint32_t*>(s.rad_small.p);
+    k.stats = static_cast<unsigned long long*>(s.rq_stats.p) + (host_block ? 8 : 0);
+    k.spill = static_cast<uint4*>(s.ws.spill.p);
+}
+
+void radiance_async(mcpt_scene& s, const Radiance& R, int64_t n, const float* d_o, const float* d_d,
+                    const uint32_t* d_stream, float* d_out, bool host_block, hipStream_t st) {
+    uint64_t tail = 0;
+    mcpt::KernelParams k = radiance_plan(s, R, n, &tail);
+    ensure_radiance(s, k, tail, host_block, stream_capturing(st));
+    const mcpt::RayInputs ri{d_o, d_d, d_stream};
+    HIP_TRY(mcpt::launch_radiance(k, ri, s.cus, R.q.workgroups, reinterpret_cast<float4*>(d_out), st));
+}
+
+// the synchronous host entries' counter block (behind the device entries'), cleared
+unsigned long long* clear_host_block(mcpt_scene& s) {
+    unsigned long long* blk = static_cast<unsigned long long*>(s.rq_stats.p) + 8;
+    HIP_TRY(hipMemset(blk, 0, 64));
+    return blk;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcpt_intersect(mcpt_scene* s, int64_t n, const float* o, const float* d, float t_max, int32_t* tri_out,
+                   float* hit_out, mcpt_render_stats* stats) {
+    return guarded([&]() -> int {
+        if (!s || n < 0 || (n && (!o || !d || !tri_out || !hit_out))) return fail(MCPT_E_INVALID, "NULL argument");
+        if (!s->on_device) return fail(MCPT_E_INVALID, "scene was created host-only");
+        if (n >= (int64_t(1) << 31) / 3) return fail(MCPT_E_UNSUPPORTED, "too many rays for one call");
+        set_device(*s);
+        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (n) {
+            const size_t N = static_cast<size_t>(n);
+            // one allocation: o, d, hits (3 floats each), slots, counters, then the
+            // stack spill area of the old query kernel: kSpillEntries per ray, not per lane
+            const auto p = carve({N * 12, N * 12, N * 12, N * 4, size_t(64), N * kSpillEntries * 16});
+            TempDev buf(p.total);
+            mcpt::QueryParams q{};
+            q.scene = s->gpu;
+            q.o = p.at<float>(buf.p, 0);
+            q.d = p.at<float>(buf.p, 1);
+            q.hit = p.at<float>(buf.p, 2);
+            q.slot = p.at<int32_t>(buf.p, 3);
+            q.stats = p.at<unsigned long long>(buf.p, 4);
+            q.spill = p.at<uint4>(buf.p, 5);
+            q.n = static_cast<uint32_t>(n);
+            q.best_init = t_max;
+            HIP_TRY(hipMemcpy(p.at<float>(buf.p, 0), o, N * 12, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(p.at<float>(buf.p, 1), d, N * 12, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemset(q.stats, 0, 64));
+            HIP_TRY(mcpt::launch_query(q, nullptr));
+            HIP_TRY(hipDeviceSynchronize());
+            std::vector<int32_t> slot(N);
+            HIP_TRY(hipMemcpy(slot.data(), q.slot, N * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(hit_out, q.hit, N * 12, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(c, q.stats, 64, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < N; ++i)
+                tri_out[i] = slot[i] < 0 ? -1 : static_cast<int32_t>(s->tri_order[static_cast<size_t>(slot[i])]);
+        }
+        // (the old query kernel leaves paths and shades 0)
+        if (stats) stats_from_counters(c, *stats);
+        return MCPT_OK;
+    });
+}
+
+int mcpt_trace_device(mcpt_scene* s, const mcpt_trace_params* p, int64_t n, const float* d_o, const float* d_d,
+                      const float* d_t_max, int32_t* d_tri, float* d_hit, void* hip_stream) {
+    return guarded([&]() -> int {
+        const mcpt_trace_params q = trace_resolve(s, p, n, d_o && d_d && d_tri, true);
+        const size_t N = static_cast<size_t>(n);
+        const void* in[3] = {d_o, d_d, d_t_max};
+        const size_t in_bytes[3] = {N * 12, N * 12, d_t_max ? N * 4 : 0};
+        for (int i = 0; i < 3; ++i)
+            if (ranges_overlap(d_tri, N * 4, in[i], in_bytes[i]) ||
+                (d_hit && ranges_overlap(d_hit, N * 12, in[i], in_bytes[i])))
+                return fail(MCPT_E_INVALID, "an output buffer overlaps an input of the call");
+        if (d_hit && ranges_overlap(d_tri, N * 4, d_hit, N * 12))
+            return fail(MCPT_E_INVALID, "the triangle and hit buffers overlap");
+        if (!n) return MCPT_OK;
+        set_device(*s);                   // (a multi-device scene: devices[0], the primary)
+        rays_async(*s, q, n, d_o, d_d, d_t_max, d_tri, d_hit, nullptr, false, static_cast<hipStream_t>(hip_stream));
+        return MCPT_OK;
+    });
+}
+
+int mcpt_occluded_device(mcpt_scene* s, const mcpt_trace_params* p, int64_t n, const float* d_o, const float* d_d,
+                         const float* d_t_max, uint8_t* d_occluded, void* hip_stream) {
+    return guarded([&]() -> int {
+        const mcpt_trace_params q = trace_resolve(s, p, n, d_o && d_d && d_occluded, false);
+        const size_t N = static_cast<size_t>(n);
+        if (ranges_overlap(d_occluded, N, d_o, N * 12) || ranges_overlap(d_occluded, N, d_d, N * 12) ||
+            ranges_overlap(d_occluded, N, d_t_max, d_t_max ? N * 4 : 0))
+            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+        if (!n) return MCPT_OK;
+        set_device(*s);
+        rays_async(*s, q, n, d_o, d_d, d_t_max, nullptr, nullptr, d_occluded, false,
+                   static_cast<hipStream_t>(hip_stream));
+        return MCPT_OK;
+    });
+}
+
+// rays, t_max and the flags are staged in the scene's host-render buffer
+int mcpt_occluded(mcpt_scene* s, const mcpt_trace_params* p, int64_t n, const float* o, const float* d,
+                  const float* t_max, uint8_t* occluded, mcpt_render_stats* stats) {
+    return guarded([&]() -> int {
+        const mcpt_trace_params q = trace_resolve(s, p, n, o && d && occluded, false);
+        const size_t N = static_cast<size_t>(n);
+        if (ranges_overlap(occluded, N, o, N * 12) || ranges_overlap(occluded, N, d, N * 12) ||
+            ranges_overlap(occluded, N, t_max, t_max ? N * 4 : 0))
+            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (n) {
+            set_device(*s);
+            const auto part = carve({N * 12, N * 12, N * 4, N});
+            ensure_buf(s->ws.fb, part.total);
+            float* d_o = part.at<float>(s->ws.fb.p, 0);
+            float* d_d = part.at<float>(s->ws.fb.p, 1);
+            float* d_t = part.at<float>(s->ws.fb.p, 2);
+            uint8_t* d_occ = part.at<uint8_t>(s->ws.fb.p, 3);
+            HIP_TRY(hipMemcpy(d_o, o, N * 12, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_d, d, N * 12, hipMemcpyHostToDevice));
+            if (t_max) HIP_TRY(hipMemcpy(d_t, t_max, N * 4, hipMemcpyHostToDevice));
+            ensure_rays(*s, false);
+            unsigned long long* blk = clear_host_block(*s);
+            rays_async(*s, q, n, d_o, d_d, t_max ? d_t : nullptr, nullptr, nullptr, d_occ, true, nullptr);
+            HIP_TRY(hipStreamSynchronize(nullptr));
+            HIP_TRY(hipMemcpy(occluded, d_occ, N, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(c, blk, 64, hipMemcpyDeviceToHost));
+        }
+        if (stats) stats_from_counters(c, *stats);
+        return MCPT_OK;
+    });
+}
+
+int mcpt_trace_stats_read(mcpt_scene* s, mcpt_render_stats* out) {
+    return guarded([&]() -> int {
+        if (!s || !s->on_device) return fail(MCPT_E_INVALID, "scene is not on a device");
+        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (s->rq_stats.p) {              // (no query yet: zeros)
+            DeviceGuard guard;
+            set_device(*s);
+            // the queries may run on any stream: wait for the device, then read and clear
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(hipMemcpy(c, s->rq_stats.p, 64, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemset(s->rq_stats.p, 0, 64));
+        }
+        if (out) stats_from_counters(c, *out);
+        return MCPT_OK;
+    });
+}
+
+int mcpt_scene_reserve_rays(mcpt_scene* s) {
+    return guarded([&]() -> int {
+        if (!s || !s->on_device) return fail(MCPT_E_INVALID, "scene is not on a device");
+        DeviceGuard guard;
+        set_device(*s);
+        ensure_rays(*s, false);
+        return MCPT_OK;
+    });
+}
+
+int mcpt_radiance_device(mcpt_scene* s, const mcpt_radiance_params* p, int64_t n, const float* d_o, const float* d_d,
+                         const uint32_t* d_stream, float* d_radiance, void* hip_stream) {
+    return guarded([&]() -> int {
+        const Radiance R = radiance_resolve(s, p, n, d_o && d_d && d_radiance);
+        const size_t N = static_cast<size_t>(n);
+        if (ranges_overlap(d_radiance, N * 16, d_o, N * 12) || ranges_overlap(d_radiance, N * 16, d_d, N * 12) ||
+            ranges_overlap(d_radiance, N * 16, d_stream, d_stream ? N * 4 : 0))
+            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+        if (!n) return MCPT_OK;
+        set_device(*s);                   // (a multi-device scene: devices[0], the primary)
+        radiance_async(*s, R, n, d_o, d_d, d_stream, d_radiance, false, static_cast<hipStream_t>(hip_stream));
+        return MCPT_OK;
+    });
+}
+
+// rays, stream ids and the result are staged in the scene's host-render buffer
+int mcpt_radiance(mcpt_scene* s, const mcpt_radiance_params* p, int64_t n, const float* o, const float* d,
+                  const uint32_t* stream, float* radiance, mcpt_render_stats* stats) {
+    return guarded([&]() -> int {
+        const Radiance R = radiance_resolve(s, p, n, o && d && radiance);
+        const size_t N = static_cast<size_t>(n);
+        if (ranges_overlap(radiance, N * 12, o, N * 12) || ranges_overlap(radiance, N * 12, d, N * 12) ||
+            ranges_overlap(radiance, N * 12, stream, stream ? N * 4 : 0))
+            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (n) {
+            set_device(*s);
+            const auto part = carve({N * 16, N * 12, N * 12, N * 4});
+            ensure_buf(s->ws.fb, part.total);
+            float* d_out = part.at<float>(s->ws.fb.p, 0);
+            float* d_o = part.at<float>(s->ws.fb.p, 1);
+            float* d_d = part.at<float>(s->ws.fb.p, 2);
+            uint32_t* d_s = part.at<uint32_t>(s->ws.fb.p, 3);
+            HIP_TRY(hipMemcpy(d_o, o, N * 12, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_d, d, N * 12, hipMemcpyHostToDevice));
+            if (stream) HIP_TRY(hipMemcpy(d_s, stream, N * 4, hipMemcpyHostToDevice));
+            std::vector<float> rgba(N * 4, 0.0f);
+            if (R.q.prev_count) {
+                rgb_to_rgba(radiance, N, rgba.data());
+                HIP_TRY(hipMemcpy(d_out, rgba.data(), N * 16, hipMemcpyHostToDevice));
+            }
+            ensure_rays(*s, false);       // (the counter blocks exist before the host entry's is cleared)
+            unsigned long long* blk = clear_host_block(*s);
+            radiance_async(*s, R, n, d_o, d_d, stream ? d_s : nullptr, d_out, true, nullptr);
+            HIP_TRY(hipStreamSynchronize(nullptr));
+            HIP_TRY(hipMemcpy(rgba.data(), d_out, N * 16, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(c, blk, 64, hipMemcpyDeviceToHost));
+            rgba_to_rgb(rgba.data(), N, radiance);
+        }
+        if (stats) stats_from_counters(c, *stats);
+        return MCPT_OK;
+    });
+}
+
+int mcpt_scene_reserve_radiance(mcpt_scene* s, const mcpt_radiance_params* p, int64_t n) {
+    return guarded([&]() -> int {
+        const Radiance R = radiance_resolve(s, p, n, true);
+        DeviceGuard guard;
+        set_device(*s);
+        uint64_t tail = 0;
+        mcpt::KernelParams k = radiance_plan(*s, R, n, &tail);
+        ensure_radiance(*s, k, tail, false, false);
+        return MCPT_OK;
+    });
+}
+
+}  // extern "C"

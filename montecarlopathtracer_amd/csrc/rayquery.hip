@@ -226,12 +226,12 @@ hipError_t launch_rayquery(const RayQueryParams& q_in, bool any, bool lean, int 
     RayQueryParams q = q_in;
     const RayQueryGrid g = rayquery_grid(q.scene, q.n, cus, max_workgroups);
     q.seg = g.seg;
-    // the extend's defaults (capi.cpp make_plan wf_refill)
+    // the extend's defaults (plan.cpp make_plan wf_refill)
     if (q.refill <= 0) q.refill = q.scene.node_boxes ? 8 : 16;
     if (q.scene.node_boxes)
         return launch_rq<kLayGlobal, MCPT_RQ_GLOBAL_S, kGlobalBlock>(q, any, lean, g.workgroups,
                                                                     lds_bytes_global(MCPT_RQ_GLOBAL_S, true), st);
-    // (an image without child boxes fits: capi.cpp build_image)
+    // (an image without child boxes fits: scene_image.cpp build_image)
     const size_t lds = lds_bytes_counted_in_lds(q.scene.image_bytes, kRqLdsS);
     if (lds > kMaxLds) return hipErrorInvalidValue;
     return launch_rq<kLayLds, kRqLdsS, kLdsBlock>(q, any, lean, g.workgroups, lds, st);

@@ -650,7 +650,7 @@ hipError_t launch_gather(const GatherParams& g, hipStream_t st) {
 }
 
 int total_lanes_for(uint32_t image_bytes, int cus) {
-    // an image that fits in LDS is built without leaf boxes (capi.cpp build_image)
+    // an image that fits in LDS is built without leaf boxes (scene_image.cpp build_image)
     if (lds_bytes_counted_in_lds(image_bytes, 4) <= kMaxLds) return cus * kLdsBlock;
     return cus * (kGlobalBlocksPerCu > kWfGlobalSegsPerCu ? kGlobalBlocksPerCu : kWfGlobalSegsPerCu) * kGlobalBlock;
 }

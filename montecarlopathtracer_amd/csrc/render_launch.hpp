@@ -284,7 +284,7 @@ struct RayInputs {
 // grid shrinks with the work (the ray queries' floor, rayquery_launch.hpp)
 constexpr uint32_t kRadMinUnits = 64;
 
-// Multi-device gather (capi.cpp render_multi): shard r of `nshards` wrote the
+// Multi-device gather (render_host.cpp render_multi): shard r of `nshards` wrote the
 // plain means of its owned tiles, packed tile-major, to src[r * slot ...]
 // (peer-copied to the primary device); gather_kernel unpermutes them into the
 // row-major framebuffer with the running mean of reduce_kernel, bit for bit.

@@ -174,7 +174,7 @@ __host__ __device__ __forceinline__ bool implicit0(const KernelParams& kp, const
 // of a scattering ray from it (tri_hit_params: the traversal's own
 // operations, bit-identical).  The 16-B hit records cost the extend 2.4x their
 // bytes in partly written L2 lines; C2 wavefront +3.7% (12.70 -> 13.18, three
-// rounds), C4 +2.8%.  (capi.cpp wf_layout sizes the queues for this.)
+// rounds), C4 +2.8%.  (plan.cpp wf_layout sizes the queues for this.)
 
 // Issue priority of the extend's traversal bursts (its hand-off runs one
 // higher); the co-resident shade runs at 0.

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Host-side sanitizer run (SURVEY.md §5 "Race detection / sanitizers"): the C ABI's
 # host code -- OBJ/MTL reader, CreateGeometry, KD build, KD cache, model
-# descriptors (csrc/capi.cpp, host_model.cpp, kd_cache.cpp) -- built with
+# descriptors (every non-.hip source of _build.py's SOURCES) -- built with
 # AddressSanitizer + UndefinedBehaviorSanitizer (-fno-sanitize-recover: the
 # first report fails the run) and driven by tests/cpp/sanitize_driver.cpp over
 # the bundled scenes, the C4 mesh, a malformed OBJ/MTL corpus and forged KD-cache
@@ -11,19 +11,29 @@ set -euo pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 B=${1:-/tmp/mcpt_sanitize}
 mkdir -p "$B/corpus"
-CSRC=$ROOT/montecarlopathtracer_amd/csrc
-HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SAN="-fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -g -O1"
 COMMON="-std=c++17 -fPIC -ffp-contract=off -I$ROOT/include"
 
-# kernels: as shipped (device code is not sanitized; nothing launches them here)
-for k in render wavefront; do
-  [ "$B/$k.o" -nt "$CSRC/$k.hip" ] || $HIPCC -x hip --offload-arch=gfx950 -O3 $COMMON -c "$CSRC/$k.hip" -o "$B/$k.o"
-done
-# host code with ASan + UBSan
+# the library's sources: _build.py's one list.  Kernels as shipped -- the objects
+# the normal build left (device code is not sanitized; nothing launches them
+# here), built first if they are missing or stale; every other source is host
+# code and is compiled here with ASan + UBSan
+LISTS=$(cd "$ROOT" && python3 -c "
+import os
+from montecarlopathtracer_amd import _build as b
+b.build()
+objs = [os.path.join(b.LIBDIR, 'obj', os.path.basename(b.LIB) + '.' + s + '.o') for s in b.SOURCES if s.endswith('.hip')]
+if not all(map(os.path.exists, objs)):
+    b.build(force=True)
+print(' '.join(os.path.join(b.CSRC, s) for s in b.SOURCES if not s.endswith('.hip')))
+print(' '.join(objs))")
+HOST_SRCS=$(sed -n 1p <<<"$LISTS")
+KERNEL_OBJS=$(sed -n 2p <<<"$LISTS")
 g++ $SAN $COMMON -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
-    "$CSRC/capi.cpp" "$CSRC/host_model.cpp" "$CSRC/kd_cache.cpp" "$ROOT/tests/cpp/sanitize_driver.cpp" \
-    "$B/render.o" "$B/wavefront.o" -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -o "$B/sanitize_driver"
+    $HOST_SRCS "$ROOT/tests/cpp/sanitize_driver.cpp" \
+    $KERNEL_OBJS -L/opt/rocm/lib -lamdhip64 -ldl -Wl,-rpath,/opt/rocm/lib -o "$B/sanitize_driver"
+# the host staging header (tests/cpp/staging_probe.cpp), with the same sanitizers
+g++ $SAN $COMMON "$ROOT/tests/cpp/staging_probe.cpp" -o "$B/staging_probe"
 
 # malformed OBJ/MTL corpus
 python3 - "$B/corpus" <<'EOF'
@@ -88,6 +98,7 @@ print(' '.join(scene_path(s) for s in ('scene01', 'scene02', 'scene03', 'cornell
 export ASAN_OPTIONS=detect_leaks=1:abort_on_error=1:strict_string_checks=1
 export UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1
 export LSAN_OPTIONS=suppressions=$ROOT/scripts/lsan.supp
+"$B/staging_probe"
 # the driver runs with a memory watchdog (ASan's shadow makes ulimit -v unusable):
 # a KD build that ran away once took 45 GB before it was stopped
 "$B/sanitize_driver" "$B" $SCENES -- "$B"/corpus/*.obj &

@@ -5,6 +5,7 @@ qe_viewer         include/mcpt_qe_viewer.hpp: the QuinEngine OnUpdate frame loop
 image_io          include/mcpt_image_io.hpp: the main.cpp:19-29 encode, PNG and PFM
 half_box_probe    csrc/half_box.hpp: the outward-rounded fp16 leaf boxes (vs the oracle's)
 fastdiv_probe     csrc/render_launch.hpp FastDiv: multiply-high division == n / d
+staging_probe     csrc/staging.hpp: the host entries' carve arithmetic and RGB <-> RGBA converters
 """
 import os
 import subprocess
@@ -12,7 +13,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 LINKS_MCPT = {"pw_tracer_dropin": True, "qe_viewer": True, "image_io": False, "half_box_probe": False,
-              "fastdiv_probe": False}
+              "fastdiv_probe": False, "staging_probe": False}
 
 
 def build(name: str = "pw_tracer_dropin") -> str:

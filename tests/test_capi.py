@@ -130,3 +130,16 @@ def test_fastdiv_equals_integer_division():
     import build_dropin
     out = subprocess.run([build_dropin.build("fastdiv_probe")], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout + out.stderr
+
+
+def test_host_staging_carve_and_rgb_converters():
+    """The host-array entries' staging (csrc/staging.hpp): for the part lists of
+    the nine entries at n / pixel counts 0, 1, 3, 63, 64, 65 and 1000 every carved
+    part is 16-B aligned, inside the total and overlaps no other; RGB -> RGBA ->
+    RGB is the identity bit for bit (NaN payloads, -0) with the padding lane 0."""
+    import subprocess
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "cpp"))
+    import build_dropin
+    out = subprocess.run([build_dropin.build("staging_probe")], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout + out.stderr

@@ -211,6 +211,21 @@ def test_per_unit_counters_are_those_of_tile_8_pixel_by_pixel(mcpt, oracle_mod, 
         assert int(tot[i]) == rc[k], (k, int(tot[i]), rc[k])
 
 
+def test_unit_counters_refuse_the_wavefront_and_leave_the_scene_usable(mcpt, oracle_mod):
+    """Per-unit counters exist on the megakernel only: the wavefront refuses them
+    with MCPT_E_UNSUPPORTED before anything is launched, and the scene's next
+    render is the oracle's image with the oracle's counters."""
+    from montecarlopathtracer_amd._capi import McptError
+    W, H, _ = FRAMES[4]
+    with pytest.raises(McptError, match="unit counters need the megakernel pipeline") as e:
+        _scene(mcpt).render_unit_counters(_params(mcpt, "scene01", 4, "wavefront"))
+    assert e.value.code == -6
+    ref, rc = _ref(mcpt, oracle_mod, "scene01", W, H)
+    img, st = _scene(mcpt).render(_params(mcpt, "scene01", 4, "wavefront"))
+    _assert_image(img, ref)
+    _assert_counters(st, rc)
+
+
 @pytest.mark.parametrize("pipeline", ["megakernel", "wavefront"])
 @pytest.mark.parametrize("T", [4, 5])
 def test_three_shards_reassemble_the_image(mcpt, oracle_mod, T, pipeline):
