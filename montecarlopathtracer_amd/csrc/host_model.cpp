@@ -501,7 +501,7 @@ int terminal_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes) {
 // ---------------------------------------------------------------------------
 // Miss cull: occluder boxes.  A secondary ray whose segment misses the box of
 // every triangle has no hit, so the shade that creates it may end the path at
-// once (trace_device.hpp may_hit_scene).  The boxes need no material
+// once (trace_device.hpp scene_box_hits).  The boxes need no material
 // knowledge: bottom-up clustering from one box per triangle, always merging
 // the pair whose union adds the least volume (then the least surface area,
 // then the lower indices: deterministic), until max_boxes or fewer are left

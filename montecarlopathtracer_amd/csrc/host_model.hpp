@@ -80,19 +80,19 @@ struct HostScene {
 // kd_build: MCPT_KD_BUILD_REFERENCE (KDTree.hpp) or MCPT_KD_BUILD_SAH.
 void build_host_scene(const ObjModel& m, HostScene& out, const char* kd_cache_dir = nullptr,
                       int* cache_hit = nullptr, int kd_build = 0);
-// Terminal cull (render_launch.hpp MCPT_TERMINAL_CULL): the number of emitter
+// Terminal cull (render_launch.hpp "Terminal cull"): the number of emitter
 // geometries and their AABBs (min xyz, max xyz) if the scene allows the cull --
 // every non-emitter has Ka == 0 exactly, every Kd and Ks is finite, and there
 // are 1..max_boxes emitter geometries -- else 0.
 int terminal_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes);
-// Miss cull (render_launch.hpp MCPT_MISS_CULL): at most max_boxes fp32 AABBs
+// Miss cull (render_launch.hpp "Miss cull"): at most max_boxes fp32 AABBs
 // (min xyz, max xyz; bounds are vertex coordinates, unrounded) such that every
 // KD triangle lies inside at least one of them, clustered bottom-up from one
 // box per triangle by least added volume (host_model.cpp).  0 = no cull for
 // the scene: a non-finite vertex, a box that spans the scene bounds, or a
 // closed room (each face of the scene bounds covered by a flat box).
 int miss_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes);
-// Direct lists (render_launch.hpp MCPT_DIRECT_LISTS): kd id -> the first of
+// Direct lists (render_launch.hpp "Direct lists"): kd id -> the first of
 // miss_cull_boxes' boxes that holds the triangle's three vertices.  One always
 // does (the boxes are unions of triangle boxes); -1 only for no boxes.  Which
 // of several holding boxes a triangle goes to does not matter: a hit on it lies

@@ -53,7 +53,7 @@ int wavefront_streams(const mcpt_scene& s, uint64_t work, const mcpt_render_para
 // whole path groups (2^group_shift paths: 64 for LDS scenes, up to 2^14 for
 // global-memory ones): up to one group of slots per segment beyond the paths.
 // Each stream's part also has room for the primary lists' tile records
-// (render_launch.hpp MCPT_PRIMARY_LISTS; one record per owned 8x8 tile, only
+// (render_launch.hpp "Primary lists"; one record per owned 8x8 tile, only
 // the first stream's is used), so the records come out of the same plan and
 // reservation as the queues.
 struct WfLayout {
@@ -69,10 +69,7 @@ WfLayout wf_layout(const mcpt_scene& s, const Plan& pl, uint64_t cap) {
     l.cap_slots = size_t(cap) + (nseg << pl.wf_group_shift);
     l.f4 = l.cap_slots * 16;
     l.queue = al256(3 * l.f4 + 4 * l.cap_slots);
-    l.tiles = 0;
-#if MCPT_PRIMARY_LISTS
-    if (kp.tile == 8) l.tiles = al256(size_t(kp.npix_local >> 6) * mcpt::kListRecWords * 4);
-#endif
+    l.tiles = kp.tile == 8 ? al256(size_t(kp.npix_local >> 6) * mcpt::kListRecWords * 4) : 0;
     l.need = al256(2 * l.queue + l.f4 + l.tiles + bounces * sizeof(mcpt::WfCounters) + 256);
     return l;
 }
@@ -94,17 +91,14 @@ void prepare_wavefront(mcpt_scene& s, const Plan& pl, int sets, mcpt::WfParams* 
         w.q[0] = reinterpret_cast<float4*>(b); b += l.queue;
         w.q[1] = reinterpret_cast<float4*>(b); b += l.queue;
         w.radiance = reinterpret_cast<float4*>(b); b += l.f4;
-#if MCPT_PRIMARY_LISTS
-        uint32_t* const tiles = l.tiles ? reinterpret_cast<uint32_t*>(b) : nullptr;
-        b += l.tiles;
-#endif
+        w.tile_cand = l.tiles ? reinterpret_cast<uint32_t*>(b) : nullptr; b += l.tiles;
+        w.tile_classes = tile_classes(s);
         w.cnt = reinterpret_cast<mcpt::WfCounters*>(b);
         w.capacity = pl.wf_capacity;                   // paths per batch (pid range)
         w.slot_stride = static_cast<uint32_t>(l.cap_slots);
         w.refill_thresh = clamp_i(pl.wf_refill, 1, 64);
         w.group_shift = pl.wf_group_shift;
         w.sort = pl.wf_sort;
-#if MCPT_TERMINAL_CULL
         // a culled ray stands for color * (0 * illum) = 0: illum must be finite,
         // and so must the throughput, a product of at most max_depth Kd / Ks
         // components (each rounding grows it by 2^-24 at most: 2^127 leaves room)
@@ -112,23 +106,15 @@ void prepare_wavefront(mcpt_scene& s, const Plan& pl, int sets, mcpt::WfParams* 
                           std::log2(std::max(1.0, double(s.cull_gain))) * pl.kp.max_depth < 127.0;
         w.n_cull_boxes = zero ? s.n_cull_boxes : 0u;
         std::memcpy(w.cull_box, s.cull_box, sizeof w.cull_box);
-#endif
-#if MCPT_PRIMARY_LISTS
-        w.tile_cand = tiles;
-        w.tile_classes = tile_classes(s);
-#endif
-#if MCPT_MISS_CULL
         // (counting renders walk every ray: their visit counters stay the oracle's)
         w.n_miss_boxes = pl.kp.lean ? s.n_miss_boxes : 0u;
         std::memcpy(w.miss_box, s.miss_box, sizeof w.miss_box);
-#endif
-#if MCPT_DIRECT_LISTS
-        // (where the miss cull runs in front of the lean LDS extend and the table
-        // fits behind the image; launch_wavefront checks the same)
+        // direct lists: active where the miss cull runs in front of the lean LDS extend
+        // and the tables fit beside the image (direct_lists_fit implies a scene in
+        // LDS).  Decided here alone: direct_counts != 0 is what launch_wavefront reads
         const bool direct = w.n_miss_boxes && mcpt::direct_lists_fit(s.gpu.image_bytes, s.gpu.node_boxes);
         w.direct_counts = direct ? s.direct_counts : 0u;
         std::memcpy(w.direct_list, s.direct_list, sizeof w.direct_list);
-#endif
     }
 }
 

@@ -100,10 +100,8 @@ void render_async(mcpt_scene& s, const mcpt_render_params* p, float* d_fb, hipSt
     Plan& pl = R.pl;
     pl.kp.raw_mean = raw_mean ? 1 : 0;
     pl.kp.unit_counters = d_unit_counters;
-#if MCPT_PRIMARY_LISTS
     // (a render without primary lists reports none)
     HIP_TRY(hipMemsetAsync(tile_classes(s), 0, 16, st));
-#endif
     const Timing t = acquire_timing(s, pl.capturing);
     if (pl.pipeline == MCPT_PIPELINE_WAVEFRONT) {
         mcpt::WfStreams wst{};

@@ -42,10 +42,6 @@ constexpr size_t kMaxLds = 160 * 1024;   // gfx950 LDS per CU
 // adds exactly 0, so wf_cull_terminal (wavefront.hip) takes every ray that
 // misses all emitter boxes out of the last queue before its closest-hit walk
 // (scene01: ~99% of the last bounce's rays, 6.7% of the frame's extend time).
-// 0: the pipeline without it, the same kernels as before it (A/B builds).
-#ifndef MCPT_TERMINAL_CULL
-#define MCPT_TERMINAL_CULL 1
-#endif
 constexpr int kMaxCullBoxes = 8;         // emitter geometries a scene may have and keep the cull
 // Primary lists (wavefront, lean CV renders of scenes in LDS, 8x8 tiles): which
 // triangles the primary rays of a tile can hit depends on the camera, the tile
@@ -56,10 +52,6 @@ constexpr int kMaxCullBoxes = 8;         // emitter geometries a scene may have 
 // kListK tests them two at a time, a longer list keeps the packet walk.  The
 // closest hit is the minimum of (t, rank) over the triangles tested, so a
 // superset of the triangles a ray can hit gives the walk's hit id, bit for bit.
-// 0: the pipeline without it, the same kernels as before it (A/B builds).
-#ifndef MCPT_PRIMARY_LISTS
-#define MCPT_PRIMARY_LISTS 1
-#endif
 // candidates a tile's record holds (longer lists: the walk).  C2 frame, ms,
 // three runs each: K = 2 222.1-224.2, 4 221.5-223.5, 6 220.8-227.0, 8 229.2-230.2,
 // 16 229.3-229.8 (the parent 234.3-234.8; PERFLOG row 175)
@@ -84,10 +76,7 @@ constexpr uint32_t kListMaxTris = 4096;
 // it: the next queue is shorter, every extend keeps its code.  scene01 is a
 // box open towards the camera: about one secondary ray in six leaves through
 // the opening.  Counting renders keep the full walk (their visit counters stay
-// the oracle's).  0: the pipeline without it, the same kernels as before it.
-#ifndef MCPT_MISS_CULL
-#define MCPT_MISS_CULL 1
-#endif
+// the oracle's).
 // boxes a scene may have: the test costs ~25 VALU instructions per box and ray.
 // scene01 on the CPU oracle: 6 / 7 / 8 / 10 / 15 boxes recognise 56 / 66 / 86 /
 // 86.5 / 88% of the escaping rays (five walls, the light and two boxes over
@@ -100,17 +89,9 @@ constexpr int kMaxMissBoxes = 8;
 // it), so a ray that hits exactly one box can only hit that box's triangles,
 // and the closest hit is the minimum of (t, rank) over the triangles tested:
 // when that box is small (1..kDirectK triangles; scene01's five walls hold two
-// each) the extend tests the box's list with its own leaf branch instead of
-// walking the tree -- same hit id, bit for bit.  The shade stores the selector
-// with the ray, in the top four bits of the {d, depth} word: 0 = walk, 1 + box
-// index = that box's list (kNoRay, all ones, stays unique).
-// 0: the pipeline without it, the same kernels as before it (A/B builds).
-#ifndef MCPT_DIRECT_LISTS
-#define MCPT_DIRECT_LISTS MCPT_MISS_CULL
-#endif
-#if MCPT_DIRECT_LISTS && !MCPT_MISS_CULL
-#error "MCPT_DIRECT_LISTS needs MCPT_MISS_CULL (its box test)"
-#endif
+// each) the box's list is tested instead of walking the tree -- same hit id,
+// bit for bit.  Such a ray is a direct ray; the shade that makes it also
+// resolves it (Direct resolve, below).
 // triangles a box may hold and keep its list: the smallest K that loses nothing.
 // Priced on the CPU oracle (scripts/price_direct_lists.py,
 // profiles/direct_lists/pricing.txt): K = 2, 4 and 8 list the same boxes on
@@ -121,7 +102,7 @@ constexpr int kMaxMissBoxes = 8;
 #endif
 constexpr uint32_t kDirectK = MCPT_DIRECT_K;
 static_assert(kDirectK >= 1 && kDirectK <= 15, "a box's count is carried in 4 bits");
-// (kDirectShift, kDepthMask: below, behind MCPT_CLIP_WALK, which moves them)
+// (kDirectShift, kDepthMask: below, with the clip walk, whose selector they place)
 // the extend's LDS copy of the table: kMaxMissBoxes x kDirectK record indices
 // and one 16-B unit more (the leaf branch reads its refs in pairs)
 constexpr uint32_t kDirectTableWords = kMaxMissBoxes * kDirectK;
@@ -137,23 +118,15 @@ constexpr int kStatDirect = 13;
 // the next shade takes both.  A resolved ray without a hit ends as the miss
 // cull's rays do, and one made for the terminal query gets the radiance the
 // last shade would store (its hit's emission), so the last queue has no tail
-// and the terminal cull keeps its code.  No selector reaches an extend, whose
-// direct code (LDS table, selector lines) compiles out.
-// 0: the pipeline without it, the same kernels as before it (A/B builds).
-#ifndef MCPT_DIRECT_RESOLVE
-#define MCPT_DIRECT_RESOLVE MCPT_DIRECT_LISTS
-#endif
-#if MCPT_DIRECT_RESOLVE && !MCPT_DIRECT_LISTS
-#error "MCPT_DIRECT_RESOLVE needs MCPT_DIRECT_LISTS (its boxes and lists)"
-#endif
+// and the terminal cull keeps its code.  No direct ray reaches an extend.
 // The shade reads the lists' records (at most 16 x 48 B) and their indices from
 // a copy in its own LDS, kDirectShadeLds bytes counted beside the co-resident
 // extend: the reads are a dependent round trip behind the box test (from the
 // L2-resident global image the C2 frame gained 1.2% instead of 5.0%, row 179)
-constexpr size_t kDirectShadeLds = MCPT_DIRECT_RESOLVE ? size_t(kDirectTableWords) * (48 + 4) : 0;
+constexpr size_t kDirectShadeLds = size_t(kDirectTableWords) * (48 + 4);
 static_assert(kDirectTableWords * 3 <= 256, "the shade's smallest workgroup copies one record part per thread");
-// the rays the secondary extends (bounce >= 1) took, one atomic per workgroup
-// (MCPT_DIRECT_RESOLVE builds): the next slot of KernelParams::stats
+// the rays the secondary extends (bounce >= 1) took, one atomic per workgroup:
+// the next slot of KernelParams::stats
 constexpr int kStatExtend = 14;
 // Clip walk (where the direct resolve is active): the rays the secondary extends
 // still walk are almost all rays through a large box (scene01: one of the two
@@ -171,20 +144,12 @@ constexpr int kStatExtend = 14;
 // inside that box's interval: the list plus the leaves the walk reaches inside
 // the interval are a superset of what the ray can hit, and the closest hit is
 // the minimum of (t, rank) over the triangles tested.
-// 0: the pipeline without it, the same kernels as before it (A/B builds).
-#ifndef MCPT_CLIP_WALK
-#define MCPT_CLIP_WALK MCPT_DIRECT_RESOLVE
-#endif
-#if MCPT_CLIP_WALK && !MCPT_DIRECT_RESOLVE
-#error "MCPT_CLIP_WALK needs MCPT_DIRECT_RESOLVE (the direct selector's bits)"
-#endif
-// the selector's place in the depth word: a direct ray's 1 + box in the top four
-// bits, or (clip walk) the box mask in the top byte
-constexpr uint32_t kDirectShift = MCPT_CLIP_WALK ? 24 : 28, kDepthMask = (1u << kDirectShift) - 1u;
+// the selector's place in the depth word: the box mask in the top byte
+constexpr uint32_t kDirectShift = 24, kDepthMask = (1u << kDirectShift) - 1u;
 // a ray's depth is at most 3 * max_depth + 1 (QuinEngine), max_depth <= kMaxDepthParam
 constexpr int kMaxDepthParam = 1000;
 static_assert(3u * kMaxDepthParam + 1u < kDepthMask, "a ray's depth must fit under its selector");
-static_assert(!MCPT_CLIP_WALK || kMaxMissBoxes <= 8, "the clip walk's selector is one byte of box bits");
+static_assert(kMaxMissBoxes <= 8, "the clip walk's selector is one byte of box bits");
 // the rays an extend started with a selector: the last slot of KernelParams::stats
 constexpr int kStatClipped = 15;
 
@@ -324,7 +289,7 @@ struct WfCounters {                      // per (bounce, segment), 8 words
     uint32_t queued;                     // rays in this segment's queue (written by its producer)
     uint32_t hits;                       // slots whose hit id extend wrote (= queued; shade's count)
     uint32_t resolved;                   // rays in the queue's tail [seg - resolved, seg), hit ids written by
-                                         // the shade that made them (MCPT_DIRECT_RESOLVE; else 0)
+                                         // the shade that made them
     uint32_t pad[5];
 };
 struct WfParams {
@@ -348,33 +313,26 @@ struct WfParams {
     // terminal cull: the scene's emitter boxes (one per emitter geometry, fp16
     // rounded outward, packed as box_hit reads them); 0 boxes = no cull.  Last in
     // the kernel arguments, outside the scene image: no offset before them moves
-#if MCPT_TERMINAL_CULL
     uint32_t n_cull_boxes;
     uint32_t cull_box[kMaxCullBoxes][3];
-#endif
     // primary lists: one record of kListRecWords words per owned tile of the
     // call {count, indices}, and the call's tile classes {0, 1..K, > K}
     // (stream 0's are used; also last in the kernel arguments)
-#if MCPT_PRIMARY_LISTS
     uint32_t* tile_cand;
     uint32_t* tile_classes;
-#endif
     // miss cull: the scene's occluder boxes {lo xyz, hi xyz} in fp32; 0 boxes =
     // no cull (the scene has none, or a counting render).  Also last in the
     // kernel arguments: only the shade reads them, as scalar operands
-#if MCPT_MISS_CULL
     uint32_t n_miss_boxes;
     float miss_box[kMaxMissBoxes][6];
-#endif
     // direct lists: per occluder box, 4 bits of direct_counts -- the triangles of
     // its list, 0 = the box's rays walk -- and kDirectK words of direct_list, their
     // record indices (the unit of the image's leaf refs) in image order.
-    // direct_counts == 0: no ray carries a selector (the feature is off for the
-    // render).  Behind everything else in the kernel arguments
-#if MCPT_DIRECT_LISTS
+    // direct_counts == 0: no ray is direct and none carries a selector (the lists
+    // are off for the render: plan.cpp prepare_wavefront decides, and nothing
+    // after it asks again).  Behind everything else in the kernel arguments
     uint32_t direct_counts;
     uint32_t direct_list[kDirectTableWords];
-#endif
 };
 
 // LDS need of the in-LDS variant for a scene image of `image_bytes`: the
@@ -387,22 +345,15 @@ constexpr size_t kLdsCounterBytes = 32;
 inline size_t lds_bytes_counted_in_lds(uint32_t image_bytes, int S) {
     return lds_bytes_in_lds(image_bytes, S) + kLdsCounterBytes;
 }
-#if MCPT_DIRECT_LISTS
-// direct lists: the lean LDS extend keeps its table behind the counter block.
-// The table never decides where a scene lives: if it does not fit beside the
-// image the scene stays in LDS and its renders carry no selectors
-// (direct resolve with the records in the shade's LDS: the shade's static LDS --
-// its copy and 64 B of counters -- must fit beside the extend's workgroup instead)
+// direct lists: the lean LDS extend keeps its table (a clipped ray's listed box)
+// behind the counter block, and the shade's static LDS -- its copy of the lists'
+// records and 64 B of counters -- must fit beside the extend's workgroup.
+// Neither decides where a scene lives: if they do not fit beside the image the
+// scene stays in LDS and its renders make no direct rays and no selectors
 inline bool direct_lists_fit(uint32_t image_bytes, uint32_t node_boxes) {
-#if MCPT_CLIP_WALK
-    // (clip walk: the extend holds the table again, beside the shade's copy)
     const size_t need = kDirectShadeLds + 64 + kDirectLdsBytes;
-#else
-    const size_t need = kDirectShadeLds + 64 > kDirectLdsBytes ? kDirectShadeLds + 64 : kDirectLdsBytes;
-#endif
     return !node_boxes && lds_bytes_counted_in_lds(image_bytes, 4) + need <= kMaxLds;
 }
-#endif
 constexpr size_t lds_bytes_global(int S, bool counted) {
     return (size_t)S * kGlobalBlock * 16 + (counted ? kLdsCounterBytes : 0);
 }

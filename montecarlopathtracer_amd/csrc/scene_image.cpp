@@ -261,7 +261,6 @@ void build_image(mcpt_scene& s, bool force_global) {
     s.direct_counts = 0;
     std::memset(s.direct_list, 0, sizeof s.direct_list);
     std::memset(s.box_tris, 0, sizeof s.box_tris);
-#if MCPT_DIRECT_LISTS
     for (uint32_t slot = 0; slot < nt && s.n_miss_boxes; ++slot) {
         const int32_t b = s.tri_box[s.tri_order[slot]];
         if (b < 0) throw mcpt::Error{MCPT_E_INVALID, "a triangle outside every occluder box"};
@@ -272,7 +271,6 @@ void build_image(mcpt_scene& s, bool force_global) {
         if (s.box_tris[b] >= 1 && s.box_tris[b] <= mcpt::kDirectK) s.direct_counts |= s.box_tris[b] << (4u * b);
         else std::memset(&s.direct_list[size_t(b) * mcpt::kDirectK], 0, 4 * mcpt::kDirectK);
     }
-#endif
     s.cull_gain = 0.0f;
     for (const mcpt::Geometry& ge : hs.geoms)
         for (float k : {ge.Kd.x, ge.Kd.y, ge.Kd.z, ge.Ks.x, ge.Ks.y, ge.Ks.z})
@@ -511,7 +509,7 @@ int mcpt_scene_primary_tile_classes(mcpt_scene* s, uint32_t out[4]) {
     if (!s || !out) return MCPT_E_INVALID;
     return guarded([&] {
         out[0] = out[1] = out[2] = 0;
-        out[3] = MCPT_PRIMARY_LISTS ? mcpt::kListK : 0u;
+        out[3] = mcpt::kListK;
         if (!s->on_device || !s->ws.small.p) return MCPT_OK;
         set_device(*s);
         HIP_TRY(hipDeviceSynchronize());
@@ -521,7 +519,7 @@ int mcpt_scene_primary_tile_classes(mcpt_scene* s, uint32_t out[4]) {
 }
 
 int mcpt_scene_terminal_cull_boxes(const mcpt_scene* s) {
-    return s && MCPT_TERMINAL_CULL ? static_cast<int>(s->n_cull_boxes) : 0;
+    return s ? static_cast<int>(s->n_cull_boxes) : 0;
 }
 
 int mcpt_scene_miss_cull_boxes(const mcpt_scene* s, float* boxes) {
@@ -532,7 +530,7 @@ int mcpt_scene_miss_cull_boxes(const mcpt_scene* s, float* boxes) {
 
 int mcpt_scene_direct_lists(const mcpt_scene* s, int32_t* tri_box, uint32_t* box_tris, uint32_t* lists,
                             int32_t* list_kd) {
-    if (!s || !MCPT_DIRECT_LISTS) return 0;
+    if (!s) return 0;
     if (list_kd)
         for (uint32_t b = 0; b < mcpt::kMaxMissBoxes; ++b)
             for (uint32_t j = 0; j < mcpt::kDirectK; ++j) {

@@ -342,65 +342,13 @@ __device__ __forceinline__ bool box_hit(const RayState& r, uint32_t b0, uint32_t
     return slab_hit(r, lx, ly, lz, hx, hy, hz);
 }
 
-#if MCPT_MISS_CULL
-// Miss cull (render_launch.hpp MCPT_MISS_CULL): can ray (o, d) hit anything?
-// slab_hit on the segment (0, best_init] against each of the scene's n
-// occluder boxes, fp32 bounds taken from the vertices unrounded (kernel
-// arguments: scalar operands, n wave-uniform, the loop rolled).  A hit the
-// walk could accept lies on a triangle, hence inside the box that holds the
-// triangle, and the margins cover the rounding -- a ray that
-// fails every box has no hit.  inv: the IEEE reciprocals of d, as begin_ray
-// computes them.
-__device__ __forceinline__ bool may_hit_scene(V3 o, V3 d, V3 inv, float best_init,
-                                              const float (&boxes)[kMaxMissBoxes][6], uint32_t n) {
-    // slab_hit with the slab ends ordered after the products instead of before:
-    // the same operations on the same operands, so the same decisions, but the
-    // bounds stay scalar operands of the subtractions (a select of two scalars
-    // needs both copied to vector registers first: 7 instructions per box less)
-    const bool nx = __float_as_uint(d.x) >> 31, ny = __float_as_uint(d.y) >> 31, nz = __float_as_uint(d.z) >> 31;
-    bool hit = false;
-#pragma unroll 1
-    for (uint32_t i = 0; i < n; i++) {
-        const float ax = (boxes[i][0] - o.x) * inv.x, bx = (boxes[i][3] - o.x) * inv.x;
-        const float ay = (boxes[i][1] - o.y) * inv.y, by = (boxes[i][4] - o.y) * inv.y;
-        const float az = (boxes[i][2] - o.z) * inv.z, bz = (boxes[i][5] - o.z) * inv.z;
-        const float lo = max_qnan(max3_qnan(0.0f, nx ? bx : ax, ny ? by : ay), nz ? bz : az);
-        const float hi = min_qnan(min3_qnan(best_init, nx ? ax : bx, ny ? ay : by), nz ? az : bz);
-        hit |= !(lo * kEpsLo > hi * kEpsHi);
-    }
-    return hit;
-}
-#if MCPT_DIRECT_LISTS
-// Direct lists (render_launch.hpp MCPT_DIRECT_LISTS): may_hit_scene's tests, and
-// which boxes passed, in one accumulator -- box i adds 256 + i, so the result is
-// 0 when the ray fails every box (may_hit_scene's false), its high part is the
-// number of boxes hit and, when that is 1, its low byte is the box
-// (kMaxMissBoxes x 7 < 256: the index sum never carries into the count)
-__device__ __forceinline__ uint32_t scene_box_hits(V3 o, V3 d, V3 inv, float best_init,
-                                                   const float (&boxes)[kMaxMissBoxes][6], uint32_t n) {
-    const bool nx = __float_as_uint(d.x) >> 31, ny = __float_as_uint(d.y) >> 31, nz = __float_as_uint(d.z) >> 31;
-    uint32_t acc = 0;
-#pragma unroll 1
-    for (uint32_t i = 0; i < n; i++) {
-        const float ax = (boxes[i][0] - o.x) * inv.x, bx = (boxes[i][3] - o.x) * inv.x;
-        const float ay = (boxes[i][1] - o.y) * inv.y, by = (boxes[i][4] - o.y) * inv.y;
-        const float az = (boxes[i][2] - o.z) * inv.z, bz = (boxes[i][5] - o.z) * inv.z;
-        const float lo = max_qnan(max3_qnan(0.0f, nx ? bx : ax, ny ? by : ay), nz ? bz : az);
-        const float hi = min_qnan(min3_qnan(best_init, nx ? ax : bx, ny ? ay : by), nz ? az : bz);
-#if MCPT_CLIP_WALK
-        // (clip walk: the boxes that passed as a bit mask -- bit i box i -- whose
-        // popcount is the number of boxes hit; 0 as before when the ray fails all)
-        acc |= !(lo * kEpsLo > hi * kEpsHi) ? 1u << i : 0u;
-#else
-        acc += !(lo * kEpsLo > hi * kEpsHi) ? 256u + i : 0u;
-#endif
-    }
-    return acc;
-}
-#if MCPT_CLIP_WALK
-// Clip walk (render_launch.hpp MCPT_CLIP_WALK): the slab interval [lo, hi] of ray
-// (o, d) in one occluder box, scene_box_hits' operations on the same operands
-// (the extend runs them again for the unlisted boxes of a ray's selector)
+// The slab interval [lo, hi] of ray (o, d) in one occluder box --
+// slab_hit with the slab ends ordered after the products instead of before: the
+// same operations on the same operands, so the same decisions, but the bounds
+// stay scalar operands of the subtractions (a select of two scalars needs both
+// copied to vector registers first: 7 instructions per box less).  The shade
+// tests every box with it (scene_box_hits); the extend runs it again for the
+// unlisted boxes of a clipped ray's selector (render_launch.hpp "Clip walk")
 __device__ __forceinline__ void box_interval(V3 o, V3 d, V3 inv, float best_init, const float (&b)[6], float& lo,
                                              float& hi) {
     const bool nx = __float_as_uint(d.x) >> 31, ny = __float_as_uint(d.y) >> 31, nz = __float_as_uint(d.z) >> 31;
@@ -410,11 +358,28 @@ __device__ __forceinline__ void box_interval(V3 o, V3 d, V3 inv, float best_init
     lo = max_qnan(max3_qnan(0.0f, nx ? bx : ax, ny ? by : ay), nz ? bz : az);
     hi = min_qnan(min3_qnan(best_init, nx ? ax : bx, ny ? ay : by), nz ? az : bz);
 }
-#endif
-#endif
-#endif
+// Miss cull and direct lists (render_launch.hpp "Miss cull", "Direct lists"): which
+// of the scene's n occluder boxes can ray (o, d) hit?  slab_hit on the segment
+// (0, best_init] against each box, fp32 bounds taken from the vertices unrounded
+// (kernel arguments: scalar operands, n wave-uniform, the loop rolled); the boxes
+// that passed come back as a bit mask -- bit i box i -- whose popcount is the
+// number of boxes hit.  A hit the walk could accept lies on a triangle, hence
+// inside the box that holds the triangle, and the margins cover the rounding
+//  -- a ray that fails every box (mask 0) has no hit.  inv: the
+// IEEE reciprocals of d, as begin_ray computes them.
+__device__ __forceinline__ uint32_t scene_box_hits(V3 o, V3 d, V3 inv, float best_init,
+                                                   const float (&boxes)[kMaxMissBoxes][6], uint32_t n) {
+    uint32_t acc = 0;
+#pragma unroll 1
+    for (uint32_t i = 0; i < n; i++) {
+        float lo, hi;
+        box_interval(o, d, inv, best_init, boxes[i], lo, hi);
+        acc |= !(lo * kEpsLo > hi * kEpsHi) ? 1u << i : 0u;
+    }
+    return acc;
+}
 
-// Terminal cull (render_launch.hpp MCPT_TERMINAL_CULL): can the closest hit of
+// Terminal cull (render_launch.hpp "Terminal cull"): can the closest hit of
 // ray (o, d) lie on an emitter?  box_hit itself, on the segment (0, best_init]
 // against each of the scene's n emitter boxes (kernel arguments: scalar
 // operands, n wave-uniform).  The child-box cull's argument: a hit the walk

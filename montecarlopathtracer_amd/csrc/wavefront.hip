@@ -21,13 +21,13 @@
 //               (wf_sort = 1) each block is first sorted by material in LDS, so
 //               a wave runs one material branch; lean renders: a new ray that
 //               misses every occluder box of the scene is not enqueued, its
-//               path gets the zero its miss would store (may_hit_scene); one
+//               path gets the zero its miss would store (scene_box_hits); one
 //               that hits a single small box is resolved from that box's
 //               triangles here and goes, with its hit id, to the far end of
-//               queue b+1, which the extend does not visit (MCPT_DIRECT_RESOLVE)
+//               queue b+1, which the extend does not visit (direct resolve),
 //               and one that walks through a box without a list carries the mask
 //               of the boxes it hits, so that extend b+1 walks it only inside those
-//               boxes' slab interval (MCPT_CLIP_WALK)
+//               boxes' slab interval (clip walk)
 //   cull        lean renders, before the last extend: the terminal query's rays
 //               that can reach no emitter leave the queue (wf_cull_terminal)
 //   candidates  lean CV renders of an LDS scene, once per call: per 8x8 tile, the
@@ -129,30 +129,24 @@ wf_extend(const KernelParams kp, const WfParams wf) {
     uint32_t* const lslot = reinterpret_cast<uint32_t*>(lds_image + (IN_LDS ? sc.image_bytes : 0u));
     if (tid == 0) *lslot = 0;
     const SceneView sv = open_scene<IN_LDS, BLOCK>(lds_image, sc, tid);
-#if MCPT_DIRECT_LISTS
-    // direct lists (lean renders, scene in LDS): the boxes' triangle lists behind
-    // the counter block, read by the leaf branch as leaf refs -- dtab is the
-    // table's word offset from sv.leafs; its last 16 B are zeros (the branch reads
-    // the ref after a list's last one: record 0, in bounds, unused)
-    // (MCPT_DIRECT_RESOLVE: the shade resolves those rays, none reaches an extend)
-    constexpr bool DIRECT = LAY == kLayLds && !COUNT && !MCPT_DIRECT_RESOLVE;
-    // (MCPT_CLIP_WALK: the table is here again, for the listed box of a clipped ray's selector)
-    constexpr bool CLIP = LAY == kLayLds && !COUNT && MCPT_CLIP_WALK;
+    // clip walk (lean renders, scene in LDS): the boxes' triangle lists behind the
+    // counter block, for the listed box of a clipped ray's selector, read by the
+    // leaf branch as leaf refs -- dtab is the table's word offset from sv.leafs;
+    // its last 16 B are zeros (the branch reads the ref after a list's last one:
+    // record 0, in bounds, unused)
+    constexpr bool CLIP = LAY == kLayLds && !COUNT;
     uint32_t dtab = 0, dcnt = 0;
-    if constexpr (DIRECT || CLIP) {
+    if constexpr (CLIP) {
         // (asm results, as the refill threshold below: not kernel-argument reads in the loop)
         asm volatile("s_mov_b32 %0, %1" : "=s"(dcnt) : "s"(wf.direct_counts));
         asm volatile("s_mov_b32 %0, %1" : "=s"(dtab) : "s"((sc.image_bytes + (uint32_t)kLdsCounterBytes - sc.off_leafs) / 4u));
         if (dcnt && tid < (int)(kDirectLdsBytes / 4))
             (lslot + kLdsCounterBytes / 4)[tid] = tid < (int)kDirectTableWords ? wf.direct_list[tid] : 0u;
     }
-#if MCPT_CLIP_WALK
-    // clip walk: the boxes without a list (a selector's other bit, if any, is its
-    // listed box), and this wave's rays started with a selector
+    // the boxes without a list (a selector's other bit, if any, is its listed
+    // box), and this wave's rays started with a selector
     uint32_t unl = 0, nclip = 0, csel = 0;
     if constexpr (CLIP) asm volatile("s_mov_b32 %0, %1" : "=s"(unl) : "s"(unlisted_boxes(wf.direct_counts)));
-#endif
-#endif
     __syncthreads();
     uint4* st = reinterpret_cast<uint4*>(smem) + tid;
     uint4* spill = kp.spill + (blockIdx.x * BLOCK + (uint32_t)tid);
@@ -186,18 +180,6 @@ wf_extend(const KernelParams kp, const WfParams wf) {
         // (no branch: an empty slot's walk is set up and dropped; begin_ray
         // leaves htri = -1, its miss)
         const bool live = begin_ray(r, sc, kp.best_init);
-#if MCPT_DIRECT_LISTS
-        // a direct ray: the leaf branch runs over its box's list, and the pop on
-        // the empty stack ends it (no descent; sel is 14 for kNoRay)
-        if constexpr (DIRECT) {
-            const uint32_t sel = (depth >> kDirectShift) - 1u;
-            const bool dr = sel < (uint32_t)kMaxMissBoxes;
-            const uint32_t lp = dtab + sel * kDirectK;
-            r.lpos = dr ? lp : 0u;
-            r.lend = dr ? lp + ((dcnt >> (4u * sel)) & 15u) : 0u;
-        }
-#endif
-#if MCPT_CLIP_WALK
         // a clipped ray (selector: the mask of the boxes its segment hits): the root
         // interval cut to the union of its unlisted boxes' slab intervals -- the
         // shade's test again, box by box, boxes no lane carries skipped -- and its
@@ -239,7 +221,6 @@ wf_extend(const KernelParams kp, const WfParams wf) {
             mode = (depth != kNoRay && live && (!sel | hasl | walk)) ? kTrav : kReady;
             return;
         }
-#endif
         mode = (depth != kNoRay && live) ? kTrav : kReady;
     };
 #ifdef MCPT_PHASE_TIMING
@@ -260,9 +241,7 @@ wf_extend(const KernelParams kp, const WfParams wf) {
     const float4 eye4 = make_float4(kp.eye[0], kp.eye[1], kp.eye[2], 0.0f);
     auto ld_o = [&](uint32_t sl) { return eye0 ? eye4 : ldq(&qb[qf(seg0 + sl, kQO, qs)]); };
     if (slot < count) start(ld_o(slot), ldq(&qb[qf(seg0 + slot, kQD, qs)]));
-#if MCPT_CLIP_WALK
     if constexpr (CLIP) nclip += (uint32_t)__popcll(__ballot(slot < count && csel != 0u));
-#endif
     if (PF && nslot < count) { no4 = ld_o(nslot); nd4 = ldq(&qb[qf(seg0 + nslot, kQD, qs)]); }
     WF_STAMP(tm_setup);
     for (;;) {
@@ -308,9 +287,7 @@ wf_extend(const KernelParams kp, const WfParams wf) {
         const bool fin = mode == kReady;
         const uint32_t ns0 = PF ? 0u : cur_chunk.take(fin, lslot);   // (collective: every lane)
         const uint32_t fslot = slot;
-#if MCPT_CLIP_WALK
         csel = 0u;
-#endif
         if (fin) {
             const int32_t hid = r.htri;
             // (the next ray set up unconditionally: no branch in the hand-off; a
@@ -328,10 +305,8 @@ wf_extend(const KernelParams kp, const WfParams wf) {
             // (r holds the next ray by now: the id saved before)
             reinterpret_cast<int32_t*>(qb + qf(0, kQHIT, qs))[seg0 + fslot] = hid;
         }
-#if MCPT_CLIP_WALK
         // (wave-uniform: a scalar register; a lane past the segment's end started no ray)
         if constexpr (CLIP) nclip += (uint32_t)__popcll(__ballot(fin && mode != kDead && csel != 0u));
-#endif
         // ---- prefetch the next ray of every lane that just started one -------
         if constexpr (PF) {
             const bool want = fin && mode != kDead;
@@ -364,14 +339,10 @@ wf_extend(const KernelParams kp, const WfParams wf) {
     }
 #endif
     flush_counters(c, kp.stats);
-#if MCPT_DIRECT_RESOLVE
     // the rays the secondary extends took (queues past 0 hold no empty slot)
     if (tid == 0 && wf.bounce > 0) atomicAdd(kp.stats + kStatExtend, (unsigned long long)count);
-#endif
-#if MCPT_CLIP_WALK
     if constexpr (CLIP)
         if ((tid & 63) == 0 && nclip) atomicAdd(kp.stats + kStatClipped, (unsigned long long)nclip);
-#endif
     if (tid == 0) cn->hits = count;                        // every slot's hit id is written
 }
 
@@ -381,7 +352,7 @@ wf_extend(const KernelParams kp, const WfParams wf) {
 // continuing ray goes to the next free slot of the segment's queue b+1 (one
 // LDS atomic per wave, 64 consecutive slots), so queue b+1 is dense.  Queue
 // order is scheduling-dependent, but nothing reads it (state keyed by pid).
-// Direct resolve (render_launch.hpp MCPT_DIRECT_RESOLVE): a queue is two-ended
+// Direct resolve (render_launch.hpp "Direct resolve"): a queue is two-ended
 // -- the rays the extend walks from slot 0 up, the rays the shade that made them
 // already resolved from the segment's last slot down -- and the shade takes
 // both ends, through one map from its index to the slot.
@@ -392,10 +363,9 @@ wf_extend(const KernelParams kp, const WfParams wf) {
 // lane j shades the block's j-th slot in class order, so a wave runs one
 // material branch except at the (at most three) class boundaries of a block.
 // The class is a scheduling key only: every slot runs the same code.
-// (SORTB held at <= 80 VGPRs, the queue-order shade's count: two of its waves
-// per SIMD beside the LDS extend's four)
+// (held at <= 80 VGPRs: two of its waves per SIMD beside the LDS extend's four)
 template <int BLOCK, bool GEO_LDS, bool SORTB>
-__global__ void __launch_bounds__(BLOCK, SORTB || MCPT_DIRECT_RESOLVE ? 6 : (MCPT_WF_SHADE_WPE ? MCPT_WF_SHADE_WPE : 1))
+__global__ void __launch_bounds__(BLOCK, 6)
 wf_shade_slots(const KernelParams kp, const WfParams wf) {
     const uint32_t g = blockIdx.x;
     if (g >= wf.nseg) return;
@@ -410,7 +380,6 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
     extern __shared__ __attribute__((aligned(16))) GpuGeom lgeo[];
     const WfCounters* cn = wf.cnt + (size_t)wf.bounce * wf.nseg + g;
     WfCounters* nx = wf.cnt + (size_t)(wf.bounce + 1) * wf.nseg + g;
-#if MCPT_DIRECT_RESOLVE
     // direct resolve: the queue is two-ended -- index i < head is slot i (extend b
     // wrote its hit id), the others are the tail's slots [seg - resolved, seg),
     // whose rays and hit ids shade b - 1 wrote
@@ -420,10 +389,6 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
     const uint32_t tail0 = wf.seg - total;                 // index i >= head -> slot tail0 + i
     if (threadIdx.x == 0) ltail = 0;
     auto slot_at = [&](uint32_t i) { return i < head ? i : tail0 + i; };
-#else
-    const uint32_t total = cn->hits;                       // the slots extend b wrote a hit id for
-    auto slot_at = [&](uint32_t i) { return i; };
-#endif
     const GpuScene& sc = kp.scene;
     if (threadIdx.x == 0) lnext = 0;
     if constexpr (GEO_LDS) {
@@ -431,7 +396,6 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
         uint4* dst = reinterpret_cast<uint4*>(lgeo);
         for (uint32_t i = threadIdx.x; i < sc.n_geoms * 4u; i += BLOCK) dst[i] = src[i];
     }
-#if MCPT_DIRECT_RESOLVE
     // the lists' triangle records (at most 16 x 48 B) and their record indices in
     // LDS, entry box * kDirectK + j: the resolve's reads are a dependent round trip
     // behind the box test (a box without a list: entry 0, record 0, never read;
@@ -446,11 +410,8 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
         ldrec[threadIdx.x] = open_scene<false, BLOCK>(nullptr, sc, 0).tris[k + (threadIdx.x - 3u * e)];
         if (threadIdx.x == 3u * e) ldk[e] = k;
     }
-#endif
-#if MCPT_CLIP_WALK
     // clip walk: the boxes without a list, bit i box i (0 where the render has no lists: no selector)
     const uint32_t unlisted = unlisted_boxes(wf.direct_counts);
-#endif
     __syncthreads();
     const SceneView sv = open_scene<false, BLOCK>(nullptr, sc, 0);
     const float4* tris = sv.tris;
@@ -463,9 +424,7 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
     const bool imp = wf.bounce == 0 && implicit0(kp, wf);
     const int lane = (int)(threadIdx.x & 63u);
     Counters c = {0, 0, 0, 0, 0, 0, 0, 0};
-#if MCPT_DIRECT_LISTS
     uint32_t ndirect = 0;                                       // this wave's direct rays
-#endif
     uint32_t par = 0;
     for (uint32_t base = 0; base < total; base += BLOCK) {      // block-uniform trip count
         uint32_t i = base + threadIdx.x;
@@ -502,12 +461,8 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
             par ^= 1u;
         }
         bool cont = false;
-#if MCPT_DIRECT_LISTS
         bool direct = false;                                    // the new ray goes by a box's list
-#endif
-#if MCPT_DIRECT_RESOLVE
         int32_t rhit = -1;                                      // >= 0: the new ray is resolved, this is its hit id
-#endif
         uint32_t pid = 0, depth = kNoRay, sd = 0;
         V3 o = v3(0, 0, 0), d = v3(0, 0, 0), color = v3(0, 0, 0);
         if (i < total) {
@@ -567,35 +522,29 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
                     else scatter<false>(gm, sc.normals, htri, h.y, h.z, h.x, kp.fresnel_kd, sd, color, o, d);
                     cont = true;
                     c.rays++;
-#if MCPT_MISS_CULL
-                    // miss cull (lean renders: n_miss_boxes != 0): the new ray misses every
-                    // occluder box, so its walk would return no hit and the next shade would
-                    // store this zero; the ray stays counted and is not enqueued
+                    // the new ray against the scene's occluder boxes (lean renders:
+                    // n_miss_boxes != 0), in this order: box test, cull, direct, resolve,
+                    // clip selector
                     // (o and d settled: only they, the throughput, the RNG state and pid are
                     // live here, but with the test's operations free to move up into scatter
                     // the queue-order shade took 81 VGPRs, one over its budget; 79 with this)
                     o = v3(opaque(o.x), opaque(o.y), opaque(o.z));
                     d = v3(opaque(d.x), opaque(d.y), opaque(d.z));
-#if MCPT_DIRECT_LISTS
-                    // direct lists: the same tests also say which boxes the ray hits; one
-                    // box, and a small one (direct_counts: 4 bits per box, 0 = walk), and the
-                    // ray carries 1 + its index in the top bits of its depth word
                     if (wf.n_miss_boxes) {
+                        // (acc: the mask of the boxes hit)
                         const uint32_t acc = scene_box_hits(o, d, v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), kp.best_init,
                                                             wf.miss_box, wf.n_miss_boxes);
+                        // miss cull: the new ray misses every occluder box, so its walk would
+                        // return no hit and the next shade would store this zero; the ray stays
+                        // counted and is not enqueued
                         if (!acc) {
                             stq(&wf.radiance[pid], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
                             cont = false;
                         }
-#if MCPT_CLIP_WALK
-                        // (acc: the mask of the boxes hit)
+                        // direct lists: a ray that hits one box, and a small one (direct_counts:
+                        // 4 bits per box, 0 = walk), can only hit that box's list
                         const uint32_t box = (uint32_t)(__ffs((int)acc) - 1) & 7u;
                         direct = acc != 0u && (acc & (acc - 1u)) == 0u && ((wf.direct_counts >> (4u * box)) & 15u) != 0u;
-#else
-                        const uint32_t box = acc & 255u;
-                        direct = (acc >> 8) == 1u && ((wf.direct_counts >> (4u * box)) & 15u) != 0u;
-#endif
-#if MCPT_DIRECT_RESOLVE
                         // direct resolve: the extend's answer for a direct ray, operation for
                         // operation -- begin_ray (its reciprocals are the box test's), then
                         // the box's list in list order, in pairs, records from the LDS copy;
@@ -640,7 +589,6 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
                             } else if (rhit < 0)
                                 stq(&wf.radiance[pid], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
                         }
-#if MCPT_CLIP_WALK
                         // clip walk: a walking ray through at least one box without a list and
                         // at most one with a list carries its box mask (never a direct ray, whose
                         // one box has a list, nor a culled one, whose mask is 0)
@@ -648,33 +596,12 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
                             const uint32_t lm = acc & ~unlisted;
                             if ((acc & unlisted) != 0u && (lm & (lm - 1u)) == 0u) depth |= acc << kDirectShift;
                         }
-#endif
-#else
-                        if (direct) depth |= (box + 1u) << kDirectShift;
-#ifdef MCPT_PRICE_DIRECT
-                        // pricing build (never a default; the image is wrong, only bounce 1's
-                        // extend is timed): bounce 0's direct rays are not enqueued, so the
-                        // next extend sees exactly the walking rays of an unchanged queue
-                        if (direct && wf.bounce == 0) cont = false;
-#endif
-#endif
                     }
-#else
-                    if (wf.n_miss_boxes &&
-                        !may_hit_scene(o, d, v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), kp.best_init, wf.miss_box,
-                                       wf.n_miss_boxes)) {
-                        stq(&wf.radiance[pid], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                        cont = false;
-                    }
-#endif
-#endif
                 }
             }
             if (term) stq(&wf.radiance[pid], make_float4(L.x, L.y, L.z, 0.0f));   // (kNoRay slots: 0)
         }
-#if MCPT_DIRECT_LISTS
         ndirect += (uint32_t)__popcll(__ballot(direct));        // (wave-uniform: a scalar register)
-#endif
         // next ray: the wave's continuing lanes take consecutive slots of queue b+1
         const uint64_t m = __ballot(cont);
         if (m) {
@@ -689,7 +616,6 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
                 stq(&qb2[qf(ji, kQPS, qs)], pack(color, sd));
             }
         }
-#if MCPT_DIRECT_RESOLVE
         // resolved rays: the wave's take 64 consecutive slots from the segment's last
         // one downward, lanes ascending inside them, with their hit ids (head and
         // tail together hold at most this queue's rays, <= seg: they never meet)
@@ -708,23 +634,17 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
                 reinterpret_cast<int32_t*>(qb2 + qf(0, kQHIT, qs))[ji] = rhit;
             }
         }
-#endif
     }
     flush_counters(c, kp.stats);
-#if MCPT_DIRECT_LISTS
     if (lane == 0 && ndirect) atomicAdd(kp.stats + kStatDirect, (unsigned long long)ndirect);
-#endif
     __syncthreads();
     if (threadIdx.x == 0) nx->queued = lnext;
-#if MCPT_DIRECT_RESOLVE
     if (threadIdx.x == 0) nx->resolved = ltail;
-#endif
 }
 
-#if MCPT_TERMINAL_CULL
 // ---- terminal cull: the last queue without the rays that cannot add radiance --
 // Runs between the last scattering shade and the terminal query's extend
-// (lean renders; render_launch.hpp MCPT_TERMINAL_CULL), one workgroup per
+// (lean renders; render_launch.hpp "Terminal cull"), one workgroup per
 // segment on its queue wf.bounce.  CV: a ray that can reach no emitter box
 // (emitter_reachable) would add color * 0 * illum whatever it hits; QE: the
 // hit of the query at depth 3 * max_depth is never read.  Such a ray's path
@@ -784,11 +704,9 @@ __global__ void __launch_bounds__(kCullBlock, 6) wf_cull_terminal(const KernelPa
     __syncthreads();
     if (threadIdx.x == 0) cn->queued = lnext;
 }
-#endif
 
-#if MCPT_PRIMARY_LISTS
 // ---- candidate pass: the triangles each owned tile's primary rays can hit ---
-// Once per render call (render_launch.hpp MCPT_PRIMARY_LISTS), one wave per
+// Once per render call (render_launch.hpp "Primary lists"), one wave per
 // owned 8x8 tile.  Every sample of the tile's pixels has its jittered position
 // (primary_ray_sd's bias) in [x0 - 1, x0 + 8] x [y0 - 1, y0 + 8], so its ray
 // lies in the cone through the eye and that rectangle's corners, mapped as
@@ -870,7 +788,6 @@ __global__ void __launch_bounds__(kCandBlock) wf_tile_candidates(const KernelPar
         atomicAdd(&wf.tile_classes[n == 0u ? 0 : (n <= kListK ? 1 : 2)], 1u);
     }
 }
-#endif
 
 // ---- accumulate: samples of the batch in sample order -> partial sums -------
 // A batch holds wf.ns / wf.nsc whole chunks of nsc samples each (blockIdx.y).
@@ -946,7 +863,6 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
         if (variant_out) *variant_out = in_lds ? 4 : 5;
         return hipSuccess;
     }
-#if MCPT_PRIMARY_LISTS
     // primary lists: lean renders where the packet extend runs (CV mode, scene
     // in LDS, implicit queue 0) whose tiles are 8x8 -- one tile of one sample
     // per 64-slot group -- and whose scene a per-tile scan of every triangle
@@ -961,7 +877,6 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
                            dim3(kCandBlock), 0, st, kp, wf_in[0]);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-#endif
     if (ns > 1) {
         if ((e = hipEventRecord(ws.fork, st)) != hipSuccess) return e;
         for (int i = 1; i < ns; i++)
@@ -997,18 +912,11 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
             wf.v0 = v0;
             wf.nb = (kp.npix_local - v0) < nb_max ? (kp.npix_local - v0) : nb_max;
             const uint32_t n = wf.nb * wf.ns;
-#if MCPT_DIRECT_LISTS
-            // direct lists: where the miss cull runs in front of the lean LDS extend,
-            // and the table fits behind the image; else no ray carries a selector
-            const bool direct = in_lds && kp.lean && wf.n_miss_boxes && wf.direct_counts &&
-                                direct_lists_fit(img, kp.scene.node_boxes);
-            if (!direct) wf.direct_counts = 0;
-            // (direct resolve: the same renders, but the extend holds no table -- unless the
-            // clip walk tests a clipped ray's listed box from it)
-            const size_t direct_lds = direct && (!MCPT_DIRECT_RESOLVE || MCPT_CLIP_WALK) ? kDirectLdsBytes : 0;
-#else
-            const size_t direct_lds = 0;
-#endif
+            // direct lists: active where the plan left the counts (plan.cpp prepare_wavefront:
+            // a lean render of an LDS scene with occluder boxes, direct_lists_fit); the
+            // extend then holds the table, for a clipped ray's listed box
+            const bool direct = wf.direct_counts != 0;
+            const size_t direct_lds = direct ? kDirectLdsBytes : 0;
             // the shade's material table in LDS if it fits beside the extend's
             // workgroups on a CU (MCPT_WF_GEO_LDS)
             const size_t ext_lds = in_lds ? wf_lds_extend_bytes(kp.scene) + direct_lds
@@ -1040,15 +948,12 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
             for (int b = 0; b < max_bounces && e == hipSuccess; b++) {
                 wf.bounce = b;
                 const size_t llds = in_lds ? wf_lds_extend_bytes(kb.scene) : 0;
-#if MCPT_PRIMARY_LISTS
                 // (a batch whose pixel range is not whole tiles keeps the walk: its
                 // 64-slot groups would straddle tiles)
                 if (lists && packet && b == 0 && (wf.v0 & 63u) == 0u && (wf.nb & 63u) == 0u) {
                     wf.tile_cand = wf_in[0].tile_cand;
                     e = launch_wavefront_primary_lists(kb, wf, (int)nseg, llds, bs);
-                } else
-#endif
-                if (packet && b == 0) {
+                } else if (packet && b == 0) {
                     e = launch_wavefront_primary(kb, wf, (int)nseg, llds, bs);
                 } else if (in_lds) {
                     e = launch_extend<kLayLds, 4, kLdsBlock>(kb, wf, (int)nseg, llds + direct_lds, bs);
@@ -1065,7 +970,6 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
                 else
                     hipLaunchKernelGGL(shade_kernel<256>(geo_bytes != 0, sortb), dim3(nseg), dim3(256), geo_bytes, bs, kb, wf);
                 e = hipGetLastError();
-#if MCPT_TERMINAL_CULL
                 // the terminal query's queue (CV: a scene with emitter boxes; QE:
                 // every ray) loses the rays whose hit adds nothing; counting
                 // renders keep the full walk, so their visit counters stay the oracle's
@@ -1076,7 +980,6 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
                     hipLaunchKernelGGL(wf_cull_terminal, dim3(nseg), dim3(kCullBlock), 0, bs, kb, wf);
                     e = hipGetLastError();
                 }
-#endif
             }
             if (e != hipSuccess) break;
             hipLaunchKernelGGL(wf_accumulate, dim3((wf.nb + 255u) / 256u, ncb), dim3(256), 0, bs, kb, wf);

@@ -31,7 +31,7 @@ namespace {
 // source text, not a function, so that wf_extend_primary's code stays what it
 // was without the second kernel (inlined from a shared function, its epilogue
 // came out one instruction shorter).
-// LIST (wf_primary_lists, render_launch.hpp MCPT_PRIMARY_LISTS; lean renders
+// LIST (wf_primary_lists, render_launch.hpp "Primary lists"; lean renders
 // whose groups are whole 8x8 tiles): a group first reads its tile's candidate
 // record (wf_tile_candidates), fetched one group ahead.  No candidate: every
 // lane's ray is a miss, and nothing but the path count is computed.  Up to
@@ -45,14 +45,12 @@ __global__ void __launch_bounds__(BLOCK, 1) wf_extend_primary(const KernelParams
     constexpr bool LIST = false;
 #include "wf_primary_body.hpp"
 }
-#if MCPT_PRIMARY_LISTS
 // (<= 88 VGPRs, as the LDS scenes' other lean extends: two shade waves per SIMD beside it)
 template <int S, int BLOCK>
 __global__ void __launch_bounds__(BLOCK, 1) wf_primary_lists(const KernelParams kp, const WfParams wf) {
     constexpr bool LIST = true, COUNT = false;
 #include "wf_primary_body.hpp"
 }
-#endif
 
 }  // namespace
 
@@ -61,11 +59,9 @@ hipError_t launch_wavefront_primary(const KernelParams& kp, const WfParams& wf, 
     auto kern = kp.lean ? wf_extend_primary<4, kLdsBlock, false> : wf_extend_primary<4, kLdsBlock, true>;
     return launch_dyn_lds(kern, dim3(grid), dim3(kLdsBlock), lds, st, kp, wf);
 }
-#if MCPT_PRIMARY_LISTS
 hipError_t launch_wavefront_primary_lists(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
                                           hipStream_t st) {
     return launch_dyn_lds(wf_primary_lists<4, kLdsBlock>, dim3(grid), dim3(kLdsBlock), lds, st, kp, wf);
 }
-#endif
 
 }  // namespace mcpt

@@ -24,10 +24,8 @@ using namespace trace;
 // resolving its groups from the per-tile candidate lists (launch_wavefront calls them)
 hipError_t launch_wavefront_primary(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
                                     hipStream_t st);
-#if MCPT_PRIMARY_LISTS
 hipError_t launch_wavefront_primary_lists(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
                                           hipStream_t st);
-#endif
 
 namespace {
 
@@ -35,19 +33,11 @@ namespace {
 // queue slot without a ray (pixel outside the image): it ends as a miss with
 // zero radiance and is counted nowhere, like the megakernel's empty units.
 constexpr uint32_t kNoRay = 0xFFFFFFFFu;
-// Direct lists (render_launch.hpp MCPT_DIRECT_LISTS): the word's top four bits
-// carry the ray's selector (0 walk, 1 + box its list); the depth is the rest
-// (MCPT_DIRECT_RESOLVE: the shade resolves a direct ray itself, no word carries a selector;
-// MCPT_CLIP_WALK: the top byte carries a walking ray's box mask, 0 = the full walk)
-__device__ __forceinline__ uint32_t ray_depth(uint32_t w) {
-#if (MCPT_DIRECT_LISTS && !MCPT_DIRECT_RESOLVE) || MCPT_CLIP_WALK
-    return w == kNoRay ? w : (w & kDepthMask);
-#else
-    return w;
-#endif
-}
+// Clip walk (render_launch.hpp "Clip walk"): the word's top byte carries a walking
+// ray's selector, the mask of the boxes it hits (0 = the full walk); the depth is
+// the rest
+__device__ __forceinline__ uint32_t ray_depth(uint32_t w) { return w == kNoRay ? w : (w & kDepthMask); }
 
-#if MCPT_CLIP_WALK
 // Clip walk: the occluder boxes without a list as a mask, bit i box i, from
 // WfParams::direct_counts (wave-uniform: scalar operations); 0 for a render
 // without lists, whose shades then make no selector
@@ -57,7 +47,6 @@ __device__ __forceinline__ uint32_t unlisted_boxes(uint32_t direct_counts) {
     for (uint32_t b = 0; b < (uint32_t)kMaxMissBoxes; b++) m |= ((direct_counts >> (4u * b)) & 15u) ? 0u : 1u << b;
     return direct_counts ? m : 0u;
 }
-#endif
 
 __device__ __forceinline__ float4 pack(V3 v, uint32_t w) { return make_float4(v.x, v.y, v.z, __uint_as_float(w)); }
 
@@ -219,14 +208,11 @@ static_assert(kGlobalBlock == 256, "MCPT_WF_GLOBAL_WAVES = workgroups per CU onl
 #ifndef MCPT_WF_GLOBAL_PREFETCH
 #define MCPT_WF_GLOBAL_PREFETCH 1
 #endif
-// register budgets (waves per SIMD the compiler plans for; 0 = none) of the
-// LDS scenes' lean extend and of the queue-order shade, and the shade's
-// workgroup beside an LDS extend workgroup (512: two waves per SIMD)
+// register budget (waves per SIMD the compiler plans for; 0 = none) of the
+// LDS scenes' lean extend, and the shade's workgroup beside an LDS extend
+// workgroup (512: two waves per SIMD)
 #ifndef MCPT_WF_LDS_WPE
 #define MCPT_WF_LDS_WPE 0
-#endif
-#ifndef MCPT_WF_SHADE_WPE
-#define MCPT_WF_SHADE_WPE 0
 #endif
 #ifndef MCPT_WF_SHADE_LDS_BLOCK
 #define MCPT_WF_SHADE_LDS_BLOCK 512

@@ -77,7 +77,6 @@
     };
     uint32_t base = take_group();
     float4 nd4 = make_float4(0, 0, 0, 0);
-#if MCPT_PRIMARY_LISTS
     // the record of the group whose first slot is j0 (wave-uniform; the groups
     // of a LIST launch are whole tiles: launch_wavefront).  Records are read
     // through the constant address space, i.e. by scalar loads into SGPRs: no
@@ -96,16 +95,14 @@
             nrec = rec_of(base);
             nh4 = *(const_u32x4*)nrec;
         }
-    } else
-#endif
-    if (base + (uint32_t)lane < count) nd4 = dir_of(base + (uint32_t)lane);
+    } else if (base + (uint32_t)lane < count)
+        nd4 = dir_of(base + (uint32_t)lane);
     uint32_t pslot = count;                             // the previous group's slot (count: none)
     int32_t phit = -1;
     for (;;) {
         if (base >= count) break;
         const uint32_t slot = base + (uint32_t)lane;
         uint32_t nbase = 0;
-#if MCPT_PRIMARY_LISTS
         if constexpr (LIST) {
             const u32x4 h4 = nh4;
             const_u32* const rec = nrec;
@@ -163,7 +160,6 @@
             if (slot < count) nd4 = dir_of(slot);
             else nd4 = make_float4(0, 0, 0, __uint_as_float(kNoRay));
         }
-#endif
         const float4 d4 = make_float4(opaque(nd4.x), opaque(nd4.y), opaque(nd4.z), opaque(nd4.w));
         if constexpr (!LIST) {
             if (pslot < count) hq[pslot] = phit;

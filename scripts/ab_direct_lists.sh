@@ -1,11 +1,11 @@
 #!/bin/bash
-# A/B of a compile switch (direct lists, PERFLOG row 178; direct resolve, row
-# 179): six alternated runs of the plain bench, three with A first and three
-# with B first, A = libmcpt_a.so (this tree built with the switch at 0: the
-# parent's kernels by scripts/isa_diff.py), B = libmcpt.so.  The first pair also
-# dumps image and ray count, compared at the end.  Any failing run ends the
-# script.  Output under $OUT.
-#   MCPT_LIB_NAME=libmcpt_a.so MCPT_EXTRA_FLAGS=-DMCPT_DIRECT_RESOLVE=0 python montecarlopathtracer_amd/_build.py
+# A/B of a change against its parent (direct lists, PERFLOG row 178; direct
+# resolve, row 179): six alternated runs of the plain bench, three with A first
+# and three with B first, A = libmcpt_a.so, the parent commit's build
+# (scripts/build_base.sh), B = libmcpt.so.  The first pair also dumps image and
+# ray count, compared at the end.  Any failing run ends the script.  Output
+# under $OUT.
+#   bash scripts/build_base.sh libmcpt_a.so
 #   bash scripts/ab_direct_lists.sh
 set -e -o pipefail
 O=${OUT:-build/ab_direct}; mkdir -p $O

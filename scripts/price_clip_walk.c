@@ -1,4 +1,4 @@
-/* price_clip_walk.c -- prices the clip walk (render_launch.hpp MCPT_CLIP_WALK)
+/* price_clip_walk.c -- prices the clip walk (render_launch.hpp "Clip walk")
  * on the oracle's own path loop, with no GPU: for every secondary ray of a
  * render -- the mask of the occluder boxes its segment hits (the slab test of
  * trace_device.hpp scene_box_hits, in float), whether the miss cull takes it

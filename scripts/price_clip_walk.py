@@ -1,4 +1,4 @@
-"""Price the clip walk (render_launch.hpp MCPT_CLIP_WALK) on the CPU oracle's own
+"""Price the clip walk (render_launch.hpp "Clip walk") on the CPU oracle's own
 path loop (no GPU): of a render's secondary rays, how many the miss cull takes
 (no occluder box hit), the direct resolve (one box, a listed one) and the walk;
 of the walked rays, how many carry a selector (at least one box without a list,

@@ -1,5 +1,5 @@
 /* price_direct_lists.c -- prices the direct lists (render_launch.hpp
- * MCPT_DIRECT_LISTS) on the oracle's own path loop, with no GPU: for every
+ * "Direct lists") on the oracle's own path loop, with no GPU: for every
  * secondary ray of a render, by depth -- does its segment hit an occluder box
  * at all (the rays the extend still walks after the miss cull), does it hit
  * exactly one box and a listed one (a direct ray: the slab test of

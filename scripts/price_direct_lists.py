@@ -1,4 +1,4 @@
-"""Price the direct lists (render_launch.hpp MCPT_DIRECT_LISTS) on the CPU oracle's
+"""Price the direct lists (render_launch.hpp "Direct lists") on the CPU oracle's
 own path loop (no GPU): per bounce, the share of the walked secondary rays (those
 that hit at least one occluder box: the miss cull takes the others) that are
 direct -- exactly one box hit, and a listed one -- their share of the walk's

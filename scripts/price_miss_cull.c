@@ -1,4 +1,4 @@
-/* price_miss_cull.c -- prices the miss cull (render_launch.hpp MCPT_MISS_CULL)
+/* price_miss_cull.c -- prices the miss cull (render_launch.hpp "Miss cull")
  * on the oracle's own path loop, with no GPU: for every secondary ray of a
  * render, by depth -- does it miss, does it fail every occluder box (the
  * slab test of trace_device.hpp may_hit_scene, in float), did a box-failing

@@ -1,4 +1,4 @@
-"""Price the miss cull (render_launch.hpp MCPT_MISS_CULL) on the CPU oracle's own
+"""Price the miss cull (render_launch.hpp "Miss cull") on the CPU oracle's own
 path loop (no GPU): per bounce, the share of secondary rays that miss, that
 fail every occluder box of the scene (the product's boxes, the product's slab
 test), whether any box-failing ray had a hit (must be 0), and the walk's cost

@@ -1,7 +1,7 @@
 #!/bin/bash
-# Where a compile switch's gain is (direct lists, PERFLOG row 178; direct
-# resolve, row 179), for A = libmcpt_a.so (this tree built with the switch
-# at 0, e.g. -DMCPT_DIRECT_RESOLVE=0) and B = libmcpt.so: a kernel trace of
+# Where a change's gain is (direct lists, PERFLOG row 178; direct resolve,
+# row 179), for A = libmcpt_a.so, the parent commit's build
+# (scripts/build_base.sh libmcpt_a.so), and B = libmcpt.so: a kernel trace of
 # one C2 frame on one stream (extend and shade per bounce,
 # scripts/wf_bounce_times.py), then, in runs of their own with no tracing
 # alongside, SQ_INSTS_VALU per kernel class (scripts/valu_by_class.py); then the

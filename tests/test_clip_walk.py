@@ -1,4 +1,4 @@
-"""The wavefront's clip walk on the GPU (render_launch.hpp MCPT_CLIP_WALK): in
+"""The wavefront's clip walk on the GPU (render_launch.hpp "Clip walk"): in
 lean renders where the direct lists are active, a walking ray through at least
 one occluder box without a list and at most one with a list carries its box mask;
 the lean LDS extend walks it only inside its unlisted boxes' slab interval, its

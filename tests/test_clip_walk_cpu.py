@@ -1,4 +1,4 @@
-"""The wavefront's clip walk without a GPU (render_launch.hpp MCPT_CLIP_WALK): the
+"""The wavefront's clip walk without a GPU (render_launch.hpp "Clip walk"): the
 decision -- the shade's selector (trace_device.hpp scene_box_hits as a box mask:
 at least one box without a list, at most one with a list, not a direct ray) and
 the extend's clip interval (box_interval over the selector's unlisted boxes:

@@ -1,4 +1,4 @@
-"""The wavefront's direct lists on the GPU (render_launch.hpp MCPT_DIRECT_LISTS):
+"""The wavefront's direct lists on the GPU (render_launch.hpp "Direct lists"):
 in lean renders of a scene in LDS the shade marks a new ray whose segment hits
 exactly one occluder box, a small one, and the extend resolves it from that
 box's triangles without a tree walk.  The image stays the oracle's bit for bit.

@@ -1,5 +1,5 @@
 """The wavefront's direct lists without a GPU (render_launch.hpp
-MCPT_DIRECT_LISTS): the host's assignment of triangles to occluder boxes and the
+"Direct lists"): the host's assignment of triangles to occluder boxes and the
 small boxes' lists (capi.cpp build_image), and the decision -- the shade's
 selector (trace_device.hpp scene_box_hits: exactly one box hit, and a small one)
 followed by the extend's test of that box's triangles alone -- restated in

@@ -1,4 +1,4 @@
-"""The wavefront's direct resolve on the GPU (render_launch.hpp MCPT_DIRECT_RESOLVE):
+"""The wavefront's direct resolve on the GPU (render_launch.hpp "Direct resolve"):
 where the direct lists are active -- lean renders of a scene in LDS with occluder
 boxes -- the shade that makes a direct ray also finds its hit and writes ray and
 hit id to the far end of the segment's next queue; no direct ray reaches an

@@ -1,4 +1,4 @@
-"""The wavefront's miss cull (render_launch.hpp MCPT_MISS_CULL): in lean renders
+"""The wavefront's miss cull (render_launch.hpp "Miss cull"): in lean renders
 the shade that creates a ray ends the path at once when the ray misses every
 occluder box of the scene, and the image stays the oracle's bit for bit.
 

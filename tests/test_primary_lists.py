@@ -1,5 +1,5 @@
 """Primary rays resolved from per-tile candidate lists (render_launch.hpp
-MCPT_PRIMARY_LISTS): lean wavefront renders of a scene in LDS list, per 8x8
+"Primary lists"): lean wavefront renders of a scene in LDS list, per 8x8
 tile, the triangles the tile's jitter-grown frustum can touch, and bounce 0
 tests those instead of walking the KD tree.  The closest hit is the minimum of
 (t, rank) over the triangles tested, so the image and the ray count stay the

@@ -1,4 +1,4 @@
-"""The wavefront's terminal cull (render_launch.hpp MCPT_TERMINAL_CULL): lean
+"""The wavefront's terminal cull (render_launch.hpp "Terminal cull"): lean
 renders drop the rays of the path loop's last query that can reach no emitter
 box, and the image stays the oracle's bit for bit.
 
