@@ -91,7 +91,9 @@ typedef struct {
                                    each), 0 = automatic: LDS scenes 2^28 on one or two streams,
                                    2^27 on three or more; global-memory scenes 2^28 on one stream,
                                    2^27 on more; a default batch is also capped at work / streams
-                                   and shrunk (halved) until the queues fit wf_mem_limit */
+                                   and shrunk (halved) until the queues fit wf_mem_limit; where it
+                                   cuts the frame of a render that can use the primary lists
+                                   (mcpt_scene_primary_tile_classes) it holds whole 8x8 tiles */
     int32_t mode;               /* MCPT_MODE_*: path semantics (default CVMCTracer)       */
     int32_t lean;               /* 1: the megakernel counts only rays (paths, shades, spills,
                                    inner/leaf visits, leaf refs, triangle tests read 0; image and
@@ -106,7 +108,8 @@ typedef struct {
                                    faster); same image */
     /* Scheduling.  None of these changes the image or the counters, only the
      * time; 0 = automatic (the measured defaults).
-     * mcpt_plan_query reports the values a render would use. */
+     * mcpt_plan_query reports the values a render would use.  Pinned on the
+     * device, with wf_batch, against the CPU oracle: tests/test_gpu_schedules.py. */
     int32_t wf_streams;         /* wavefront HIP streams 1..4 the batches rotate over; 0: scenes in
                                    LDS 2 (3 for frames of more than 2^29 paths), global-memory scenes 4 */
     int32_t wf_refill;          /* wavefront extend: ready lanes before a wave refills (1..64);
@@ -340,7 +343,13 @@ uint64_t mcpt_scene_clipped_rays(const mcpt_scene* s);
  * list is empty (no primary ray made), holds 1..K triangles (tested straight
  * from the list) or more than K (the packet walk), out[3] = K (0: built
  * without the lists).  All three are 0 after a render that did not use the
- * lists.  Waits for the device.  (Its own entry, as the one above.) */
+ * lists.  A batch reads the lists only if its pixel range is whole tiles; the
+ * batch split is known on the host before anything is launched, so a render
+ * none of whose batches is whole tiles (wf_batch = 1000 on a frame of more
+ * pixels, say) runs no candidate pass and reports 0 0 0, and a render with at
+ * least one such batch runs the pass once and reports every owned tile, also
+ * those whose batches walked.  tests/test_gpu_schedules.py pins both.  Waits
+ * for the device.  (Its own entry, as the one above.) */
 int mcpt_scene_primary_tile_classes(mcpt_scene* s, uint32_t out[4]);
 /* KD tree as built (BFS order, QuinEngine/RTX/ShaderResource.hpp:128-179):
  * nodes n_nodes*12 words {left,right,axis(0 leaf,1..3),split bits,min[3],max[3],

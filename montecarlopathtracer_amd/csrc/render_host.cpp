@@ -113,8 +113,8 @@ void render_async(mcpt_scene& s, const mcpt_render_params* p, float* d_fb, hipSt
             wst.join[i] = s.wf_join[i];
         }
         const int queries = pl.kp.mode == MCPT_MODE_QUINENGINE ? 3 * pl.kp.max_depth + 1 : pl.kp.max_depth + 1;
-        HIP_TRY(mcpt::launch_wavefront(pl.kp, R.wf, wst, s.cus, queries, t.e[0], t.e[1], t.e[2],
-                                       reinterpret_cast<float4*>(d_fb), &s.last_variant));
+        HIP_TRY(mcpt::launch_wavefront(pl.kp, R.wf, wst, s.cus, queries, !pl.wf_batch_explicit, t.e[0], t.e[1],
+                                       t.e[2], reinterpret_cast<float4*>(d_fb), &s.last_variant));
     } else {
         HIP_TRY(mcpt::launch_render(pl.kp, s.cus, st, t.e[0], t.e[1], t.e[2], reinterpret_cast<float4*>(d_fb),
                                     &s.last_variant));

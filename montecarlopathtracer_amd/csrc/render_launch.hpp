@@ -405,7 +405,9 @@ int wavefront_segments(const GpuScene& sc, int cus);
 // wavefront pipeline: generate / extend / shade per bounce / accumulate per
 // batch, then the same reduction (events: ev0 before, ev1 after the batches)
 // wavefront streams: batch i runs on stream i mod n (st[0] = the caller's),
-// forked from and joined back into st[0] with the events of each extra stream
+// forked from and joined back into st[0] with the events of each extra stream.
+// default_batch: the plan chose wf[].capacity (mcpt_render_params::wf_batch 0);
+// the batches of a render that can use the primary lists are then whole tiles
 constexpr int kMaxWfStreams = 4;
 struct WfStreams {
     int n;
@@ -413,7 +415,7 @@ struct WfStreams {
     hipEvent_t fork, join[kMaxWfStreams];
 };
 hipError_t launch_wavefront(const KernelParams& kp, const WfParams* wf, const WfStreams& ws, int cus,
-                            int max_bounces, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2, float4* fb,
-                            int* variant_out);
+                            int max_bounces, bool default_batch, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2,
+                            float4* fb, int* variant_out);
 
 }  // namespace mcpt

@@ -827,6 +827,51 @@ void read_lane_use_wf(unsigned long long out[6]) {   // wavefront extend lane-us
 }
 #endif
 
+namespace {
+
+// The batch split of a render, one run of chunks at a time: from `chunk` on,
+// ncb chunks of nsc samples each are rendered together (whole-image batches may
+// span several full chunks: fewer, longer launches), in batches of at most
+// nb_max pixels each.  whole: batches that cut the frame hold whole 8x8 tiles
+// (a default batch of a render that can use the primary lists: work / streams
+// pixels are no whole tiles when the tile count is odd, nor is a batch over a
+// chunk length that does not divide it, and such a render would walk every
+// primary ray).
+struct WfSpan {
+    uint32_t nsc, ncb, nb_max;
+};
+WfSpan wf_span(const KernelParams& kp, uint32_t capacity, uint32_t chunk, bool whole) {
+    WfSpan s;
+    s.nsc = (kp.spp - chunk * kp.chunk) < kp.chunk ? (kp.spp - chunk * kp.chunk) : kp.chunk;
+    s.ncb = 1;
+    if (s.nsc == kp.chunk && (uint64_t)kp.npix_local * kp.chunk <= capacity) {
+        const uint32_t full = (kp.spp / kp.chunk) - chunk;             // full chunks left
+        const uint32_t fit = (uint32_t)(capacity / ((uint64_t)kp.npix_local * kp.chunk));
+        s.ncb = fit < full ? fit : full;
+    }
+    s.nb_max = capacity / (s.ncb * s.nsc);
+    if (whole && s.nb_max >= 64u && s.nb_max < kp.npix_local) s.nb_max &= ~63u;
+    return s;
+}
+// (a batch whose pixel range is not whole 8x8 tiles keeps the walk: its 64-slot
+// groups would straddle tiles)
+bool whole_tiles(uint32_t v0, uint32_t nb) { return (v0 & 63u) == 0u && (nb & 63u) == 0u; }
+// whether any batch of the split is whole tiles, i.e. can read the primary lists
+bool any_whole_tile_batch(const KernelParams& kp, uint32_t capacity, bool whole) {
+    for (uint32_t chunk = 0; chunk < kp.nchunks;) {
+        const WfSpan s = wf_span(kp, capacity, chunk, whole);
+        chunk += s.ncb;
+        // every batch but the last holds nb_max pixels: whole tiles only if nb_max is (then
+        // all are; npix_local is whole 8x8 tiles); else the last one alone can be, which
+        // ends with the frame, if it starts on a tile
+        const uint32_t last_v0 = (kp.npix_local - 1u) / s.nb_max * s.nb_max;
+        if ((s.nb_max & 63u) == 0u || whole_tiles(last_v0, kp.npix_local - last_v0)) return true;
+    }
+    return false;
+}
+
+}  // namespace
+
 int wavefront_segments(const GpuScene& sc, int cus) {
     return wf_in_lds(sc) ? cus : cus * kWfGlobalSegsPerCu;
 }
@@ -836,8 +881,8 @@ size_t wf_lds_extend_bytes(const GpuScene& sc) {
 }
 
 hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, const WfStreams& ws, int cus,
-                            int max_bounces, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2, float4* fb,
-                            int* variant_out) {
+                            int max_bounces, bool default_batch, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2,
+                            float4* fb, int* variant_out) {
     KernelParams kp = kp_in;
     const uint32_t img = kp.scene.image_bytes;
     const bool in_lds = wf_in_lds(kp.scene);
@@ -867,10 +912,15 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
     // in LDS, implicit queue 0) whose tiles are 8x8 -- one tile of one sample
     // per 64-slot group -- and whose scene a per-tile scan of every triangle
     // suits (kListMaxTris).  The candidate pass runs once, on the caller's
-    // stream, before the batches' streams fork from it.
-    const bool lists = MCPT_WF_PACKET0 && MCPT_WF_GEN0 && MCPT_WF_IMPLICIT0 >= 2 && kp.lean && in_lds &&
-                       implicit0(kp, wf_in[0]) && kp.tile == 8 && kp.scene.n_tris <= kListMaxTris &&
-                       wf_in[0].tile_cand && wf_in[0].tile_classes;
+    // stream, before the batches' streams fork from it -- if the split below
+    // has a batch of whole tiles at all: a render none of whose batches can read
+    // the lists runs no pass and reports no tile classes.
+    const bool can_list = MCPT_WF_PACKET0 && MCPT_WF_GEN0 && MCPT_WF_IMPLICIT0 >= 2 && kp.lean && in_lds &&
+                          implicit0(kp, wf_in[0]) && kp.tile == 8 && kp.scene.n_tris <= kListMaxTris &&
+                          wf_in[0].tile_cand && wf_in[0].tile_classes;
+    // (a batch size the caller asked for is kept as asked)
+    const bool whole = can_list && default_batch;
+    const bool lists = can_list && any_whole_tile_batch(kp, wf_in[0].capacity, whole);
     if (lists) {
         const uint32_t tiles = kp.npix_local >> 6;
         hipLaunchKernelGGL(wf_tile_candidates, dim3((tiles + kCandBlock / 64 - 1) / (kCandBlock / 64)),
@@ -887,17 +937,10 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
     // writing the shared partial sums or spill areas behind a failed call.
     uint32_t batch = 0;
     for (uint32_t chunk = 0; chunk < kp.nchunks && e == hipSuccess;) {
-        // whole-image batches may span several full chunks (fewer, longer launches)
-        const uint32_t nsc = (kp.spp - chunk * kp.chunk) < kp.chunk ? (kp.spp - chunk * kp.chunk) : kp.chunk;
-        uint32_t ncb = 1;
-        if (nsc == kp.chunk && (uint64_t)kp.npix_local * kp.chunk <= wf_in[0].capacity) {
-            const uint32_t full = (kp.spp / kp.chunk) - chunk;             // full chunks left
-            const uint32_t fit = (uint32_t)(wf_in[0].capacity / ((uint64_t)kp.npix_local * kp.chunk));
-            ncb = fit < full ? fit : full;
-        }
+        const WfSpan span = wf_span(kp, wf_in[0].capacity, chunk, whole);
+        const uint32_t nsc = span.nsc, ncb = span.ncb, nb_max = span.nb_max;
         const uint32_t chunk0 = chunk;
         chunk += ncb;
-        const uint32_t nb_max = wf_in[0].capacity / (ncb * nsc);
         for (uint32_t v0 = 0; v0 < kp.npix_local && e == hipSuccess; v0 += nb_max, ++batch) {
             const int h = (int)(batch % (uint32_t)ns);
             const hipStream_t bs = ws.st[h];
@@ -948,9 +991,7 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
             for (int b = 0; b < max_bounces && e == hipSuccess; b++) {
                 wf.bounce = b;
                 const size_t llds = in_lds ? wf_lds_extend_bytes(kb.scene) : 0;
-                // (a batch whose pixel range is not whole tiles keeps the walk: its
-                // 64-slot groups would straddle tiles)
-                if (lists && packet && b == 0 && (wf.v0 & 63u) == 0u && (wf.nb & 63u) == 0u) {
+                if (lists && packet && b == 0 && whole_tiles(wf.v0, wf.nb)) {
                     wf.tile_cand = wf_in[0].tile_cand;
                     e = launch_wavefront_primary_lists(kb, wf, (int)nseg, llds, bs);
                 } else if (packet && b == 0) {
