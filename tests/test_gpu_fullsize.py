@@ -211,7 +211,8 @@ def test_c4_full_spp_crop_matches_oracle(mcpt, oracle_mod):
 def test_c5_full_spp_crop_matches_oracle(mcpt, oracle_mod, scene01):
     """BASELINE configs[4] (4096 spp, 128 chunks; the wavefront's batches span
     several chunks) on one GPU: a 64x64 crop over the glass sphere of the
-    wavefront's and the megakernel's whole frames equals the oracle bit for bit."""
+    wavefront's, the material-sorted wavefront's and the megakernel's whole frames
+    equals the oracle bit for bit."""
     W = 1024
     region = (608, 672, 672, 736)
     x0, y0, x1, y1 = region
@@ -219,10 +220,10 @@ def test_c5_full_spp_crop_matches_oracle(mcpt, oracle_mod, scene01):
         width=W, height=W, spp=4096, spp_chunk=32, traversal=oracle_mod.KD_ORDERED, threads=_host_threads(),
         region=region))
     want = ref[y0:y1, x0:x1]
-    for pipe in ("wavefront", "megakernel"):
-        img, st = scene01.render(mcpt.RenderParams(width=W, height=W, spp=4096, spp_chunk=32, pipeline=pipe))
+    for pipe, sort in (("wavefront", False), ("megakernel", False), ("wavefront", True)):
+        img, st = scene01.render(mcpt.RenderParams(width=W, height=W, spp=4096, spp_chunk=32, pipeline=pipe, wf_sort=sort))
         assert st["rays"] > 1.3e10
-        assert np.array_equal(img[y0:y1, x0:x1].view(np.uint32), want.view(np.uint32)), pipe
+        assert np.array_equal(img[y0:y1, x0:x1].view(np.uint32), want.view(np.uint32)), (pipe, sort)
 
 
 def test_c5_wavefront_equals_megakernel_and_is_deterministic(mcpt, scene01):
