@@ -38,9 +38,18 @@ int clamp_i(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 // N = 2, 2^29 paths: 136.1 ms on 2 x 2^27, 136.7 on 2 x 2^28, 143.3 on
 // 3 x 2^27 -- four batches on three streams leave one alone at the end; at
 // N = 8, 2^27 paths: 35.4 ms on 2 streams, 37.6 on 3)
+// Renders whose queue-order shade carries the rays it resolves (lean, direct
+// lists active, wf_sort = 0: render_launch.hpp "Direct resolve") do most of
+// their shading in the first bounces' kernels, and two streams of 2^28 suit
+// them at every size (C2, ms per frame, one round of 10 frames: 2 x 2^28 145.5,
+// 3 x 2^27 157.9, 4 x 2^27 153.3, 3 x 2^26 168.3, 4 x 2^26 160.0, 1 x 2^28
+// 168.6; the commit before the carry 152.6 / 149.7 / 149.2 / 159.4 / 149.9;
+// PERFLOG row 184)
 int wavefront_streams(const mcpt_scene& s, uint64_t work, const mcpt_render_params* p) {
+    const bool carry = p->lean && !p->wf_sort && s.n_miss_boxes && s.direct_counts &&
+                       mcpt::direct_lists_fit(s.gpu.image_bytes, s.gpu.node_boxes);
     const int n = p->wf_streams > 0 ? p->wf_streams
-                                    : (s.gpu.node_boxes ? 4 : (work > (uint64_t(1) << 29) ? 3 : 2));
+                                    : (s.gpu.node_boxes ? 4 : (work > (uint64_t(1) << 29) && !carry ? 3 : 2));
     return clamp_i(n, 1, mcpt::kMaxWfStreams);
 }
 

@@ -39,9 +39,13 @@ constexpr size_t kMaxLds = 160 * 1024;   // gfx950 LDS per CU
 // Terminal cull (wavefront, lean CV renders): after max_depth scatters the path
 // loop traces once more and adds color * Ka(hit) * illum.  In a scene whose
 // non-emitters all have Ka == 0 a terminal ray that cannot reach an emitter
-// adds exactly 0, so wf_cull_terminal (wavefront.hip) takes every ray that
-// misses all emitter boxes out of the last queue before its closest-hit walk
-// (scene01: ~99% of the last bounce's rays, 6.7% of the frame's extend time).
+// adds exactly 0, so every ray that misses all emitter boxes is kept from the
+// last closest-hit walk (scene01: ~99% of the last bounce's rays, 6.7% of the
+// frame's extend time).  Where: the queue-order shade of an LDS scene with
+// occluder boxes (WfParams::shade_cull) tests the ray as it makes it, behind its
+// miss-box loop, and does not enqueue it; the sorting shade and global-memory
+// scenes run wf_cull_terminal (wavefront.hip) on the last queue.  Both go
+// through terminal_ray_adds (wf_device.hpp), and the ray stays counted.
 constexpr int kMaxCullBoxes = 8;         // emitter geometries a scene may have and keep the cull
 // Primary lists (wavefront, lean CV renders of scenes in LDS, 8x8 tiles): which
 // triangles the primary rays of a tile can hit depends on the camera, the tile
@@ -118,7 +122,15 @@ constexpr int kStatDirect = 13;
 // the next shade takes both.  A resolved ray without a hit ends as the miss
 // cull's rays do, and one made for the terminal query gets the radiance the
 // last shade would store (its hit's emission), so the last queue has no tail
-// and the terminal cull keeps its code.  No direct ray reaches an extend.
+// and the terminal cull sees no resolved ray.  No direct ray reaches an extend.
+// Carry (queue-order shade, WfParams::shade_cull): the lane that resolved a ray
+// keeps it in registers and shades it in its wave's next loop iteration, up to
+// kCarryMax (wf_device.hpp) times in a row, so the ray and its hit id are
+// neither written to the tail nor read back; only a chain's last ray goes to a
+// queue.  tri_hit_params runs from the triangle records as for any slot: the
+// values are the ones the next shade would compute.  Queues then hold rays of
+// mixed depths (a carried ray's product sits in queue b+1 with a depth above
+// b+1), each ray's depth is its own word's, and later queues get shorter.
 // The shade reads the lists' records (at most 16 x 48 B) and their indices from
 // a copy in its own LDS, kDirectShadeLds bytes counted beside the co-resident
 // extend: the reads are a dependent round trip behind the box test (from the
@@ -333,6 +345,11 @@ struct WfParams {
     // after it asks again).  Behind everything else in the kernel arguments
     uint32_t direct_counts;
     uint32_t direct_list[kDirectTableWords];
+    // 1: the queue-order shade owns the terminal cull and carries resolved rays
+    // ("Terminal cull", "Direct resolve" above; launch_wavefront decides per
+    // render: lean, scene in LDS with occluder boxes, wf_sort = 0).  The last
+    // kernel argument: no offset an extend reads moves
+    uint32_t shade_cull;
 };
 
 // LDS need of the in-LDS variant for a scene image of `image_bytes`: the

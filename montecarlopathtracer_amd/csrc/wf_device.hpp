@@ -48,6 +48,25 @@ __device__ __forceinline__ uint32_t unlisted_boxes(uint32_t direct_counts) {
     return direct_counts ? m : 0u;
 }
 
+// Terminal cull (render_launch.hpp "Terminal cull"): can the terminal query's
+// ray (o, d) add radiance?  QE: never (its hit is not read); CV: only if its
+// closest hit can lie on an emitter (emitter_reachable, reciprocals as
+// begin_ray computes them).  The one rule of the shade that makes such a ray
+// and of wf_cull_terminal.
+__device__ __forceinline__ bool terminal_ray_adds(bool qe, V3 o, V3 d, float best_init,
+                                                  const uint32_t (&boxes)[kMaxCullBoxes][3], uint32_t n) {
+    if (qe) return false;
+    return emitter_reachable(o, d, v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), best_init, boxes, n);
+}
+
+// Carry (render_launch.hpp "Direct resolve"): how many times in a row a lane of
+// the queue-order shade may keep the ray it resolved instead of writing it to
+// the next queue's tail (~0u: no bound).  C2 on two streams of 2^28, ms per
+// frame, three runs each: 1 142.4-143.1, 2 144.2-145.8, unbounded 144.7-145.2,
+// 0 (no carry; its best schedule, 4 x 2^27) 147.1-147.2 (PERFLOG row 184): a
+// longer chain moves more of the frame's shading into the first bounces' kernels
+constexpr uint32_t kCarryMax = 1;
+
 __device__ __forceinline__ float4 pack(V3 v, uint32_t w) { return make_float4(v.x, v.y, v.z, __uint_as_float(w)); }
 
 // Queue layout: field k of slot j (kQO {o, pid}, kQD {d, depth}, kQPS
