@@ -338,6 +338,17 @@ uint64_t mcpt_scene_extend_rays(const mcpt_scene* s);
  * tested first).  0 wherever the direct lists are off, and in a build without
  * the clip walk.  (An addition, as the ones above; the ABI stays 9.) */
 uint64_t mcpt_scene_clipped_rays(const mcpt_scene* s);
+/* Paths of the stats record last read whose bounce 0 was shaded by the kernel
+ * that resolved their primary rays (wavefront, lean CV renders of a scene in
+ * LDS with occluder boxes, 8x8 tiles, batches of whole tiles, wf_sort 0): equal
+ * to the record's paths there, 0 for every other render.  (An addition, as the
+ * ones above; the ABI stays 9.) */
+uint64_t mcpt_scene_primary_shaded(const mcpt_scene* s);
+/* LDS bytes per workgroup that such a render's bounce-0 kernel is launched
+ * with (all of it dynamic: the kernel has no static LDS), from the same
+ * function the launch calls; 0 for a scene that is not rendered from LDS.
+ * (An addition; the ABI stays 9.) */
+uint64_t mcpt_scene_primary_shade_lds(const mcpt_scene* s);
 /* Primary lists of the scene's last render (wavefront, lean CV renders of a
  * scene in LDS with 8x8 tiles): out[0..2] = the owned tiles whose candidate
  * list is empty (no primary ray made), holds 1..K triangles (tested straight

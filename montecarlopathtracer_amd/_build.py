@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, os.environ.get("MCPT_LIB_NAME", "libmcpt.so"))
 SOURCES = ["host_model.cpp", "kd_cache.cpp", "capi.cpp", "scene_image.cpp", "plan.cpp", "render_host.cpp", "queries.cpp",
-           "render.hip", "wavefront.hip", "wavefront_primary.hip",
+           "render.hip", "wavefront.hip", "wavefront_primary.hip", "wavefront_primary_shade.hip",
            "aov.hip", "denoise.hip", "variance.hip", "denoise_var.hip", "adaptive.hip", "rayquery.hip"]
 # per-source code generation (wavefront_primary.hip: the bounce-0 packet extend's
 # wave-uniform control flow as scalar branches; render.hip: GVN hoisting,
@@ -29,13 +29,19 @@ SOURCES = ["host_model.cpp", "kd_cache.cpp", "capi.cpp", "scene_image.cpp", "pla
 _WF_FLAGS = ["-mllvm", "-amdgpu-set-wave-priority=1", "-mllvm", "-two-entry-phi-node-folding-threshold=8",
              "-mllvm", "-unroll-threshold=2000"]
 SOURCE_FLAGS = {"wavefront_primary.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=1"] + _WF_FLAGS,
+                # (not the packet extend's option: it miscompiles the divergent shading code)
+                "wavefront_primary_shade.hip": _WF_FLAGS,
                 "wavefront.hip": _WF_FLAGS,
                 # the ray queries' kernel is the extend's loop: it starts from the extend's flags
                 "rayquery.hip": _WF_FLAGS,
                 "render.hip": ["-mllvm", "-enable-gvn-hoist", "-mllvm", "-unroll-threshold=2000"]}
+# the machine scheduler where it is not the build's max-ILP one (wf_primary_shade: the
+# register-minimising scheduler holds its 88-VGPR budget without scratch; MCPT_SCHED, the
+# A/B variable, does not reach such a source -- any other scheduler gives it scratch)
+SOURCE_SCHED = {"wavefront_primary_shade.hip": "iterative-minreg"}
 HEADERS = ["capi_internal.hpp", "staging.hpp", "host_model.hpp", "mcpt_device.hpp", "render_launch.hpp", "trace_device.hpp", "half_box.hpp",
            "aov_device.hpp", "aov_launch.hpp", "variance_launch.hpp", "adaptive_launch.hpp", "partial_sum.hpp", "rayquery_launch.hpp",
-           "wf_device.hpp", "wf_primary_body.hpp"]
+           "wf_device.hpp", "wf_primary_body.hpp", "wf_primary_walk.hpp", "wf_primary_pairs.hpp", "wf_primary_shade_body.hpp", "wf_shade_item.hpp"]
 ARCH = os.environ.get("MCPT_OFFLOAD_ARCH", "gfx950")
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-Wall",
@@ -68,7 +74,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         obj = os.path.join(LIBDIR, "obj", os.path.basename(LIB) + "." + src + ".o")
         # max-ILP machine scheduling for the kernels: +1.2% C2, +1.5% C4, +0.9% wavefront
         # (the default occupancy-driven scheduler gains nothing: occupancy is fixed by LDS)
-        sched = os.environ.get("MCPT_SCHED", "max-ilp")   # A/B builds only
+        sched = SOURCE_SCHED.get(src) or os.environ.get("MCPT_SCHED", "max-ilp")   # (the variable: A/B builds only)
         lang = (["-x", "hip", f"--offload-arch={ARCH}", "-mllvm", f"-amdgpu-sched-strategy={sched}"]
                 if src.endswith(".hip")
                 else ["-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"])

@@ -82,7 +82,7 @@ struct TempDev {
 
 struct Workspace {
     DevBuf partial;
-    DevBuf small;        // counter (16 B) + stats (64 B)
+    DevBuf small;        // counter (64 B) + stats (kStatSlots x 8 B) + tile classes
     DevBuf spill;
     DevBuf fb;           // mcpt_render staging framebuffer
     DevBuf wf;           // wavefront queues / path state (one allocation)
@@ -129,6 +129,7 @@ struct mcpt_scene {
     uint64_t direct_rays = 0;           // of the stats record last read
     uint64_t extend_rays = 0;           // likewise: the rays the secondary extends took
     uint64_t clipped_rays = 0;          // likewise: the rays an extend started with a selector (clip walk)
+    uint64_t primary_shaded = 0;        // likewise: the paths whose bounce 0 wf_primary_shade shaded
     mcpt::host::DevBuf d_image, d_normals;
     mcpt::host::Workspace ws;
     std::vector<mcpt::host::Timing> pending, free_timing;

@@ -434,7 +434,7 @@ void prepare_workspace(mcpt_scene& s, Plan& pl, bool tail_split, int spill_sets)
 // the last render's tile classes (primary lists): three counters behind the
 // render counters in the scene's small block (prepare_workspace)
 uint32_t* tile_classes(const mcpt_scene& s) {
-    return reinterpret_cast<uint32_t*>(static_cast<char*>(s.ws.small.p) + 192);
+    return reinterpret_cast<uint32_t*>(static_cast<char*>(s.ws.small.p) + 64 + 8 * mcpt::kStatSlots + 8);
 }
 
 // What a render of p allocates and creates on the scene's (current) device,

@@ -143,8 +143,9 @@ void read_stats(mcpt_scene& s, mcpt_render_stats* out) {
     s.direct_rays = 0;
     s.extend_rays = 0;
     s.clipped_rays = 0;
+    s.primary_shaded = 0;
     if (s.ws.small.p) {
-        unsigned long long st[16];
+        unsigned long long st[mcpt::kStatSlots];
         char* const block = static_cast<char*>(s.ws.small.p) + 64;
         HIP_TRY(hipMemcpy(st, block, sizeof st, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemset(block, 0, sizeof st));
@@ -168,6 +169,7 @@ void read_stats(mcpt_scene& s, mcpt_render_stats* out) {
         s.direct_rays = st[mcpt::kStatDirect];
         s.extend_rays = st[mcpt::kStatExtend];
         s.clipped_rays = st[mcpt::kStatClipped];
+        s.primary_shaded = st[mcpt::kStatPrimaryShaded];
     }
     r.renders = s.renders;
     r.devices = 1;
@@ -295,6 +297,7 @@ void read_stats_all(mcpt_scene& s, mcpt_render_stats* out) {
         s.direct_rays += R->direct_rays;
         s.extend_rays += R->extend_rays;
         s.clipped_rays += R->clipped_rays;
+        s.primary_shaded += R->primary_shaded;
         r.kernel_ms = std::max(r.kernel_ms, q.kernel_ms);
         r.reduce_ms = std::max(r.reduce_ms, q.reduce_ms);
     }

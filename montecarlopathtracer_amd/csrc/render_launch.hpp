@@ -71,6 +71,19 @@ constexpr uint32_t kListRecWords = (kListK + 2u + 3u) & ~3u;
 // in at most 96 KB beside the stack), so the bound only guards the scan's cost
 // should that limit ever move: above it the render keeps the packet walk.
 constexpr uint32_t kListMaxTris = 4096;
+// Primary shade (where the primary lists are read and the queue-order shade culls
+// and carries, WfParams::shade_cull): the same 8x8 tile of one sample is one wave's
+// group in wf_primary_lists and 64 consecutive indices of bounce 0's shade, so
+// wf_primary_shade (wavefront_primary_shade.hip) does both -- it resolves the
+// group as wf_primary_lists does and its lanes then run the shade's per-item code
+// (wf_shade_item.hpp, the one source of the path rule) on the ray they hold: the
+// primary ray is made once, t, beta and gamma are the ones test_tri_pair left, the
+// material and the direct lists' records come from the LDS scene image, no hit
+// id goes through memory, and a tile without a candidate only gets its zeros.
+// Continuing rays go to queue 1's head, resolved ones to its tail (shading them
+// once more in place needed scratch at 88 VGPRs, PERFLOG row 185), and the kernel writes bounce 1's counters as a shade does;
+// bounce 0 has no shade launch.  Every other render keeps the two kernels.
+// C2 frame, ms, six alternated runs: 143.6-144.3 -> 135.7-136.6 (PERFLOG row 185).
 // Miss cull (wavefront, lean renders): a secondary ray whose segment
 // (0, best_init] misses the box of every triangle has no hit; the next shade
 // would turn its miss into zero radiance and end the path.  The shade that
@@ -162,8 +175,11 @@ constexpr uint32_t kDirectShift = 24, kDepthMask = (1u << kDirectShift) - 1u;
 constexpr int kMaxDepthParam = 1000;
 static_assert(3u * kMaxDepthParam + 1u < kDepthMask, "a ray's depth must fit under its selector");
 static_assert(kMaxMissBoxes <= 8, "the clip walk's selector is one byte of box bits");
-// the rays an extend started with a selector: the last slot of KernelParams::stats
+// the rays an extend started with a selector: the next slot of KernelParams::stats
 constexpr int kStatClipped = 15;
+// the paths whose bounce 0 wf_primary_shade shaded (Primary shade, above): the slot behind it
+constexpr int kStatPrimaryShaded = 16;
+constexpr int kStatSlots = 17;
 
 struct GpuGeom {
     float Ka[3], Kd[3], Ks[3];
@@ -223,7 +239,7 @@ struct KernelParams {
     uint32_t key;                        // TEA-16 key of the 64-bit seed
     float4* partial;                     // [nchunks][npix_local]
     uint32_t* counter;                   // work-unit counter
-    unsigned long long* stats;           // 8 counters
+    unsigned long long* stats;           // 8 counters, then the slots kStat* name (kStatSlots in all)
     uint4* spill;                        // traversal-stack spill [32][total_lanes]
     uint32_t total_lanes;
     uint32_t* unit_counters;             // optional [total_units][4]: rays, inner, leaf, tests
@@ -370,6 +386,13 @@ inline size_t lds_bytes_counted_in_lds(uint32_t image_bytes, int S) {
 inline bool direct_lists_fit(uint32_t image_bytes, uint32_t node_boxes) {
     const size_t need = kDirectShadeLds + 64 + kDirectLdsBytes;
     return !node_boxes && lds_bytes_counted_in_lds(image_bytes, 4) + need <= kMaxLds;
+}
+// dynamic LDS of a wf_primary_shade launch (Primary shade, above): the lean LDS
+// extend's -- stack, image, counter block -- and, where the direct lists are
+// active, its table; the kernel has no static LDS.  launch_wavefront launches
+// with it, mcpt_scene_primary_shade_lds reports it
+inline size_t primary_shade_lds_bytes(uint32_t image_bytes, bool direct) {
+    return lds_bytes_counted_in_lds(image_bytes, 4) + (direct ? kDirectLdsBytes : 0);
 }
 constexpr size_t lds_bytes_global(int S, bool counted) {
     return (size_t)S * kGlobalBlock * 16 + (counted ? kLdsCounterBytes : 0);

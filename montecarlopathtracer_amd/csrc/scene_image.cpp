@@ -547,6 +547,13 @@ int mcpt_scene_direct_lists(const mcpt_scene* s, int32_t* tri_box, uint32_t* box
 uint64_t mcpt_scene_direct_rays(const mcpt_scene* s) { return s ? s->direct_rays : 0; }
 uint64_t mcpt_scene_extend_rays(const mcpt_scene* s) { return s ? s->extend_rays : 0; }
 uint64_t mcpt_scene_clipped_rays(const mcpt_scene* s) { return s ? s->clipped_rays : 0; }
+uint64_t mcpt_scene_primary_shaded(const mcpt_scene* s) { return s ? s->primary_shaded : 0; }
+uint64_t mcpt_scene_primary_shade_lds(const mcpt_scene* s) {
+    if (!s || s->gpu.node_boxes || mcpt::lds_bytes_counted_in_lds(s->gpu.image_bytes, 4) > mcpt::kMaxLds) return 0;
+    // (the lists as prepare_wavefront turns them on for a lean render: plan.cpp)
+    const bool direct = s->n_miss_boxes && s->direct_counts && mcpt::direct_lists_fit(s->gpu.image_bytes, s->gpu.node_boxes);
+    return mcpt::primary_shade_lds_bytes(s->gpu.image_bytes, direct);
+}
 
 int mcpt_scene_copy_kd(const mcpt_scene* s, uint32_t* nodes, uint32_t* leaf_ids, int32_t* kd_tris, float* geoms) {
     if (!s) return fail(MCPT_E_INVALID, "NULL scene");

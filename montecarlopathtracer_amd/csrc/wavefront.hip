@@ -50,8 +50,10 @@
 // the MCPT_WF_* tuning macros are in wf_device.hpp; bounce 0's packet extend
 // and its primary-list form (wf_extend_primary, wf_primary_lists) are in
 // wavefront_primary.hip, a translation unit with flags of its own, reached
-// through launch_wavefront_primary[_lists]; every other kernel and the host
-// pipeline are here.
+// through launch_wavefront_primary[_lists]; wf_primary_shade, which resolves
+// bounce 0 and shades it in place, is in wavefront_primary_shade.hip
+// (launch_wavefront_primary_shade); the shade's per-item code, which that kernel
+// shares, is wf_shade_item.hpp; every other kernel and the host pipeline are here.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -549,162 +551,11 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
             o = xyz(o4);
             d = xyz(d4);
         }
-        if (carried || i < total) {
-            float4 h = make_float4(0, 0, 0, 0);
-            // CV: miss -> 0; emitter -> color*Ka*ILLUM (:111-113); terminal query
-            // (:162-175); else scatter.  QE: miss / bounce >= 3*depth -> 0; roulette
-            // from bounce `depth` on; emitter -> color*Ka (rtx.hlsl:312-331)
-            V3 L = v3(0, 0, 0);
-            bool term = true;
-            if (htri >= 0 && depth != kNoRay) {
-                const GpuGeom& gm = geoms[__float_as_uint(tris[htri + 1].w)];
-                if (qe) {
-                    if ((int32_t)depth < 3 * kp.max_depth &&
-                        ((int32_t)depth < kp.max_depth || qe_roulette(sd, color))) {
-                        if (is_emitter(gm)) L = emitted(color, gm, 1.0f);
-                        else term = false;
-                    }
-                } else if ((int32_t)depth >= kp.max_depth || is_emitter(gm)) {
-                    L = emitted(color, gm, kp.illum);
-                } else {
-                    term = false;
-                }
-                if (!term) {
-                    c.shades++;
-                    tri_hit_params(o, d, tris[htri], tris[htri + 1], tris[htri + 2], h.x, h.y, h.z);
-                    if (qe) scatter<true>(gm, sc.normals, htri, h.y, h.z, h.x, 0, sd, color, o, d);
-                    else scatter<false>(gm, sc.normals, htri, h.y, h.z, h.x, kp.fresnel_kd, sd, color, o, d);
-                    cont = true;
-                    c.rays++;
-                    // the new ray against the scene's occluder boxes (lean renders:
-                    // n_miss_boxes != 0), in this order: box test, cull, direct, resolve,
-                    // clip selector
-                    // (o and d settled: only they, the throughput, the RNG state and pid are
-                    // live here, but with the test's operations free to move up into scatter
-                    // the queue-order shade took 81 VGPRs, one over its budget; 79 with this)
-                    o = v3(opaque(o.x), opaque(o.y), opaque(o.z));
-                    d = v3(opaque(d.x), opaque(d.y), opaque(d.z));
-                    if (wf.n_miss_boxes) {
-                        // (acc: the mask of the boxes hit)
-                        const uint32_t acc = scene_box_hits(o, d, v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), kp.best_init,
-                                                            wf.miss_box, wf.n_miss_boxes);
-                        // miss cull: the new ray misses every occluder box, so its walk would
-                        // return no hit and the next shade would store this zero; the ray stays
-                        // counted and is not enqueued
-                        if (!acc) {
-                            stq(&wf.radiance[pid], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                            cont = false;
-                        }
-                        // direct lists: a ray that hits one box, and a small one (direct_counts:
-                        // 4 bits per box, 0 = walk), can only hit that box's list
-                        const uint32_t box = (uint32_t)(__ffs((int)acc) - 1) & 7u;
-                        direct = acc != 0u && (acc & (acc - 1u)) == 0u && ((wf.direct_counts >> (4u * box)) & 15u) != 0u;
-                        // direct resolve: the extend's answer for a direct ray, operation for
-                        // operation -- begin_ray (its reciprocals are the box test's), then
-                        // the box's list in list order, in pairs, records from the LDS copy;
-                        // a hit goes to the next queue's tail with its ray, no hit ends the
-                        // path with the zero the next shade would store
-                        if (direct) {
-                            RayState r;
-                            r.o = o;
-                            r.d = d;
-                            if (begin_ray(r, sc, kp.best_init)) {
-                                const uint32_t n = (wf.direct_counts >> (4u * box)) & 15u;
-#pragma unroll
-                                for (uint32_t j = 0; j < kDirectK; j += 2u) {
-                                    if (j < n) {
-                                        const bool two = n - j >= 2u;
-                                        const uint32_t e0 = box * kDirectK + j, e1 = (j + 1u < kDirectK && two) ? e0 + 1u : e0;
-                                        const uint32_t k0 = ldk[e0], k1 = ldk[e1];
-                                        const float4* const ra = ldrec + 3u * e0;
-                                        const float4* const rb = ldrec + 3u * e1;
-                                        test_tri_pair<false>(r, ld_tri<true>(ra), ld_tri<true>(ra + 1), ld_tri<true>(ra + 2), k0,
-                                                             ld_tri<true>(rb), ld_tri<true>(rb + 1), ld_tri<true>(rb + 2), k1, two);
-                                    }
-                                }
-                            }
-                            rhit = r.htri;
-                            cont = false;
-                            // the terminal query's ray (CV: depth max_depth, QE: 3 * max_depth): the next
-                            // shade would only store its hit's emission (QE: zero) -- stored here, so
-                            // the last queue has no tail and the ray is neither written nor read again
-                            if (rhit >= 0 && (int32_t)(depth + 1u) >= tdepth) {
-                                V3 Lt = v3(0, 0, 0);
-                                if (!qe) {
-                                    uint32_t gi = 0;                  // the hit record's geometry, from the copy
-#pragma unroll
-                                    for (uint32_t j = 0; j < kDirectK; j++)
-                                        if (ldk[box * kDirectK + j] == (uint32_t)rhit)
-                                            gi = __float_as_uint(ldrec[3u * (box * kDirectK + j) + 1u].w);
-                                    Lt = emitted(color, geoms[gi], kp.illum);
-                                }
-                                stq(&wf.radiance[pid], make_float4(Lt.x, Lt.y, Lt.z, 0.0f));
-                                rhit = -1;
-                            } else if (rhit < 0)
-                                stq(&wf.radiance[pid], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                        }
-                        // terminal cull (wf.shade_cull; render_launch.hpp "Terminal cull"): a walking
-                        // ray made for the terminal query that can add no radiance -- wf_cull_terminal's
-                        // own rule -- gets the zero its shade would store and is not enqueued; it stays
-                        // counted.  (A resolved one was finished above.)
-                        if (!SORTB && wf.shade_cull && (qe || wf.n_cull_boxes) && cont && (int32_t)(depth + 1u) == tdepth &&
-                            !terminal_ray_adds(qe, o, d, kp.best_init, wf.cull_box, wf.n_cull_boxes)) {
-                            stq(&wf.radiance[pid], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                            cont = false;
-                        }
-                        // clip walk: a walking ray through at least one box without a list and
-                        // at most one with a list carries its box mask (never a direct ray, whose
-                        // one box has a list, nor a culled one, whose mask is 0)
-                        {
-                            const uint32_t lm = acc & ~unlisted;
-                            if ((acc & unlisted) != 0u && (lm & (lm - 1u)) == 0u) depth |= acc << kDirectShift;
-                        }
-                    }
-                }
-            }
-            if (term) stq(&wf.radiance[pid], make_float4(L.x, L.y, L.z, 0.0f));   // (kNoRay slots: 0)
-        }
-        ndirect += (uint32_t)__popcll(__ballot(direct));        // (wave-uniform: a scalar register)
-        // next ray: the wave's continuing lanes take consecutive slots of queue b+1
-        const uint64_t m = __ballot(cont);
-        if (m) {
-            const int leader = __ffsll((unsigned long long)m) - 1;
-            uint32_t b0 = 0;
-            if (lane == leader) b0 = atomicAdd(&lnext, (uint32_t)__popcll(m));
-            b0 = lane_bcast(b0, leader);
-            if (cont) {
-                const size_t ji = seg0 + b0 + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                stq(&qb2[qf(ji, kQO, qs)], pack(o, pid));
-                stq(&qb2[qf(ji, kQD, qs)], pack(d, depth + 1u));
-                stq(&qb2[qf(ji, kQPS, qs)], pack(color, sd));
-            }
-        }
-        // carry: the resolved ray stays in this lane, as the words the tail would hold, and
-        // enters the shading code above with its hit id in the wave's next iteration --
-        // neither written nor read back; at most kCarryMax times in a row
-        if constexpr (!SORTB) {
-            carry = wf.shade_cull && rhit >= 0 && (kCarryMax == ~0u || nchain < kCarryMax);
-            if constexpr (kCarryMax != ~0u) nchain = carry ? nchain + 1u : 0u;
-        }
-        // resolved rays that are not carried: the wave's take 64 consecutive slots from the
-        // segment's last one downward, lanes ascending inside them, with their hit ids (head
-        // and tail together hold at most this queue's rays, <= seg: they never meet)
-        const bool totail = rhit >= 0 && !carry;
-        const uint64_t mr = __ballot(totail);
-        if (mr) {
-            const int leader = __ffsll((unsigned long long)mr) - 1;
-            const uint32_t nr = (uint32_t)__popcll(mr);
-            uint32_t t0 = 0;
-            if (lane == leader) t0 = atomicAdd(&ltail, nr);
-            t0 = lane_bcast(t0, leader);
-            if (totail) {
-                const size_t ji = seg0 + (wf.seg - t0 - nr) + (uint32_t)__popcll(mr & ((1ull << lane) - 1ull));
-                stq(&qb2[qf(ji, kQO, qs)], pack(o, pid));
-                stq(&qb2[qf(ji, kQD, qs)], pack(d, depth + 1u));
-                stq(&qb2[qf(ji, kQPS, qs)], pack(color, sd));
-                reinterpret_cast<int32_t*>(qb2 + qf(0, kQHIT, qs))[ji] = rhit;
-            }
-        }
+        // the per-item code and the enqueue: one source for this kernel and wf_primary_shade
+        const bool live = carried || i < total;
+#define MCPT_SHADE_FUSED 0
+#include "wf_shade_item.hpp"
+#undef MCPT_SHADE_FUSED
     }
     flush_counters(c, kp.stats);
     if (lane == 0 && ndirect) atomicAdd(kp.stats + kStatDirect, (unsigned long long)ndirect);
@@ -1068,6 +919,14 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
                 const size_t llds = in_lds ? wf_lds_extend_bytes(kb.scene) : 0;
                 if (lists && packet && b == 0 && whole_tiles(wf.v0, wf.nb)) {
                     wf.tile_cand = wf_in[0].tile_cand;
+                    // primary shade: where the queue-order shade culls and carries, the kernel that
+                    // resolves the groups also shades them and fills queue 1 -- no bounce-0 shade
+                    // (LDS: the lean extend's, the table only where the lists are active)
+                    if (wf.shade_cull) {
+                        e = launch_wavefront_primary_shade(kb, wf, (int)nseg,
+                                                           primary_shade_lds_bytes(kb.scene.image_bytes, direct), bs);
+                        continue;
+                    }
                     e = launch_wavefront_primary_lists(kb, wf, (int)nseg, llds, bs);
                 } else if (packet && b == 0) {
                     e = launch_wavefront_primary(kb, wf, (int)nseg, llds, bs);

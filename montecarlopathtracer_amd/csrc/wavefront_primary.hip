@@ -4,6 +4,11 @@
 // launch_wavefront).  A translation unit of its own so that it can take its own
 // code-generation flags (_build.py: wave-uniform control flow left
 // unstructurized); what it shares with wavefront.hip is wf_device.hpp.
+// wf_primary_shade, the list form that also shades bounce 0, is in a sibling
+// translation unit, wavefront_primary_shade.hip (other flags, and this file's
+// kernels keep their code); it shares the walk and the listed groups' pair
+// tests with the kernels here as source text: wf_primary_walk.hpp and
+// wf_primary_pairs.hpp, both included by wf_primary_body.hpp.
 #include "wf_device.hpp"
 
 namespace mcpt {
@@ -27,7 +32,8 @@ namespace {
 // the spill area) with a wave-uniform position; a lane's copy of an entry
 // carries its interval, or tmax = NaN if the lane is not in that subtree.
 //
-// The kernel's body is wf_primary_body.hpp, included once per kernel below:
+// The kernel's body is wf_primary_body.hpp (the walk itself: wf_primary_walk.hpp,
+// which it includes), included once per kernel below:
 // source text, not a function, so that wf_extend_primary's code stays what it
 // was without the second kernel (inlined from a shared function, its epilogue
 // came out one instruction shorter).

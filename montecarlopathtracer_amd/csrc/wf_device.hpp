@@ -1,7 +1,8 @@
 // wf_device.hpp -- what the wavefront pipeline's translation units share:
 // wavefront.hip (generate, extend, shade, cull, candidates, accumulate and the
-// host pipeline) and wavefront_primary.hip (bounce 0's packet extend and its
-// primary-list form, compiled with flags of their own).  The queue layout, the
+// host pipeline), wavefront_primary.hip (bounce 0's packet extend and its
+// primary-list form, compiled with flags of their own) and
+// wavefront_primary_shade.hip (the list form that also shades bounce 0).  The queue layout, the
 // dealing of paths to segments, the MCPT_WF_* tuning macros with their
 // measurements, and the two launch entry points of wavefront_primary.hip.
 // rayquery.hip takes the extend's layouts and tuning defaults from here.
@@ -25,6 +26,9 @@ using namespace trace;
 hipError_t launch_wavefront_primary(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
                                     hipStream_t st);
 hipError_t launch_wavefront_primary_lists(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
+                                          hipStream_t st);
+// ... and the list form that also shades bounce 0 (lds: the lean LDS extend's with its direct table)
+hipError_t launch_wavefront_primary_shade(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
                                           hipStream_t st);
 
 namespace {

@@ -347,6 +347,8 @@ class Scene:
         d["extend_rays"] = int(lib().mcpt_scene_extend_rays(self.handle))
         # of those, the rays an extend started with a box selector (0: built without the clip walk)
         d["clipped_rays"] = int(lib().mcpt_scene_clipped_rays(self.handle))
+        # paths whose bounce 0 the kernel that resolved their primary rays also shaded (0: every other render)
+        d["primary_shaded"] = int(lib().mcpt_scene_primary_shaded(self.handle))
         return d
 
     def primary_tile_classes(self):

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """SQ_INSTS_VALU (or another counter) of a rocprofv3 --pmc pass over wavefront
 renders, summed per kernel class: extend0 (bounce 0: wf_extend_primary /
-wf_primary_lists), extend, shade, cull_terminal, other.
+wf_primary_lists), extend0+shade0 (wf_primary_shade: compare it with extend0 plus
+bounce 0's share of shade in earlier rows), extend, shade, cull_terminal, other.
 usage: valu_by_class.py DIR [COUNTER]"""
 import csv
 import glob
@@ -10,6 +11,8 @@ from collections import defaultdict
 
 
 def kernel_class(name):
+    if "wf_primary_shade" in name:         # bounce 0's extend and shade in one kernel
+        return "extend0+shade0"
     if "wf_extend_primary" in name or "wf_primary_lists" in name:
         return "extend0"
     if "wf_extend" in name:

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Per-bounce extend / shade times from a rocprofv3 kernel trace of wavefront
 renders on ONE stream (kernels serialized): dispatches are grouped per batch
-(wf_generate, or a generate-free bounce-0 extend -- wf_extend_primary, or
-wf_primary_lists, which resolves the tiles' candidate lists -- starts one) and
+(wf_generate, or a generate-free bounce-0 extend -- wf_extend_primary,
+wf_primary_lists, which resolves the tiles' candidate lists, or wf_primary_shade,
+which also shades bounce 0 and is reported as bounce 0's extend with a shade of
+0, so that the two together compare with earlier rows -- starts one) and
 indexed by bounce; wf_cull_terminal (the terminal cull in front of the last
 extend) and wf_tile_candidates (the primary lists' candidate pass, once per
 render) are summed on their own.  usage: wf_bounce_times.py DIR"""
@@ -24,10 +26,18 @@ def main(d):
     b_ext = b_sh = -1
     batches = 0
     for t0, t1, name in rows:
-        if "wf_generate" in name or "wf_extend_primary" in name or "wf_primary_lists" in name:
+        if ("wf_generate" in name or "wf_extend_primary" in name or "wf_primary_lists" in name
+                or "wf_primary_shade" in name):
             b_ext = b_sh = -1
             batches += 1
-        if "wf_cull_terminal" in name:
+        if "wf_primary_shade" in name:
+            # bounce 0's extend + shade in one kernel: reported as bounce 0's extend, its shade 0,
+            # so that the row's sum compares with earlier rows' extend + shade of bounce 0
+            b_ext += 1
+            b_sh += 1
+            ext[b_ext].append((t1 - t0) / 1e6)
+            sh[b_sh].append(0.0)
+        elif "wf_cull_terminal" in name:
             cull.append((t1 - t0) / 1e6)
         elif "wf_tile_candidates" in name:
             cand.append((t1 - t0) / 1e6)
