@@ -394,7 +394,21 @@ int mcpt_shard_pixels(const mcpt_render_params* p, int32_t* xy);      /* count*2
  * o, d = n*3 floats (host); tri_out[i] = kd triangle id (scene_copy_kd's
  * numbering) or -1; hit_out = n*3 floats beta, gamma, t (t = 0 on a miss);
  * t_max = the initial closest t (FLT_MAX in CVMCTracer, 10000 in QuinEngine).
- * stats (may be NULL): rays, inner/leaf visits, leaf refs, tri tests.       */
+ * stats (may be NULL): rays, inner/leaf visits, leaf refs, tri tests.
+ * Ray preconditions (this entry and the device queries below): finite
+ * origins, anywhere -- inside the scene's box, on its faces or outside it --
+ * and finite directions, not all zero, whose every component is zero (+0.0
+ * or -0.0 alike) or has a finite float reciprocal; |d| >= 2^-126 (any normal
+ * float) suffices.  Directions need not have unit length: t comes back in
+ * units of the given direction, and scaling a direction by 2^k divides t by
+ * 2^k and changes nothing else (pinned for |k| <= 40).  Inside this range the
+ * answer is the brute force's of CUTracer.cu:44-96, bit for bit, except for
+ * origins exactly on a triangle's edge.  Outside
+ * it -- a subnormal component whose reciprocal overflows -- the entries
+ * return the ordered walk's answer, which is defined and the same on every
+ * layout but can miss a hit the brute force finds at t near FLT_MAX; NaN and
+ * infinite rays are not supported.  (tests/test_ray_contract_cpu.py,
+ * tests/test_gpu_ray_contract.py)                                          */
 int mcpt_intersect(mcpt_scene* s, int64_t n, const float* o, const float* d, float t_max,
                    int32_t* tri_out, float* hit_out, mcpt_render_stats* stats);
 /* reserve device workspace for p so mcpt_render_device allocates nothing
@@ -561,7 +575,11 @@ int mcpt_render_adaptive_device(mcpt_scene*, const mcpt_render_params*, const mc
  * layout: the LDS image, or the global-memory image with the child-box cull),
  * in a persistent kernel built like the wavefront extend.  Asynchronous on a
  * stream; after mcpt_scene_reserve_rays or a first query nothing is allocated.
- * Preconditions as mcpt_intersect: finite origins, finite non-zero directions;
+ * Preconditions as mcpt_intersect ("Ray preconditions" there): finite origins,
+ * inside or outside the scene's box; finite directions, not all zero, of any
+ * length (t in units of the given direction), each component zero of either
+ * sign or with a finite float reciprocal (|d| >= 2^-126 suffices) -- outside
+ * that range the walk's answer, not the brute force's, is returned;
  * t_max finite or FLT_MAX (a t_max <= 0 simply misses).
  * MCPT_E_INVALID, before anything is launched or allocated and in this order:
  * a NULL scene, n < 0, a NULL required pointer with n > 0, a field of the
@@ -614,7 +632,9 @@ int mcpt_scene_reserve_rays(mcpt_scene*);
  * loop (CVMCTracer mode: max_depth scatters and the terminal query), samplers,
  * RNG and traversal, started from the caller's rays instead of the pinhole
  * camera.  Directions are used exactly as given (not re-normalized; the BSDF
- * arithmetic assumes unit length).  Preconditions as mcpt_trace_device.
+ * arithmetic assumes unit length: unlike the hit queries, which take any
+ * length, a radiance query wants unit directions).  Otherwise preconditions
+ * as mcpt_trace_device.
  * Ray i has the stream id id_i = d_stream[i], or i without d_stream.  Sample s
  * (global index spp_offset + s) starts from rng_init(id_i, TEA16(seed),
  * spp_offset + s), draws and drops the two uniforms a render spends on its

@@ -101,6 +101,10 @@ def lib():
         L.orc_sample_fresnel.argtypes = [f32p, f32p, C.c_float, C.c_float, f32p, f32p]
         L.orc_sample_phong_qe.argtypes = [f32p, f32p, C.c_float, f32p, f32p]
         L.orc_sample_fresnel_qe.argtypes = [f32p, f32p, C.c_float, C.c_float, f32p, f32p]
+        L.orc_f16_dir.restype = C.c_uint16
+        L.orc_f16_dir.argtypes = [C.c_float, C.c_int]
+        L.orc_f16_to_f32.restype = C.c_float
+        L.orc_f16_to_f32.argtypes = [C.c_uint16]
         L.orc_tan_half_fov.restype = C.c_float
         L.orc_tan_half_fov.argtypes = [C.c_float]
         L.orc_qe_proj.restype = None
@@ -208,6 +212,15 @@ class Scene:
         if rc != 0:
             raise RuntimeError("oracle render failed")
         return out, c.as_dict()
+
+
+def f16_outward(x, direction):
+    """float32 values of x rounded to binary16 toward -inf (direction < 0) / +inf (> 0):
+    the bounds of the child boxes the ordered walk's cull tests (orc_f16_dir)"""
+    L = lib()
+    x = np.asarray(x, np.float32)
+    out = [L.orc_f16_to_f32(L.orc_f16_dir(float(v), int(direction))) for v in x.ravel()]
+    return np.array(out, np.float32).reshape(x.shape)
 
 
 def camera_basis(eye, direction, up):

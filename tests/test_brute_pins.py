@@ -6,9 +6,10 @@ Every GPU parity test compares the kernel with the oracle's ordered walk
 scenes 02/03) both sides also run the fp16 child-box cull.  Here that walk --
 with the cull on and off -- is held to the brute-force restatement of
 CUTracer.cu:44-96 (every geometry, every triangle, strict t < tmin, ties in
-loop order) on >= 100k rays per scene: random rays, rays aimed at triangle
-interiors, axis-parallel rays, origins exactly on KD split planes, origins on
-triangle edges, rays grazing a triangle's plane and rays through vertices.
+loop order) on 112 500 rays per scene (tests/_raysets.py ray_sets(., 100 000)):
+25 000 random rays, 25 000 aimed at triangle interiors and 12 500 each of
+axis-parallel rays, origins exactly on KD split planes, origins on triangle
+edges, rays grazing a triangle's plane and rays through vertices.
 Hits are compared bit for bit (triangle, geometry, beta, gamma, t, hit point).
 
 scene02 pin: the reference's own MC.docx Figure 3 ("Scene 2 with luminance 10
@@ -29,7 +30,8 @@ GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 THREADS = min(os.cpu_count() or 8, 16)
 
 
-from _raysets import ray_sets as _ray_sets  # noqa: E402  (shared with the GPU query test)
+from _exact_hits import float_artifact as _float_artifact  # noqa: E402  (shared with test_ray_contract_cpu.py)
+from _raysets import EDGE_ORIGINS, ray_sets as _ray_sets  # noqa: E402  (shared with the GPU query tests)
 
 
 @pytest.fixture(scope="module")
@@ -44,43 +46,6 @@ def oscene(oracle_mod):
     return get
 
 
-def _exact_cramer(kv, tri, o, d):
-    """CUTracer.cu:58-92's beta, gamma, t in exact rational arithmetic (float inputs)."""
-    from fractions import Fraction as F
-    a, b, c = ([F(float(x)) for x in v] for v in kv[tri])
-    oo = [F(float(x)) for x in o]
-    dd = [F(float(x)) for x in d]
-
-    def det(m):
-        return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6])
-    col = lambda u, v, w: [u[0], v[0], w[0], u[1], v[1], w[1], u[2], v[2], w[2]]  # noqa: E731
-    ab = [a[i] - b[i] for i in range(3)]
-    ac = [a[i] - c[i] for i in range(3)]
-    ao = [a[i] - oo[i] for i in range(3)]
-    dA = det(col(ab, ac, dd))
-    if dA == 0:
-        return None
-    return det(col(ao, ac, dd)) / dA, det(col(ab, ao, dd)) / dA, det(col(ab, ac, ao)) / dA
-
-
-def _float_artifact(kv, o, d, tb, hb, tk, hk):
-    """A brute-force / KD disagreement that exact arithmetic resolves: the float
-    Cramer test accepted a triangle that the exact test rejects, the two hits'
-    float t order differs from their exact order, or the hit touches the origin
-    (t < 1e-5: the origin lies on a triangle edge)."""
-    if (tb >= 0 and hb[2] < 1e-5) or (tk >= 0 and hk[2] < 1e-5):
-        return True
-    ex = {}
-    for t in {int(tb), int(tk)} - {-1}:
-        e = _exact_cramer(kv, t, o, d)
-        if e is None or not (e[0] > 0 and e[1] > 0 and e[0] + e[1] < 1 and e[2] > 0):
-            return True            # the float test accepted an exact miss
-        ex[t] = e[2]
-    if tb >= 0 and tk >= 0:
-        return ex[int(tb)] >= ex[int(tk)]   # exact order disagrees with the float order
-    return False
-
-
 @pytest.mark.parametrize("name", ["scene02", "scene03", "cornell_bunny70k"])
 def test_ordered_walk_and_box_cull_equal_brute_force(oscene, oracle_mod, name):
     """Bit-identical hits on every ray of the random, aimed, axis-parallel,
@@ -92,11 +57,9 @@ def test_ordered_walk_and_box_cull_equal_brute_force(oscene, oracle_mod, name):
     can reproduce (the reference's own KD walk, rtx.hlsl:144-211, differs from
     its brute force on more of them)."""
     s = oscene(name)
-    o, d = _ray_sets(s, 100_000, seed=17)
-    fam5 = np.zeros(o.shape[0], bool)
-    k = 100_000 // 8
-    fam5[6 * k:7 * k] = True                                # origins on triangle edges
-    assert o.shape[0] >= 100_000 - 100
+    o, d, fam = _ray_sets(s, 100_000, seed=17, families=True)
+    fam5 = fam == EDGE_ORIGINS                              # origins on triangle edges
+    assert o.shape[0] >= 112_500 - 100 and (np.bincount(fam, minlength=8)[1:] >= 12_500 - 100).all()
     tb, gb, hb, cb = s.intersect(o, d, oracle_mod.BRUTE, threads=THREADS)
     assert 0.3 < (tb >= 0).mean() < 1.0
     kv = s.kd_verts()
@@ -167,10 +130,8 @@ def test_sah_tree_walk_equals_brute_force(oracle_mod, name):
     start on a triangle edge (family 5), as for the reference tree."""
     from montecarlopathtracer_amd.scenes import scene_path
     s = oracle_mod.Scene(scene_path(name), kd_build="sah")
-    o, d = _ray_sets(s, 60_000, seed=23)
-    fam5 = np.zeros(o.shape[0], bool)
-    k = 60_000 // 8
-    fam5[6 * k:7 * k] = True
+    o, d, fam = _ray_sets(s, 60_000, seed=23, families=True)
+    fam5 = fam == EDGE_ORIGINS
     tb, gb, hb, _ = s.intersect(o, d, oracle_mod.BRUTE, threads=THREADS)
     kv = s.kd_verts()
     for boxes in (0, 1):

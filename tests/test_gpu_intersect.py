@@ -1,7 +1,8 @@
 """Device closest-hit queries (mcpt_intersect: the render traversal run on
-caller-given rays) against the CPU oracle on the adversarial ray families of
-tests/_raysets.py -- origins exactly on KD split planes, axis-parallel and
-grazing rays, origins on triangle edges, rays through vertices.
+caller-given rays) against the CPU oracle on the seven adversarial ray families
+of tests/_raysets.py ray_sets (112 500 rays for N = 100 000) -- random and aimed
+rays, origins exactly on KD split planes, axis-parallel and grazing rays,
+origins on triangle edges, rays through vertices.
 
 Held bit for bit (triangle id, beta, gamma, t) and counter for counter to the
 oracle's ordered walk with the same child-box cull the scene's layout uses
@@ -13,7 +14,7 @@ arithmetic -- to the brute force of CUTracer.cu:44-96.
 import numpy as np
 import pytest
 
-from _raysets import ray_sets
+from _raysets import EDGE_ORIGINS, ray_sets
 
 pytestmark = pytest.mark.gpu
 
@@ -26,7 +27,8 @@ def test_device_hits_equal_oracle_walk_and_brute_force(mcpt, oracle_mod, name):
     scene = mcpt.Scene(mcpt.ObjModel(path))
     boxes = int(scene.info()["node_boxes"])
     o_s = oracle_mod.Scene(path)
-    o, d = ray_sets(o_s, N, seed=23)
+    o, d, fam = ray_sets(o_s, N, seed=23, families=True)
+    assert (np.bincount(fam, minlength=8)[1:] >= N // 8 - 100).all()      # all seven families, vertex rays included
     tri, hit, st = scene.intersect(o, d)
     tk, gk, hk, ck = o_s.intersect(o, d, oracle_mod.KD_ORDERED, node_boxes=boxes, threads=8)
     assert np.array_equal(tri, tk)
@@ -38,9 +40,7 @@ def test_device_hits_equal_oracle_walk_and_brute_force(mcpt, oracle_mod, name):
         assert st[k] == ck[k], (k, st[k], ck[k])
     # brute force: equal off the triangle-edge origins (family 5)
     tb, gb, hb, _ = o_s.intersect(o, d, oracle_mod.BRUTE, threads=8)
-    k5 = N // 8
-    fam5 = np.zeros(o.shape[0], bool)
-    fam5[6 * k5:7 * k5] = True
+    fam5 = fam == EDGE_ORIGINS
     bad = np.nonzero((tb != tri) | (np.where(tb[:, None] >= 0, hb[:, :3], 0.0).astype(np.float32).view(np.uint32)
                                     != hit_g.view(np.uint32)).any(axis=1))[0]
     assert not (~fam5[bad]).any(), bad[~fam5[bad]][:10]

@@ -39,7 +39,10 @@ def _inputs(n=200000, seed=0):
                         np.exp(r.uniform(-80, 80, n - n // 2 - n // 4))]).astype(np.float32)
     b = np.concatenate([r.uniform(-10, 10, n // 2), r.uniform(0.5, 2, n // 4),
                         np.exp(r.uniform(-40, 40, n - n // 2 - n // 4))]).astype(np.float32)
-    return a, b
+    # the ends of the float range: subnormal operands, +-0.0, subnormal and overflowing quotients
+    from test_div_shared import edge_pairs
+    ea, eb = edge_pairs()
+    return np.concatenate([a, ea]), np.concatenate([b, eb])
 
 
 def test_float_div_rcp_sqrt_exact(probe):
@@ -61,12 +64,12 @@ def test_shared_div_formulas_exact(probe):
     """ops 12 / 13: the two recip_shared variants (IEEE double 1/d; v_rcp_f64 +
     two Newton steps) give IEEE f32 a / d bit for bit (tests/test_div_shared.py)."""
     from test_div_shared import same_bits, shared_cases
-    a, d = shared_cases(400_000, seed=11)
-    with np.errstate(all="ignore"):
-        ref = a / d
-    for op in (12, 13):
-        o, _, _ = probe(op, a, d)
-        assert same_bits(o, ref), op
+    for a, d in (shared_cases(400_000, seed=11), _inputs()):     # (both end with test_div_shared.edge_pairs)
+        with np.errstate(all="ignore"):
+            ref = a / d
+        for op in (12, 13):
+            o, _, _ = probe(op, a, d)
+            assert same_bits(o, ref), op
 
 
 def test_double_div_exact(probe):
