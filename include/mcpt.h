@@ -568,6 +568,37 @@ int mcpt_render_adaptive(mcpt_scene*, const mcpt_render_params*, const mcpt_adap
  * call a further call allocates nothing.                                      */
 int mcpt_render_adaptive_device(mcpt_scene*, const mcpt_render_params*, const mcpt_adaptive_params*,
                                 float* d_fb_rgba, float* d_var_rgba, uint32_t* d_pass_count, void* hip_stream);
+/* The general form: the pair above with p->pipeline honoured.  (The pair above
+ * is the megakernel-only form, kept for its callers: it refuses the wavefront
+ * as it always did.  Additions; the ABI stays 9.)  Arguments, buffers,
+ * semantics, checks and their order are the pair's, minus the pipeline
+ * refusal.  With MCPT_PIPELINE_MEGAKERNEL the calls are the pair's, same code
+ * path, bits and counters.  With MCPT_PIPELINE_WAVEFRONT pass 0 and every
+ * full-frame pass before min_passes (without force_list) are the wavefront's
+ * uniform mcpt_render_var renders as they are, primary lists, primary shade
+ * and culls included; a listed pass of n pixels is a wavefront render of a
+ * frame of n listed pixels: its generate kernel looks each pixel up in the
+ * list and writes an explicit queue 0, bounce 0 runs the ordinary extend and
+ * shade (no packet extend, primary lists or primary shade), and the miss
+ * cull, direct lists, direct resolve, clip walk and terminal cull stay on.
+ * wf_batch, wf_streams, wf_refill, wf_group_shift, wf_sort, wf_mem_limit, lean
+ * and tile are honoured as by a wavefront mcpt_render_var; a listed pass runs
+ * on pass 0's streams with the default batch of a frame of n pixels (an
+ * explicit wf_batch as asked), never more than pass 0's, inside pass 0's
+ * workspace.  fb, var and pass_count are the megakernel's bit for bit, as are
+ * paths (spp x the sum of pass_count), renders and rays; a counting render's
+ * (lean = 0) inner_visits, leaf_visits, leaf_refs and tri_tests too, a lean
+ * one's read 0 as for every lean wavefront render.  direct_rays, extend_rays
+ * and clipped_rays accumulate over the passes; primary_shaded counts the
+ * eligible paths of the full-frame passes only (a listed pass adds 0).
+ * mcpt_scene_primary_tile_classes reports the last pass: 0 0 0 after a render
+ * whose last pass was listed, as after any render that did not use the lists.
+ * Still MCPT_E_UNSUPPORTED, with the pair's messages: QuinEngine mode, a
+ * capturing stream, shards, packed output, a multi-device scene, gather = RCCL. */
+int mcpt_render_adaptive_ex(mcpt_scene*, const mcpt_render_params*, const mcpt_adaptive_params*,
+                            float* fb_rgb, float* var_rgba, uint32_t* pass_count, mcpt_render_stats* stats);
+int mcpt_render_adaptive_ex_device(mcpt_scene*, const mcpt_render_params*, const mcpt_adaptive_params*,
+                                   float* d_fb_rgba, float* d_var_rgba, uint32_t* d_pass_count, void* hip_stream);
 
 /* ---- device ray queries: closest hit and any hit over ray buffers ------------ */
 /* The renders' traversal for rays of the caller's own, in device memory: a

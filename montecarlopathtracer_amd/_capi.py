@@ -206,6 +206,11 @@ _SIGS = {
                                        C.POINTER(RenderStats)]),
     "mcpt_render_adaptive_device": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(AdaptiveParamsC), _vp, _vp,
                                               _vp, _vp]),
+    "mcpt_render_adaptive_ex": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(AdaptiveParamsC),
+                                          C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                          C.POINTER(RenderStats)]),
+    "mcpt_render_adaptive_ex_device": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(AdaptiveParamsC), _vp,
+                                                 _vp, _vp, _vp]),
     "mcpt_trace_params_default": (None, [C.POINTER(TraceParamsC)]),
     "mcpt_trace_device": (C.c_int, [_vp, C.POINTER(TraceParamsC), C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcpt_occluded_device": (C.c_int, [_vp, C.POINTER(TraceParamsC), C.c_int64, _vp, _vp, _vp, _vp, _vp]),

@@ -237,6 +237,9 @@ void grow_spill(mcpt_scene& s, int sets, bool capturing);
 uint64_t tail_split(uint64_t lanes, int64_t per_lane, int64_t exact, uint32_t total_units, uint32_t chunk);
 uint64_t tail_units_for(const mcpt_scene& s, const Plan& pl);
 Plan make_plan(const mcpt_scene& s, const mcpt_render_params* p);
+uint32_t wf_batch_capacity(const mcpt_scene& s, const mcpt_render_params* p, uint64_t work, uint32_t chunk, int nstr);
+void prepare_wavefront_list(mcpt_scene& s, Plan& pl, const Plan& pass0, uint32_t n, const mcpt_render_params* p,
+                            mcpt::WfParams* out);
 void fit_wavefront(const mcpt_scene& s, Plan& pl);
 void prepare_workspace(mcpt_scene& s, Plan& pl, bool tail_split = false, int spill_sets = 1);
 uint32_t* tile_classes(const mcpt_scene& s);

@@ -306,29 +306,56 @@ Plan make_plan(const mcpt_scene& s, const mcpt_render_params* p) {
     pl.tail_exact = p->tail_units;
     pl.wf_mem_limit = p->wf_mem_limit;
     {
-        // default batch: big (120 B of queues per path and stream; fewer launches,
-        // shorter relative tails).  One stream: C2 2^24 5.59, 2^25 6.43, 2^26 7.07,
-        // 2^27 7.31, 2^28 7.24; C4 (256 spp) 2^24 2.90, 2^26 3.45, 2^28 4.31 G
-        // rays/s.  Global-memory scenes on 4 streams: 2^27 each (see wavefront_streams);
-        // LDS scenes on 2 streams: 2^28 each (C2 2 x 2^27 12.90, 2 x 2^28 13.03,
-        // 3 x 2^27 13.06, 4 x 2^27 12.55 G rays/s, two rounds each; 86 GB of queues)
         const uint64_t work = std::max<uint64_t>(npix, 1) * std::max<uint64_t>(p->spp, chunk);
         pl.work = npix * p->spp;
         const int nstr = wavefront_streams(s, work, p);
         pl.wf_streams = nstr;
-        const bool big = nstr == 1 || (!s.gpu.node_boxes && nstr == 2);
-        uint64_t cap = p->wf_batch ? p->wf_batch : (big ? (1u << 28) : (1u << 27));
-        // a default batch gives every stream a batch of its own (one rank's C2
-        // share at 8 GPUs, 2^27 paths: one 2^27 batch 9.26, two 2^26 12.61, four
-        // 2^25 12.13 G rays/s; the megakernel 11.22)
-        if (!p->wf_batch && nstr > 1) cap = std::min<uint64_t>(cap, (work + nstr - 1) / nstr);
-        cap = std::max<uint64_t>(cap, chunk);                        // at least one pixel per batch
-        cap = std::min<uint64_t>(cap, work);
-        cap = std::min<uint64_t>(cap, uint64_t(1) << 28);               // u32 slot arithmetic; 120 B per path
-        pl.wf_capacity = static_cast<uint32_t>(cap);
+        pl.wf_capacity = wf_batch_capacity(s, p, work, chunk, nstr);
         pl.wf_batch_explicit = p->wf_batch != 0;
     }
     return pl;
+}
+
+// Paths per wavefront batch of a frame of `work` paths (pixels x samples) on nstr
+// streams, before it is fitted to memory: p->wf_batch as asked, else the default.
+// Default batch: big (120 B of queues per path and stream; fewer launches,
+// shorter relative tails).  One stream: C2 2^24 5.59, 2^25 6.43, 2^26 7.07,
+// 2^27 7.31, 2^28 7.24; C4 (256 spp) 2^24 2.90, 2^26 3.45, 2^28 4.31 G
+// rays/s.  Global-memory scenes on 4 streams: 2^27 each (see wavefront_streams);
+// LDS scenes on 2 streams: 2^28 each (C2 2 x 2^27 12.90, 2 x 2^28 13.03,
+// 3 x 2^27 13.06, 4 x 2^27 12.55 G rays/s, two rounds each; 86 GB of queues)
+uint32_t wf_batch_capacity(const mcpt_scene& s, const mcpt_render_params* p, uint64_t work, uint32_t chunk, int nstr) {
+    const bool big = nstr == 1 || (!s.gpu.node_boxes && nstr == 2);
+    uint64_t cap = p->wf_batch ? p->wf_batch : (big ? (1u << 28) : (1u << 27));
+    // a default batch gives every stream a batch of its own (one rank's C2
+    // share at 8 GPUs, 2^27 paths: one 2^27 batch 9.26, two 2^26 12.61, four
+    // 2^25 12.13 G rays/s; the megakernel 11.22)
+    if (!p->wf_batch && nstr > 1) cap = std::min<uint64_t>(cap, (work + nstr - 1) / nstr);
+    cap = std::max<uint64_t>(cap, chunk);                        // at least one pixel per batch
+    cap = std::min<uint64_t>(cap, work);
+    cap = std::min<uint64_t>(cap, uint64_t(1) << 28);               // u32 slot arithmetic; 120 B per path
+    return static_cast<uint32_t>(cap);
+}
+
+// A wavefront render of a frame of n listed pixels (adaptive sampling's listed
+// passes), planned inside the workspace of the pass over every pixel: pl is
+// make_plan of the pass's params, pass0 the fitted plan of pass 0.  The stream
+// count is pass 0's; the batch is the one a frame of n pixels would get
+// (an explicit wf_batch as asked), never above the capacity pass 0 was fitted
+// to, so the queues, partial sums and spill areas pass 0 holds suffice and
+// nothing is allocated.
+void prepare_wavefront_list(mcpt_scene& s, Plan& pl, const Plan& pass0, uint32_t n, const mcpt_render_params* p,
+                            mcpt::WfParams* out) {
+    mcpt::KernelParams& k = pl.kp;
+    k.npix_local = n;
+    k.total_units = n * k.nchunks;
+    k.div_npix = mcpt::FastDiv::make(n);
+    pl.work = uint64_t(n) * k.spp;
+    pl.wf_streams = pass0.wf_streams;
+    pl.wf_capacity = std::min(wf_batch_capacity(s, p, pl.work, k.chunk, pl.wf_streams), pass0.wf_capacity);
+    prepare_workspace(s, pl, false, pl.sets());
+    prepare_wavefront(s, pl, pl.sets(), out);
+    ensure_wf_streams(s, pl.sets());
 }
 
 // Fit the wavefront's queues into device memory: the budget is

@@ -84,10 +84,28 @@ Timing acquire_timing(mcpt_scene& s, bool capturing) {
     return t;
 }
 
+// the wavefront's streams for a render on st: the caller's, then the scene's side streams
+mcpt::WfStreams wf_streams_on(const mcpt_scene& s, int n, hipStream_t st) {
+    mcpt::WfStreams wst{};
+    wst.n = n;
+    wst.st[0] = st;
+    wst.fork = s.wf_fork;
+    for (int i = 1; i < wst.n; i++) {
+        wst.st[i] = s.wf_stream[i];
+        wst.join[i] = s.wf_join[i];
+    }
+    return wst;
+}
+int wf_queries(const mcpt::KernelParams& kp) {
+    return kp.mode == MCPT_MODE_QUINENGINE ? 3 * kp.max_depth + 1 : kp.max_depth + 1;
+}
+
 // d_var: also the per-pixel variance of this call's pixel mean (variance.hip),
-// from the partial sums the render's kernels wrote, behind them on st
+// from the partial sums the render's kernels wrote, behind them on st.
+// fitted: the render's plan as it was fitted to memory (one device only)
 void render_async(mcpt_scene& s, const mcpt_render_params* p, float* d_fb, hipStream_t st,
-                  uint32_t* d_unit_counters = nullptr, bool raw_mean = false, float* d_var = nullptr) {
+                  uint32_t* d_unit_counters = nullptr, bool raw_mean = false, float* d_var = nullptr,
+                  Plan* fitted = nullptr) {
     if (!s.on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
     if (!d_fb) throw mcpt::Error{MCPT_E_INVALID, "framebuffer is NULL"};
     if (multi_device(s, p, d_unit_counters)) {
@@ -100,21 +118,14 @@ void render_async(mcpt_scene& s, const mcpt_render_params* p, float* d_fb, hipSt
     Plan& pl = R.pl;
     pl.kp.raw_mean = raw_mean ? 1 : 0;
     pl.kp.unit_counters = d_unit_counters;
+    if (fitted) *fitted = pl;
     // (a render without primary lists reports none)
     HIP_TRY(hipMemsetAsync(tile_classes(s), 0, 16, st));
     const Timing t = acquire_timing(s, pl.capturing);
     if (pl.pipeline == MCPT_PIPELINE_WAVEFRONT) {
-        mcpt::WfStreams wst{};
-        wst.n = pl.sets();
-        wst.st[0] = st;
-        wst.fork = s.wf_fork;
-        for (int i = 1; i < wst.n; i++) {
-            wst.st[i] = s.wf_stream[i];
-            wst.join[i] = s.wf_join[i];
-        }
-        const int queries = pl.kp.mode == MCPT_MODE_QUINENGINE ? 3 * pl.kp.max_depth + 1 : pl.kp.max_depth + 1;
-        HIP_TRY(mcpt::launch_wavefront(pl.kp, R.wf, wst, s.cus, queries, !pl.wf_batch_explicit, t.e[0], t.e[1],
-                                       t.e[2], reinterpret_cast<float4*>(d_fb), &s.last_variant));
+        HIP_TRY(mcpt::launch_wavefront(pl.kp, R.wf, wf_streams_on(s, pl.sets(), st), s.cus, wf_queries(pl.kp),
+                                       !pl.wf_batch_explicit, t.e[0], t.e[1], t.e[2],
+                                       reinterpret_cast<float4*>(d_fb), &s.last_variant));
     } else {
         HIP_TRY(mcpt::launch_render(pl.kp, s.cus, st, t.e[0], t.e[1], t.e[2], reinterpret_cast<float4*>(d_fb),
                                     &s.last_variant));
@@ -392,15 +403,17 @@ Adaptive adaptive_resolve(const mcpt_adaptive_params* p) {
 }
 
 // What mcpt_render_adaptive[_device] asks beyond mcpt_render_var; throws
-// before anything is launched.
-void check_adaptive_render(const mcpt_scene& s, const mcpt_render_params* p, const Adaptive& a, hipStream_t st) {
+// before anything is launched.  any_pipeline: the _ex entries, which honour
+// p->pipeline; the older pair is the megakernel-only form.
+void check_adaptive_render(const mcpt_scene& s, const mcpt_render_params* p, const Adaptive& a, hipStream_t st,
+                           bool any_pipeline) {
     check_var_params(s, p);
     (void)make_plan(s, p);   // mcpt_render's own argument checks
     if (p->prev_count != 0)
         throw mcpt::Error{MCPT_E_INVALID, "prev_count must be 0: an adaptive render starts its own running mean"};
     if (uint64_t(p->spp_offset) + uint64_t(a.max_passes) * uint64_t(p->spp) > (uint64_t(1) << 32))
         throw mcpt::Error{MCPT_E_INVALID, "spp_offset + max_passes * spp passes 2^32 sample indices"};
-    if (p->pipeline != MCPT_PIPELINE_MEGAKERNEL)
+    if (!any_pipeline && p->pipeline != MCPT_PIPELINE_MEGAKERNEL)
         throw mcpt::Error{MCPT_E_UNSUPPORTED, "pipeline: adaptive sampling runs on the megakernel only"};
     if (p->mode != MCPT_MODE_CVMCTRACER)
         throw mcpt::Error{MCPT_E_UNSUPPORTED, "mode: adaptive sampling selects in linear radiance, CVMCTracer mode only"};
@@ -412,7 +425,10 @@ void check_adaptive_render(const mcpt_scene& s, const mcpt_render_params* p, con
 
 // The passes of an adaptive render on st (arguments checked).  The host waits
 // for st once per listed pass, for the list's length; the last pass is left
-// running.
+// running.  The wavefront (p->pipeline) runs a listed pass as a frame of n listed
+// pixels too: wf_generate_list fills an explicit queue 0 and every later kernel
+// is the uniform render's, planned inside pass 0's workspace
+// (prepare_wavefront_list); the merge stands where its reduction would.
 void adaptive_async(mcpt_scene& s, const mcpt_render_params* p, const Adaptive& a, float* d_fb, float* d_var,
                     uint32_t* d_count, hipStream_t st) {
     set_device(s);
@@ -433,7 +449,9 @@ void adaptive_async(mcpt_scene& s, const mcpt_render_params* p, const Adaptive& 
     }
     float4* fb = reinterpret_cast<float4*>(d_fb);
     float4* var = reinterpret_cast<float4*>(d_var);
-    render_async(s, p, d_fb, st, nullptr, false, d_var);   // pass 0: every pixel
+    const bool wavefront = p->pipeline == MCPT_PIPELINE_WAVEFRONT;
+    Plan pass0;
+    render_async(s, p, d_fb, st, nullptr, false, d_var, &pass0);   // pass 0: every pixel
     HIP_TRY(mcpt::launch_adaptive_fill(d_count, npx, 1u, st));
     for (int32_t j = 1; j < a.max_passes; ++j) {
         mcpt_render_params pj = *p;
@@ -457,6 +475,24 @@ void adaptive_async(mcpt_scene& s, const mcpt_render_params* p, const Adaptive& 
         const uint32_t n = *s.ad_host_n;
         if (!n) break;
         if (n > npix) throw mcpt::Error{MCPT_E_DEVICE, "adaptive pixel list longer than the frame"};
+        if (wavefront) {
+            Prepared R;
+            R.pl = make_plan(s, &pj);
+            prepare_wavefront_list(s, R.pl, pass0, n, &pj, R.wf);
+            mcpt::KernelParams& k = R.pl.kp;
+            k.pixel_list = aw.list;
+            // (a listed pass uses no primary lists: the scene reports no tile classes after it)
+            HIP_TRY(hipMemsetAsync(tile_classes(s), 0, 16, st));
+            const Timing t = acquire_timing(s, false);
+            HIP_TRY(mcpt::launch_wavefront(k, R.wf, wf_streams_on(s, R.pl.sets(), st), s.cus, wf_queries(k),
+                                           !R.pl.wf_batch_explicit, t.e[0], t.e[1], nullptr, nullptr,
+                                           &s.last_variant));
+            HIP_TRY(mcpt::launch_adaptive_merge(k, fb, var, d_count, st));
+            HIP_TRY(hipEventRecord(t.e[2], st));
+            s.pending.push_back(t);
+            s.renders++;
+            continue;
+        }
         // a frame of n listed pixels: the unit decode, tail split and partial-sum
         // layout are the megakernel's own, over n pixels instead of npix_local
         Plan pl = make_plan(s, &pj);
@@ -654,8 +690,12 @@ int mcpt_render_var(mcpt_scene* s, const mcpt_render_params* p, float* fb_rgb, f
     return render_sync(s, p, fb_rgb, stats, nullptr, var_rgba);
 }
 
-int mcpt_render_adaptive_device(mcpt_scene* s, const mcpt_render_params* p, const mcpt_adaptive_params* ap,
-                                float* d_fb_rgba, float* d_var_rgba, uint32_t* d_pass_count, void* hip_stream) {
+// the adaptive entries' shared bodies; any_pipeline: the _ex pair (check_adaptive_render)
+namespace {
+
+int adaptive_device_entry(mcpt_scene* s, const mcpt_render_params* p, const mcpt_adaptive_params* ap,
+                          float* d_fb_rgba, float* d_var_rgba, uint32_t* d_pass_count, void* hip_stream,
+                          bool any_pipeline) {
     return guarded([&]() -> int {
         if (!s) return fail(MCPT_E_INVALID, "NULL scene");
         if (!d_fb_rgba || !d_var_rgba || !d_pass_count)
@@ -669,19 +709,19 @@ int mcpt_render_adaptive_device(mcpt_scene* s, const mcpt_render_params* p, cons
         }
         const Adaptive a = adaptive_resolve(ap);
         hipStream_t st = static_cast<hipStream_t>(hip_stream);
-        check_adaptive_render(*s, p, a, st);
+        check_adaptive_render(*s, p, a, st, any_pipeline);
         adaptive_async(*s, p, a, d_fb_rgba, d_var_rgba, d_pass_count, st);
         return MCPT_OK;
     });
 }
 
 // fb, var and the pass counts are staged in the scene's host-render buffer
-int mcpt_render_adaptive(mcpt_scene* s, const mcpt_render_params* p, const mcpt_adaptive_params* ap, float* fb_rgb,
-                         float* var_rgba, uint32_t* pass_count, mcpt_render_stats* stats) {
+int adaptive_host_entry(mcpt_scene* s, const mcpt_render_params* p, const mcpt_adaptive_params* ap, float* fb_rgb,
+                        float* var_rgba, uint32_t* pass_count, mcpt_render_stats* stats, bool any_pipeline) {
     return guarded([&]() -> int {
         if (!s || !fb_rgb || !var_rgba || !pass_count) return fail(MCPT_E_INVALID, "NULL argument");
         const Adaptive a = adaptive_resolve(ap);
-        check_adaptive_render(*s, p, a, nullptr);
+        check_adaptive_render(*s, p, a, nullptr, any_pipeline);
         set_device(*s);
         const size_t npx = size_t(p->width) * size_t(p->height);
         const auto c = carve({npx * 16, npx * 16, npx * 4});
@@ -700,6 +740,28 @@ int mcpt_render_adaptive(mcpt_scene* s, const mcpt_render_params* p, const mcpt_
         read_stats_all(*s, stats);
         return MCPT_OK;
     });
+}
+
+}  // namespace
+
+int mcpt_render_adaptive_device(mcpt_scene* s, const mcpt_render_params* p, const mcpt_adaptive_params* ap,
+                                float* d_fb_rgba, float* d_var_rgba, uint32_t* d_pass_count, void* hip_stream) {
+    return adaptive_device_entry(s, p, ap, d_fb_rgba, d_var_rgba, d_pass_count, hip_stream, false);
+}
+
+int mcpt_render_adaptive(mcpt_scene* s, const mcpt_render_params* p, const mcpt_adaptive_params* ap, float* fb_rgb,
+                         float* var_rgba, uint32_t* pass_count, mcpt_render_stats* stats) {
+    return adaptive_host_entry(s, p, ap, fb_rgb, var_rgba, pass_count, stats, false);
+}
+
+int mcpt_render_adaptive_ex_device(mcpt_scene* s, const mcpt_render_params* p, const mcpt_adaptive_params* ap,
+                                   float* d_fb_rgba, float* d_var_rgba, uint32_t* d_pass_count, void* hip_stream) {
+    return adaptive_device_entry(s, p, ap, d_fb_rgba, d_var_rgba, d_pass_count, hip_stream, true);
+}
+
+int mcpt_render_adaptive_ex(mcpt_scene* s, const mcpt_render_params* p, const mcpt_adaptive_params* ap, float* fb_rgb,
+                            float* var_rgba, uint32_t* pass_count, mcpt_render_stats* stats) {
+    return adaptive_host_entry(s, p, ap, fb_rgb, var_rgba, pass_count, stats, true);
 }
 
 }  // extern "C"

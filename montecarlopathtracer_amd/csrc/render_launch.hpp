@@ -259,7 +259,8 @@ struct KernelParams {
     // 1: the reduction writes the plain mean of this call's samples (a device's
     // shard of a multi-device render; gather_kernel applies the running mean)
     int32_t raw_mean;
-    // pixel-list kernel (adaptive sampling): packed pixel index of listed pixel i;
+    // pixel-list kernels (adaptive sampling; the megakernel's list kernel and the
+    // wavefront's wf_generate_list): packed pixel index of listed pixel i;
     // npix_local is then the list's length
     const uint32_t* pixel_list;
 };
@@ -447,7 +448,11 @@ int wavefront_segments(const GpuScene& sc, int cus);
 // wavefront streams: batch i runs on stream i mod n (st[0] = the caller's),
 // forked from and joined back into st[0] with the events of each extra stream.
 // default_batch: the plan chose wf[].capacity (mcpt_render_params::wf_batch 0);
-// the batches of a render that can use the primary lists are then whole tiles
+// the batches of a render that can use the primary lists are then whole tiles.
+// kp.pixel_list set (adaptive sampling's listed passes): a frame of kp.npix_local
+// listed pixels, CV mode -- wf_generate_list fills an explicit queue 0, bounce 0
+// runs the ordinary extend and shade, no candidate pass; fb == nullptr then skips
+// the reduction (the caller merges the partial sums, launch_adaptive_merge)
 constexpr int kMaxWfStreams = 4;
 struct WfStreams {
     int n;

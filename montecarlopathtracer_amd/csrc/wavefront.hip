@@ -8,7 +8,9 @@
 //               global memory) dealt to the segments round-robin; in CV mode
 //               with queue-order shading only the direction stream is
 //               written (MCPT_WF_IMPLICIT0: the origin is the eye, and bounce
-//               0's shade recomputes the path state from the slot)
+//               0's shade recomputes the path state from the slot); over a
+//               pixel list (adaptive sampling's listed passes) wf_generate_list
+//               looks each pixel up and writes all three streams
 //   extend b    closest hit of every ray in queue b: one persistent workgroup
 //               per queue segment, scene image in LDS (or global); waves
 //               reserve slots 64 at a time from an LDS counter, each lane
@@ -102,6 +104,42 @@ __global__ void __launch_bounds__(kGenBlock) wf_generate(const KernelParams kp, 
         }
         if (!(MCPT_WF_IMPLICIT0 >= 2 && implicit0(kp, wf))) stq(&wf.q[0][qf(slot, kQO, wf.slot_stride)], pack(o, pid));
         stq(&wf.q[0][qf(slot, kQD, wf.slot_stride)], pack(d, depth));
+    }
+    flush_counters(c, kp.stats);
+}
+
+// ---- generate over a pixel list (adaptive sampling's listed passes) ---------
+// A frame of kp.npix_local listed pixels, CV mode: pixel i of the batch is
+// packed pixel kp.pixel_list[wf.v0 + i] of the image.  Queue 0 is explicit
+// (implicit0 is false for a listed frame: a slot does not name its pixel), so
+// all three streams are written and the ordinary extend and shade take bounce 0
+// from the queue; from here on a path is its pid, and pid % nb its column of the
+// partial sums.  Listed pixels are inside the image: every pid < n is a ray,
+// and the last group's padding lies past the segment's queue length.
+__global__ void __launch_bounds__(kGenBlock) wf_generate_list(const KernelParams kp, const WfParams wf) {
+    const uint32_t n = wf.nb * wf.ns;
+    const uint32_t gs = wf.group_shift, gm = (1u << gs) - 1u;
+    const V3 eye = v3(kp.eye[0], kp.eye[1], kp.eye[2]);
+    Counters c = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint32_t pid = blockIdx.x * kGenBlock + threadIdx.x; pid < n; pid += gridDim.x * kGenBlock) {
+        const uint32_t s_local = pid / wf.nb;
+        const uint32_t v = kp.pixel_list[wf.v0 + (pid - s_local * wf.nb)];
+        const uint32_t grp = pid >> gs, blk = grp / wf.nseg;
+        const uint32_t g = seg_of(grp - blk * wf.nseg, blk, wf.nseg, wf.xcd_deal);
+        const uint32_t slot = g * wf.seg + (blk << gs) + (pid & gm);
+        if (grp < wf.nseg && (pid & gm) == 0u) wf.cnt[g].queued = seg_queue0_len(wf, g);   // segment g's queue length
+        int px, py;
+        V3 d = v3(0, 0, 0);
+        uint32_t depth = kNoRay, sd = 0;
+        if (unit_pixel(kp, v, px, py)) {
+            primary_ray(kp, (uint32_t)py * (uint32_t)kp.width + (uint32_t)px, px, py, wf.s_begin + s_local, sd, d);
+            c.paths++;
+            c.rays++;
+            depth = 0;
+        }
+        stq(&wf.q[0][qf(slot, kQO, wf.slot_stride)], pack(eye, pid));
+        stq(&wf.q[0][qf(slot, kQD, wf.slot_stride)], pack(d, depth));
+        stq(&wf.q[0][qf(slot, kQPS, wf.slot_stride)], make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(sd)));
     }
     flush_counters(c, kp.stats);
 }
@@ -242,7 +280,8 @@ wf_extend(const KernelParams kp, const WfParams wf) {
     int refill;
     asm volatile("s_mov_b32 %0, %1" : "=s"(refill) : "s"(wf.refill_thresh));
     // MCPT_WF_IMPLICIT0 >= 2: bounce 0's origins are the eye (CV mode), not read
-    const bool eye0 = MCPT_WF_IMPLICIT0 >= 2 && wf.bounce == 0 && implicit0(kp, wf);
+    // (also over a pixel list, whose generate writes the eye into every slot)
+    const bool eye0 = MCPT_WF_IMPLICIT0 >= 2 && wf.bounce == 0 && eye_origins0(kp);
     const float4 eye4 = make_float4(kp.eye[0], kp.eye[1], kp.eye[2], 0.0f);
     auto ld_o = [&](uint32_t sl) { return eye0 ? eye4 : ldq(&qb[qf(seg0 + sl, kQO, qs)]); };
     if (slot < count) start(ld_o(slot), ldq(&qb[qf(seg0 + slot, kQD, qs)]));
@@ -910,7 +949,9 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
                                 implicit0(kb, wf) && wf.group_shift == 6u;
             if (!(packet && MCPT_WF_GEN0)) {
                 const uint32_t gen_grid = (n + kGenBlock - 1) / kGenBlock;
-                hipLaunchKernelGGL(wf_generate, dim3(gen_grid < 16u * (uint32_t)cus ? gen_grid : 16u * (uint32_t)cus),
+                // (a frame over a pixel list: its generate looks the pixel up)
+                hipLaunchKernelGGL(kb.pixel_list ? wf_generate_list : wf_generate,
+                                   dim3(gen_grid < 16u * (uint32_t)cus ? gen_grid : 16u * (uint32_t)cus),
                                    dim3(kGenBlock), 0, bs, kb, wf);
                 if ((e = hipGetLastError()) != hipSuccess) break;
             }
@@ -969,7 +1010,9 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
     }
     if (e != hipSuccess) return e;
     if (ev1 && (e = hipEventRecord(ev1, st)) != hipSuccess) return e;
-    e = launch_reduce(kp, fb, st);
+    // (fb == nullptr: no reduction -- a frame over a pixel list, whose caller merges
+    // the partial sums into its pixels, adaptive.hip)
+    if (fb) e = launch_reduce(kp, fb, st);
     if (e == hipSuccess && ev2) e = hipEventRecord(ev2, st);
     if (variant_out) *variant_out = in_lds ? 4 : 5;
     return e;

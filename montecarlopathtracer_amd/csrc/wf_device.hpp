@@ -178,8 +178,18 @@ __device__ __forceinline__ uint32_t seg_queue0_len(const WfParams& wf, uint32_t 
 #ifndef MCPT_WF_IMPLICIT0
 #define MCPT_WF_IMPLICIT0 2
 #endif
-__host__ __device__ __forceinline__ bool implicit0(const KernelParams& kp, const WfParams& wf) {
+// CV mode: every primary ray starts at the eye -- what the extend's bounce 0
+// asks before it takes its origins from the kernel arguments (level 2)
+__host__ __device__ __forceinline__ bool eye_origins0(const KernelParams& kp) {
     return MCPT_WF_IMPLICIT0 && kp.mode != kModeQE;
+}
+// A frame over a pixel list (adaptive sampling's listed passes, wf_generate_list)
+// has an explicit queue 0: the slot gives the list index, not the pixel, so
+// generate writes all three streams, the host launches no packet extend and the
+// shade reads its state.  (A test of a kernel argument: a scalar compare.)  Its
+// origins are the eye all the same: the extend keeps eye_origins0 and its code.
+__host__ __device__ __forceinline__ bool implicit0(const KernelParams& kp, const WfParams& wf) {
+    return eye_origins0(kp) && kp.pixel_list == nullptr;
 }
 // Hit ids: extend writes only the hit triangle's id (4 B, the
 // first quarter of the hit stream as i32) and shade recomputes t, beta, gamma

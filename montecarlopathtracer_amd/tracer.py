@@ -497,7 +497,8 @@ class Scene:
         n = params.output_pixels()
         fb = np.zeros((n, 3), np.float32)
         chunk = params.spp_chunk if 0 < params.spp_chunk < params.spp else params.spp
-        units = n * ((params.spp + chunk - 1) // chunk)
+        # (a unit per pixel of every owned tile, padding included: more than n on a frame of partial tiles)
+        units = int(lib().mcpt_shard_pixel_count(C.byref(params.to_c()))) * ((params.spp + chunk - 1) // chunk)
         uc = np.zeros((units, 4), np.uint32)
         check(lib().mcpt_render_unit_counters(self.handle, C.byref(params.to_c()), _fptr(fb),
                                               uc.ctypes.data_as(C.POINTER(C.c_uint32))))
@@ -584,6 +585,36 @@ class Scene:
                                                 C.byref(adaptive) if adaptive is not None else None,
                                                 C.c_void_p(d_fb_rgba_ptr), C.c_void_p(d_var_rgba_ptr),
                                                 C.c_void_p(d_count_ptr), C.c_void_p(stream_ptr)))
+
+    def render_adaptive_ex(self, params: RenderParams, adaptive=None, fb: Optional[np.ndarray] = None,
+                           var: Optional[np.ndarray] = None):
+        """``render_adaptive`` with ``params.pipeline`` honoured (mcpt_render_adaptive_ex): on the
+        wavefront a listed pass is a wavefront render of the listed pixels.  Same arguments, same
+        returns, the same fb, var and count bit for bit; ``render_adaptive`` is the megakernel-only
+        form."""
+        H, W = int(params.height), int(params.width)
+        if fb is None:
+            fb = np.zeros((H, W, 3), np.float32)
+        if var is None:
+            var = np.zeros((H, W, 4), np.float32)
+        if fb.dtype != np.float32 or not fb.flags.c_contiguous or fb.size != 3 * H * W:
+            raise McptError(-1, "fb must be a C-contiguous float32 array with 3 floats per pixel")
+        if var.dtype != np.float32 or not var.flags.c_contiguous or var.size != 4 * H * W:
+            raise McptError(-1, "var must be a C-contiguous float32 array with 4 floats per pixel")
+        count = np.zeros((max(H, 0), max(W, 0)), np.uint32)
+        st = RenderStats()
+        check(lib().mcpt_render_adaptive_ex(self.handle, C.byref(params.to_c()),
+                                            C.byref(adaptive) if adaptive is not None else None, _fptr(fb),
+                                            _fptr(var), count.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st)))
+        return fb, var, count, self._render_stats(st)
+
+    def render_adaptive_ex_device(self, params: RenderParams, adaptive, d_fb_rgba_ptr: int, d_var_rgba_ptr: int,
+                                  d_count_ptr: int, stream_ptr: int = 0):
+        """``render_adaptive_device`` with ``params.pipeline`` honoured (mcpt_render_adaptive_ex_device)."""
+        check(lib().mcpt_render_adaptive_ex_device(self.handle, C.byref(params.to_c()),
+                                                   C.byref(adaptive) if adaptive is not None else None,
+                                                   C.c_void_p(d_fb_rgba_ptr), C.c_void_p(d_var_rgba_ptr),
+                                                   C.c_void_p(d_count_ptr), C.c_void_p(stream_ptr)))
 
     def reserve(self, params: RenderParams):
         check(lib().mcpt_scene_reserve(self.handle, C.byref(params.to_c())))

@@ -1,6 +1,7 @@
 """Times variance-driven adaptive sampling (mcpt_render_adaptive_device) on one GPU.
 
-    python scripts/bench_adaptive.py [--window 0.5] [--out profiles/adaptive/bench.jsonl] [--keep-trace DIR]
+    python scripts/bench_adaptive.py [--pipeline megakernel|wavefront] [--window 0.5]
+                                     [--out profiles/adaptive/bench.jsonl] [--keep-trace DIR]
 
 Setting: scene01 at the C2 camera, 1024x1024, megakernel (lean), --passes (16)
 passes of --spp (64) samples in chunks of --chunk (8).  In one run:
@@ -22,6 +23,14 @@ count, scan, scatter) and merge kernels around it.  What the adaptive call
 spends outside its kernels -- launches, and one 4-byte copy to pinned memory and
 a stream wait per listed pass -- is given as the whole call's time less the
 traced kernels', per listed pass.
+--pipeline wavefront (mcpt_render_adaptive_ex_device; the record is
+profiles/adaptive/bench_wf.jsonl): the same setting and the same four timings on
+the wavefront -- list_overhead then prices the explicit queue 0 of a listed pass
+against the implicit one, both sides rendering the same pixels -- plus, in the
+same process, megakernel_adaptive: the megakernel's adaptive render of the same
+params.  The traced child then gives, per listed pass, the kernel times of its
+generate (wf_generate_list), its bounce-0 extend and shade (the first extend and
+shade of each batch, by queue) and the rest (later bounces, cull, accumulate).
 Prints one JSON line (and appends it to --out).
 """
 import argparse
@@ -66,7 +75,8 @@ def summary(times):
 
 
 def frame_of(a):
-    return M.RenderParams.for_scene(1, width=a.size, height=a.size, spp=a.spp, spp_chunk=a.chunk, lean=True)
+    return M.RenderParams.for_scene(1, width=a.size, height=a.size, spp=a.spp, spp_chunk=a.chunk, lean=True,
+                                    pipeline=a.pipeline)
 
 
 class Bufs:
@@ -77,7 +87,9 @@ class Bufs:
         self.st = torch.cuda.current_stream().cuda_stream
 
     def adaptive(self, scene, frame, ap):
-        scene.render_adaptive_device(frame, ap, self.fb.data_ptr(), self.var.data_ptr(), self.cnt.data_ptr(), self.st)
+        # (the megakernel through the entry it always had; the general form honours the pipeline)
+        entry = scene.render_adaptive_device if frame.pipeline == "megakernel" else scene.render_adaptive_ex_device
+        entry(frame, ap, self.fb.data_ptr(), self.var.data_ptr(), self.cnt.data_ptr(), self.st)
 
     def uniform(self, scene, frame, passes):
         for j in range(passes):
@@ -113,6 +125,53 @@ KERNELS = (("pass", ("path_kernel", "list_kernel")), ("over", ("adaptive_over",)
            ("reduce", ("reduce_kernel", "variance_kernel")), ("fill", ("adaptive_fill",)))
 
 
+def wavefront_passes(rows, frames):
+    """per listed pass of the wavefront's adaptive render: median kernel times of its generate,
+    bounce-0 extend, bounce-0 shade and the rest; rows: (start, end, queue, kernel name)"""
+    renders, cur = [], None
+    for s, e, q, name in rows:
+        if "adaptive_fill" in name:                        # the fill ends pass 0: a render's listed passes follow
+            renders.append([])
+            cur = None
+            continue
+        if not renders:
+            continue
+        if "wf_generate_list" in name and (cur is None or cur["merged"]):
+            cur = {"generate": 0.0, "extend0": 0.0, "shade0": 0.0, "rest": 0.0, "merge": 0.0, "seen": {},
+                   "t0": s, "merged": False}
+            renders[-1].append(cur)
+        if cur is None or cur["merged"]:
+            continue
+        ms = (e - s) / 1e6
+        seen = cur["seen"].setdefault(q, set())
+        if "wf_generate_list" in name:
+            cur["generate"] += ms
+            seen.clear()                                   # a new batch on this queue
+        elif "adaptive_merge" in name:
+            cur["merge"] += ms
+            cur["wall"] = (e - cur["t0"]) / 1e6
+            cur["merged"] = True
+        elif "wf_extend" in name and "extend" not in seen:
+            cur["extend0"] += ms
+            seen.add("extend")
+        elif "wf_shade_slots" in name and "shade" not in seen:
+            cur["shade0"] += ms
+            seen.add("shade")
+        elif "wf_" in name:
+            cur["rest"] += ms
+    renders = [r for r in renders[1:] if r]                # the warm-up
+    if len(renders) != frames:
+        return {"error": f"{len(renders)} renders traced, expected {frames}"}
+    out = []
+    for j in range(min(len(r) for r in renders)):
+        d = {"pass": j + 1}
+        for k in ("generate", "extend0", "shade0", "rest", "merge", "wall"):
+            v = sorted(r[j].get(k, 0.0) for r in renders)
+            d[k + "_ms"] = round(v[len(v) // 2], 4)
+        out.append(d)
+    return {"listed_passes": out, "frames": len(renders)}
+
+
 def traced_kernels(a, timeout_s=600):
     """per pass: median kernel times over the traced renders, or an error note"""
     if not shutil.which("rocprofv3"):
@@ -121,14 +180,15 @@ def traced_kernels(a, timeout_s=600):
     try:
         cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", out, "-o", "run", "--", sys.executable,
                os.path.abspath(__file__), "--trace-child", "--size", str(a.size), "--spp", str(a.spp), "--chunk",
-               str(a.chunk), "--passes", str(a.passes), "--trace-frames", str(a.trace_frames)]
+               str(a.chunk), "--passes", str(a.passes), "--trace-frames", str(a.trace_frames), "--pipeline",
+               a.pipeline]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
         except subprocess.TimeoutExpired:
             return {"error": "traced run timed out"}
         if r.returncode != 0:
             return {"error": f"traced run failed ({r.returncode}): {r.stderr[-300:]}"}
-        rows = []
+        rows, wf_rows = [], []
         for f in glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True):
             if a.keep_trace:
                 os.makedirs(a.keep_trace, exist_ok=True)
@@ -136,9 +196,13 @@ def traced_kernels(a, timeout_s=600):
             with open(f) as fh:
                 for row in csv.DictReader(fh):
                     name = row.get("Kernel_Name", "")
+                    wf_rows.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]), row.get("Queue_Id", ""),
+                                    name))
                     kind = next((k for k, pats in KERNELS if any(p in name for p in pats)), None)
                     if kind:
                         rows.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]), kind, name))
+        if a.pipeline == "wavefront":
+            return wavefront_passes(sorted(wf_rows), a.trace_frames)
         rows.sort()
         # a render = from one pass-0 path kernel to the next; a pass = from one pass kernel to the next
         renders = []
@@ -174,6 +238,7 @@ def traced_kernels(a, timeout_s=600):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", type=float, default=0.5)
+    ap.add_argument("--pipeline", choices=["megakernel", "wavefront"], default="megakernel")
     ap.add_argument("--out", default="")
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--spp", type=int, default=64)
@@ -194,7 +259,7 @@ def main():
     scene.reserve(frame)
     b = Bufs(frame)
     line = {"bench": "adaptive", "device": torch.cuda.get_device_name(0), "window_s": a.window, "width": a.size,
-            "height": a.size, "spp_per_pass": a.spp, "chunk": a.chunk, "passes": a.passes}
+            "height": a.size, "spp_per_pass": a.spp, "chunk": a.chunk, "passes": a.passes, "pipeline": a.pipeline}
     default = M.adaptive_params(max_passes=a.passes)
     run_adaptive = lambda: b.adaptive(scene, frame, default)   # noqa: E731
     run_uniform = lambda: b.uniform(scene, frame, a.passes)    # noqa: E731
@@ -204,6 +269,13 @@ def main():
     active = [round(float((count > j).mean()), 5) for j in range(a.passes)]
     line["uniform"] = with_rays(scene, timed(run_uniform, a.window, min_reps=2), run_uniform)
     line["adaptive"]["ratio_to_uniform"] = round(line["adaptive"]["ms"] / line["uniform"]["ms"], 4)
+    if a.pipeline == "wavefront":   # the megakernel's adaptive render of the same params, same process
+        mk = dataclasses.replace(frame, pipeline="megakernel")
+        scene.reserve(mk)
+        run_mk = lambda: b.adaptive(scene, mk, default)        # noqa: E731
+        line["megakernel_adaptive"] = timed(run_mk, a.window, min_reps=2)
+        line["adaptive"]["ratio_to_megakernel_adaptive"] = round(
+            line["adaptive"]["ms"] / line["megakernel_adaptive"]["ms"], 4)
     one = dataclasses.replace(frame, spp=a.spp * a.passes, spp_chunk=32)
     scene.reserve(one)
     run_one = lambda: scene.render_device(one, b.fb.data_ptr(), b.st)   # noqa: E731
@@ -231,6 +303,8 @@ def main():
         tr = traced_kernels(a)
         if "error" in tr:
             line["trace_error"] = tr["error"]
+        elif a.pipeline == "wavefront":
+            line["listed_pass_kernels"] = tr["listed_passes"]
         else:
             for d, t in zip(per_pass, tr["per_pass"]):
                 d.update({k: v for k, v in t.items() if k != "pass"})
