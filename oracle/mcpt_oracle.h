@@ -120,6 +120,7 @@ float orc_sinf(float x);
 float orc_cosf(float x);
 float orc_powf(float x, float y);
 float orc_pow5f(float x);                                        /* Fresnel (1-|n.d|)^5 */
+uint32_t orc_ns_u(float Ns);                                     /* CVMCTracer Phong's (unsigned)Ns, saturating */
 /* samplers with injected uniforms: u = uniforms consumed in order */
 void orc_sample_hemi(const float* n, const float* u, float* out);
 void orc_sample_phong(const float* n, const float* in, uint32_t Ns, const float* u, float* out);

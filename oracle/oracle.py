@@ -96,6 +96,8 @@ def lib():
         L.orc_powf.argtypes = [C.c_float, C.c_float]
         L.orc_pow5f.restype = C.c_float
         L.orc_pow5f.argtypes = [C.c_float]
+        L.orc_ns_u.restype = C.c_uint32
+        L.orc_ns_u.argtypes = [C.c_float]
         L.orc_sample_hemi.argtypes = [f32p, f32p, f32p]
         L.orc_sample_phong.argtypes = [f32p, f32p, C.c_uint32, f32p, f32p]
         L.orc_sample_fresnel.argtypes = [f32p, f32p, C.c_float, C.c_float, f32p, f32p]

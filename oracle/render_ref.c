@@ -239,6 +239,13 @@ static orc_v3 sample_fresnel(usrc* u, orc_v3 n, orc_v3 in, float Tr, float Ni, i
     return out;
 }
 
+/* (PWuint)Ns, the parameter type of Utils.hpp:72, made total: C leaves the conversion of a float
+ * outside the unsigned range undefined (x86 wraps 5e9 to 705032704), so Ns at or above the
+ * largest float below 2^32 gives that value, as the product's scene image does (scene_image.cpp) */
+uint32_t orc_ns_u(float Ns) {
+    return Ns > 0.0f ? (Ns < 4294967040.0f ? (uint32_t)Ns : 0xFFFFFF00u) : 0u;
+}
+
 void orc_sample_hemi(const float* n, const float* u, float* out) {
     usrc s = {0, u, 0};
     orc_v3 r = sample_hemi(&s, v3(n[0], n[1], n[2]));
@@ -717,7 +724,7 @@ static orc_v3 sample_mc(qctx* q, usrc* u, orc_v3 pos, orc_v3 dir, int max_depth,
             if (fresnel_kd) { color.x *= g->Kd.x; color.y *= g->Kd.y; color.z *= g->Kd.z; }
             pos = vadd(hit.hp, vscale(dir, 0.01f));
         } else if (g->Ns > 1) {
-            dir = sample_phong(u, normal, dir, (float)((uint32_t)g->Ns + 1u));
+            dir = sample_phong(u, normal, dir, (float)(orc_ns_u(g->Ns) + 1u));
             color.x *= g->Ks.x; color.y *= g->Ks.y; color.z *= g->Ks.z;
             pos = vadd(hit.hp, vscale(dir, 0.01f));
         } else {

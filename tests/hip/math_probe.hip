@@ -1,6 +1,8 @@
 // math_probe.hip -- test-only probe of the product's device math
 // (montecarlopathtracer_amd/csrc/mcpt_device.hpp) for bitwise comparison with
-// the CPU specification (oracle).  Built by tests/hip/build_probe.py.
+// the CPU specification (oracle): math_probe, one operation per call on two
+// operand arrays, and sampler_probe, the samplers on injected uniforms.  Built
+// by tests/hip/build_probe.py.
 #include <hip/hip_runtime.h>
 #include "../../montecarlopathtracer_amd/csrc/mcpt_device.hpp"
 
@@ -32,6 +34,54 @@ __global__ void probe(int op, int n, const float* a, const float* b, float* o0, 
                    o0[i] = (float)((double)x * ((__builtin_isfinite(r0) && r0 != 0.0) ? r2 : r0)); } break;
         default: break;
     }
+}
+
+// The device samplers on injected uniforms, one case per thread: nrm, in and out
+// hold 3 floats per case, u (the uniforms) and par (the parameters) 2.
+//   0  sample_lobe_u diffuse                               (u0, u1)
+//   1  sample_lobe_u Phong + scatter's reflection line, ns1 = (float)(Ns_u + 1u)   (par0: Ns_u's bits)
+//   2  the same with ns1 = Ns + 1.0f                       (par0: Ns)
+//   3  sample_fresnel_u<false>                             (u0; par0: Tr, par1: Ni)
+//   4  sample_fresnel_u<true>
+__global__ void sprobe(int op, int n, const float* nrm, const float* in, const float* u, const float* par, float* out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const V3 nv = v3(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]);
+    const V3 dir = v3(in[3 * i], in[3 * i + 1], in[3 * i + 2]);
+    const float u0 = u[2 * i], u1 = u[2 * i + 1], p0 = par[2 * i], p1 = par[2 * i + 1];
+    V3 r = v3(0, 0, 0);
+    switch (op) {
+        case 0: r = sample_lobe_u(u0, u1, nv, false, 0.0f); break;
+        case 1:
+        case 2: {
+            const float ns1 = op == 1 ? (float)(__float_as_uint(p0) + 1u) : p0 + 1.0f;
+            const V3 h = sample_lobe_u(u0, u1, nv, true, ns1);
+            r = vsub(dir, vscale(vscale(h, dot3(dir, h)), 2.0f));   // (trace_device.hpp scatter_n)
+        } break;
+        case 3: r = sample_fresnel_u<false>(u0, nv, dir, p0, p1); break;
+        case 4: r = sample_fresnel_u<true>(u0, nv, dir, p0, p1); break;
+        default: break;
+    }
+    out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+}
+
+extern "C" int sampler_probe(int op, int n, const float* nrm, const float* in, const float* u, const float* par,
+                             float* out) {
+    float *dn, *di, *du, *dp, *d0;
+    const size_t f3 = 3 * sizeof(float) * (size_t)n, f2 = 2 * sizeof(float) * (size_t)n;
+    if (n <= 0) return -3;
+    if (hipMalloc(&dn, f3) || hipMalloc(&di, f3) || hipMalloc(&du, f2) || hipMalloc(&dp, f2) || hipMalloc(&d0, f3))
+        return -1;
+    hipMemcpy(dn, nrm, f3, hipMemcpyHostToDevice);
+    hipMemcpy(di, in, f3, hipMemcpyHostToDevice);
+    hipMemcpy(du, u, f2, hipMemcpyHostToDevice);
+    hipMemcpy(dp, par, f2, hipMemcpyHostToDevice);
+    hipMemset(d0, 0, f3);
+    hipLaunchKernelGGL(sprobe, dim3((n + 255) / 256), dim3(256), 0, 0, op, n, dn, di, du, dp, d0);
+    hipError_t e = hipDeviceSynchronize();
+    hipMemcpy(out, d0, f3, hipMemcpyDeviceToHost);
+    hipFree(dn); hipFree(di); hipFree(du); hipFree(dp); hipFree(d0);
+    return e == hipSuccess ? 0 : -2;
 }
 
 extern "C" int math_probe(int op, int n, const float* a, const float* b, float* o0, float* o1, uint32_t* u) {
