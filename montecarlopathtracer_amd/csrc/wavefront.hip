@@ -590,8 +590,36 @@ wf_shade_slots(const KernelParams kp, const WfParams wf) {
             o = xyz(o4);
             d = xyz(d4);
         }
-        // the per-item code and the enqueue: one source for this kernel and wf_primary_shade
         const bool live = carried || i < total;
+        // queue order: the hit's records -- its triangle record (the geometry index is
+        // tris[htri + 1].w) and its three vertex normals -- as one group of loads behind the
+        // queue's words; the per-item code takes all six from here, so an iteration has one
+        // dependent trip to L2 on its main chain where the branches of that code, each
+        // decided by the trip before, made three (geometry index, tri_hit_params' records,
+        // scatter's normals).  A carried lane has its hit id in a register.
+        // Only a lane that holds an item with a hit id >= 0 loads: no address is formed
+        // that the per-item code did not form (a scene may hold no triangle at all).
+        // The hit id decides that without the depth word: every hit id in a queue is the
+        // htri of a RayState that begin_ray or the bounce-0 extends' setup left at -1, and a
+        // kNoRay slot (a pixel outside the image) never reaches a triangle test -- wf_extend
+        // starts it as kReady, the bounce-0 extends leave it inactive -- so its id is -1;
+        // the tail's ids are resolved hits of real rays.  A terminating item does not use
+        // its 96 B (they come from L1 / L2).
+        // (zeros first: left undefined in the lanes that do not load, the values were held
+        // across the whole loop body and the kernels spilled, 52-56 B of scratch)
+        const float4 z4 = make_float4(0, 0, 0, 0);
+        float4 rt0 = z4, rt1 = z4, rt2 = z4, rn0 = z4, rn1 = z4, rn2 = z4;
+        if constexpr (!SORTB) {
+            if (live && htri >= 0) {
+                rt0 = tris[htri];
+                rt1 = tris[htri + 1];
+                rt2 = tris[htri + 2];
+                rn0 = sc.normals[htri];
+                rn1 = sc.normals[htri + 1];
+                rn2 = sc.normals[htri + 2];
+            }
+        }
+        // the per-item code and the enqueue: one source for this kernel and wf_primary_shade
 #define MCPT_SHADE_FUSED 0
 #include "wf_shade_item.hpp"
 #undef MCPT_SHADE_FUSED

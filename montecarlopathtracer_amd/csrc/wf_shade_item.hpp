@@ -9,8 +9,11 @@
 // hit's t, beta, gamma and the records come from:
 //   0  t, beta, gamma recomputed from the hit id (tri_hit_params); the direct
 //      lists' records in the shade's own copy (ldrec, indices ldk); tris and
-//      geoms wherever the kernel reads them from
-//   1  t, beta, gamma as the resolving test_tri_pair left them (ht, hb, hg:
+//      geoms wherever the kernel reads them from -- in queue order (!SORTB) the
+//      hit's own records are the values wf_shade_slots loaded in one group behind
+//      the hit id: rt0..rt2 = tris[htri .. htri + 2], rn0..rn2 = normals[htri ..
+//      htri + 2] (defined where htri >= 0 in a live lane, the only place read)
+//   1 t, beta, gamma as the resolving test_tri_pair left them (ht, hb, hg:
 //      RayState::best / hbeta / hgamma); tris and geoms are the LDS scene image's,
 //      so the lists' records are tris + ldk[entry] and no copy exists
 // In scope: SORTB, kp, wf, sc, qe, tdepth, unlisted, tris, geoms, ldk (ldrec),
@@ -25,7 +28,14 @@
             V3 L = v3(0, 0, 0);
             bool term = true;
             if (htri >= 0 && depth != kNoRay) {
+#if MCPT_SHADE_FUSED
                 const GpuGeom& gm = geoms[__float_as_uint(tris[htri + 1].w)];
+#else
+                uint32_t gi0;                                 // the hit's geometry index
+                if constexpr (SORTB) gi0 = __float_as_uint(tris[htri + 1].w);
+                else gi0 = __float_as_uint(rt1.w);
+                const GpuGeom& gm = geoms[gi0];
+#endif
                 if (qe) {
                     if ((int32_t)depth < 3 * kp.max_depth &&
                         ((int32_t)depth < kp.max_depth || qe_roulette(sd, color))) {
@@ -41,11 +51,19 @@
                     c.shades++;
 #if MCPT_SHADE_FUSED
                     h = make_float4(ht, hb, hg, 0.0f);
-#else
-                    tri_hit_params(o, d, tris[htri], tris[htri + 1], tris[htri + 2], h.x, h.y, h.z);
-#endif
                     if (qe) scatter<true>(gm, sc.normals, htri, h.y, h.z, h.x, 0, sd, color, o, d);
                     else scatter<false>(gm, sc.normals, htri, h.y, h.z, h.x, kp.fresnel_kd, sd, color, o, d);
+#else
+                    if constexpr (SORTB) {
+                        tri_hit_params(o, d, tris[htri], tris[htri + 1], tris[htri + 2], h.x, h.y, h.z);
+                        if (qe) scatter<true>(gm, sc.normals, htri, h.y, h.z, h.x, 0, sd, color, o, d);
+                        else scatter<false>(gm, sc.normals, htri, h.y, h.z, h.x, kp.fresnel_kd, sd, color, o, d);
+                    } else {   // (scatter is these loads, then scatter_n)
+                        tri_hit_params(o, d, rt0, rt1, rt2, h.x, h.y, h.z);
+                        if (qe) scatter_n<true>(gm, rn0, rn1, rn2, h.y, h.z, h.x, 0, sd, color, o, d);
+                        else scatter_n<false>(gm, rn0, rn1, rn2, h.y, h.z, h.x, kp.fresnel_kd, sd, color, o, d);
+                    }
+#endif
                     cont = true;
                     c.rays++;
                     // the new ray against the scene's occluder boxes (lean renders:
