@@ -101,7 +101,7 @@ hipError_t launch_aov(const KernelParams& kp, float4* albedo_cov, float4* normal
     const dim3 grid(std::min(want, cap));
     const bool qe = kp.mode == kModeQE;
     // stack entries in LDS as query_kernel: 8 for global-memory scenes, 4 for LDS-sized ones
-    if (kp.scene.node_boxes) {
+    if (!scene_in_lds(kp.scene)) {
         if (qe) hipLaunchKernelGGL((aov_kernel<true, 8, true>), grid, dim3(kAovBlock), 0, st, kp, albedo_cov, normal_depth);
         else hipLaunchKernelGGL((aov_kernel<true, 8, false>), grid, dim3(kAovBlock), 0, st, kp, albedo_cov, normal_depth);
     } else {

@@ -20,6 +20,7 @@
 #include "host_model.hpp"
 #include "render_launch.hpp"
 #include "staging.hpp"
+#include "wf_route.hpp"
 
 struct mcpt_model {
     mcpt::ObjModel m;
@@ -200,7 +201,7 @@ struct Plan {
     bool wf_batch_explicit;      // the caller asked for this batch (not shrunk to fit memory)
     int32_t wf_sort;             // wavefront material sort (mcpt_render_params::wf_sort)
     int32_t wf_refill;           // idle lanes before an extend wave refills
-    uint32_t wf_group_shift;     // global-memory scenes: paths dealt to segments in groups of 2^k
+    mcpt::WfRoute route;         // which steps a wavefront render takes (wf_route.hpp; make_plan)
     int64_t tail_per_lane;       // megakernel tail split: units per lane (< 0 off)
     int64_t tail_exact;          // megakernel tail split: exact units (> 0 overrides)
     uint64_t wf_mem_limit;       // mcpt_render_params::wf_mem_limit
@@ -230,6 +231,8 @@ uint32_t tea16(uint32_t v0, uint32_t v1);
 int ready_thresh_for(const mcpt_scene& s, int32_t asked);
 // lanes the persistent kernels launch on the scene's device: they index the spill area
 size_t launched_lanes(const mcpt_scene& s);
+// the scene's part of what a wavefront route is computed from (wf_route.hpp)
+mcpt::WfFacts scene_facts(const mcpt_scene& s);
 constexpr size_t kSpillEntries = 32;   // stack entries per lane (build_image caps the KD depth at 32), 16 B each
 constexpr int64_t kTailPerLane = 4;    // the tail split's default units per lane (make_plan)
 size_t spill_bytes(const mcpt_scene& s, int sets);

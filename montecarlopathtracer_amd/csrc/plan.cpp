@@ -45,12 +45,35 @@ int clamp_i(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 // 3 x 2^27 157.9, 4 x 2^27 153.3, 3 x 2^26 168.3, 4 x 2^26 160.0, 1 x 2^28
 // 168.6; the commit before the carry 152.6 / 149.7 / 149.2 / 159.4 / 149.9;
 // PERFLOG row 184)
-int wavefront_streams(const mcpt_scene& s, uint64_t work, const mcpt_render_params* p) {
-    const bool carry = p->lean && !p->wf_sort && s.n_miss_boxes && s.direct_counts &&
-                       mcpt::direct_lists_fit(s.gpu.image_bytes, s.gpu.node_boxes);
+int wavefront_streams(const mcpt::WfRoute& r, uint64_t work, const mcpt_render_params* p) {
     const int n = p->wf_streams > 0 ? p->wf_streams
-                                    : (s.gpu.node_boxes ? 4 : (work > (uint64_t(1) << 29) && !carry ? 3 : 2));
+                                    : (!r.in_lds ? 4 : (work > (uint64_t(1) << 29) && !r.carry ? 3 : 2));
     return clamp_i(n, 1, mcpt::kMaxWfStreams);
+}
+
+// the primary lists' tile records: one per owned 8x8 tile (wf_layout makes room, the route asks)
+bool tile_records(const mcpt::KernelParams& kp) { return kp.tile == 8 && (kp.npix_local >> 6) != 0; }
+
+// The route of the wavefront render pl plans (wf_route.hpp), from what the
+// scene holds and what make_plan read; listed: a frame over a pixel list
+mcpt::WfRoute plan_route(const mcpt_scene& s, const Plan& pl, uint32_t group_shift, bool listed) {
+    const mcpt::KernelParams& k = pl.kp;
+    mcpt::WfFacts f = scene_facts(s);
+    // a culled ray stands for color * (0 * illum) = 0: illum must be finite,
+    // and so must the throughput, a product of at most max_depth Kd / Ks
+    // components (each rounding grows it by 2^-24 at most: 2^127 leaves room)
+    const bool zero = std::isfinite(k.illum) && std::log2(std::max(1.0, double(s.cull_gain))) * k.max_depth < 127.0;
+    if (!zero) f.n_cull_boxes = 0;
+    f.lean = k.lean != 0;
+    f.sort = pl.wf_sort != 0;
+    f.qe = k.mode == MCPT_MODE_QUINENGINE;
+    f.listed = listed;
+    f.default_batch = !pl.wf_batch_explicit;
+    f.tile_records = tile_records(k);
+    f.tile = k.tile;
+    f.max_depth = k.max_depth;
+    f.group_shift = group_shift;
+    return mcpt::wf_route(f);
 }
 
 // Device memory of one stream's wavefront workspace for batches of `cap`
@@ -68,17 +91,16 @@ int wavefront_streams(const mcpt_scene& s, uint64_t work, const mcpt_render_para
 struct WfLayout {
     size_t cap_slots, f4, queue, tiles, need;
 };
-WfLayout wf_layout(const mcpt_scene& s, const Plan& pl, uint64_t cap) {
+WfLayout wf_layout(const Plan& pl, uint64_t cap) {
     const mcpt::KernelParams& kp = pl.kp;
-    const size_t nseg = static_cast<size_t>(mcpt::wavefront_segments(s.gpu, s.cus));
-    const size_t queries = kp.mode == MCPT_MODE_QUINENGINE ? 3 * size_t(kp.max_depth) + 1 : size_t(kp.max_depth) + 1;
-    const size_t bounces = (queries + 1) * nseg;
+    const size_t nseg = pl.route.nseg;
+    const size_t bounces = (size_t(pl.route.queries) + 1) * nseg;
     auto al256 = [](size_t x) { return (x + 255) & ~size_t(255); };
     WfLayout l;
-    l.cap_slots = size_t(cap) + (nseg << pl.wf_group_shift);
+    l.cap_slots = size_t(cap) + (nseg << pl.route.group_shift);
     l.f4 = l.cap_slots * 16;
     l.queue = al256(3 * l.f4 + 4 * l.cap_slots);
-    l.tiles = kp.tile == 8 ? al256(size_t(kp.npix_local >> 6) * mcpt::kListRecWords * 4) : 0;
+    l.tiles = tile_records(kp) ? al256(size_t(kp.npix_local >> 6) * mcpt::kListRecWords * 4) : 0;
     l.need = al256(2 * l.queue + l.f4 + l.tiles + bounces * sizeof(mcpt::WfCounters) + 256);
     return l;
 }
@@ -87,7 +109,8 @@ WfLayout wf_layout(const mcpt_scene& s, const Plan& pl, uint64_t cap) {
 // path state and radiance, per-bounce counters -- carved from one buffer, once
 // per stream (`sets`: batches rotate over the wavefront's streams, each with its own)
 void prepare_wavefront(mcpt_scene& s, const Plan& pl, int sets, mcpt::WfParams* out) {
-    const WfLayout l = wf_layout(s, pl, pl.wf_capacity);
+    const WfLayout l = wf_layout(pl, pl.wf_capacity);
+    const mcpt::WfRoute& r = pl.route;
     grow_ws(s, s.ws.wf, l.need * size_t(sets), pl.capturing);
     // a default-batch render that grew the queues past the reservation: the
     // grown queues are the reservation now (a later captured render of the same
@@ -106,23 +129,17 @@ void prepare_wavefront(mcpt_scene& s, const Plan& pl, int sets, mcpt::WfParams* 
         w.capacity = pl.wf_capacity;                   // paths per batch (pid range)
         w.slot_stride = static_cast<uint32_t>(l.cap_slots);
         w.refill_thresh = clamp_i(pl.wf_refill, 1, 64);
-        w.group_shift = pl.wf_group_shift;
         w.sort = pl.wf_sort;
-        // a culled ray stands for color * (0 * illum) = 0: illum must be finite,
-        // and so must the throughput, a product of at most max_depth Kd / Ks
-        // components (each rounding grows it by 2^-24 at most: 2^127 leaves room)
-        const bool zero = std::isfinite(pl.kp.illum) &&
-                          std::log2(std::max(1.0, double(s.cull_gain))) * pl.kp.max_depth < 127.0;
-        w.n_cull_boxes = zero ? s.n_cull_boxes : 0u;
+        // what the route decided, once for every batch
+        w.nseg = r.nseg;
+        w.group_shift = r.group_shift;
+        w.xcd_deal = r.xcd_deal;
+        w.shade_cull = r.shade_cull ? 1u : 0u;
+        w.n_cull_boxes = r.n_cull_boxes;
         std::memcpy(w.cull_box, s.cull_box, sizeof w.cull_box);
-        // (counting renders walk every ray: their visit counters stay the oracle's)
-        w.n_miss_boxes = pl.kp.lean ? s.n_miss_boxes : 0u;
+        w.n_miss_boxes = r.n_miss_boxes;
         std::memcpy(w.miss_box, s.miss_box, sizeof w.miss_box);
-        // direct lists: active where the miss cull runs in front of the lean LDS extend
-        // and the tables fit beside the image (direct_lists_fit implies a scene in
-        // LDS).  Decided here alone: direct_counts != 0 is what launch_wavefront reads
-        const bool direct = w.n_miss_boxes && mcpt::direct_lists_fit(s.gpu.image_bytes, s.gpu.node_boxes);
-        w.direct_counts = direct ? s.direct_counts : 0u;
+        w.direct_counts = r.direct_counts;
         std::memcpy(w.direct_list, s.direct_list, sizeof w.direct_list);
     }
 }
@@ -194,9 +211,13 @@ uint32_t tea16(uint32_t v0, uint32_t v1) {   // MCRT/QuinEngine/Shader/rtx.hlsl:
 
 // lanes ready before a shading round: scenes in LDS 32 (sweep 16..48);
 // scenes in global memory 40 (C4: 24 5.15, 32 5.38, 40 5.50, 48 5.39 G rays/s)
-int ready_thresh_for(const mcpt_scene& s, int32_t asked) { return asked > 0 ? asked : (s.gpu.node_boxes == 1 ? 40 : 32); }
+int ready_thresh_for(const mcpt_scene& s, int32_t asked) { return asked > 0 ? asked : (mcpt::scene_in_lds(s.gpu) ? 32 : 40); }
 
-size_t launched_lanes(const mcpt_scene& s) { return static_cast<size_t>(mcpt::total_lanes_for(s.gpu.image_bytes, s.cus)); }
+size_t launched_lanes(const mcpt_scene& s) { return static_cast<size_t>(mcpt::total_lanes_for(s.gpu, s.cus)); }
+
+mcpt::WfFacts scene_facts(const mcpt_scene& s) {   // (the render's facts: false / 0)
+    return mcpt::WfFacts{&s.gpu, s.n_miss_boxes, s.direct_counts, s.n_cull_boxes, s.cus};
+}
 
 // The traversal's stack spill area: kSpillEntries 16-B entries per launched
 // lane, which the kernels index by lane -- once per set of concurrently running
@@ -294,12 +315,12 @@ Plan make_plan(const mcpt_scene& s, const mcpt_render_params* p) {
     // idle lanes before an extend wave refills: 16 for scenes in LDS (C2 sweep
     // 8 / 16 / 24: 10.08 / 10.28 / 10.19 G rays/s), 8 for scenes in global
     // memory (C4 256 spp, 2..40: 6.18 / 6.20 (4-12) / 6.14 (16) / 5.79 (32) / 5.53)
-    pl.wf_refill = p->wf_refill > 0 ? p->wf_refill : (s.gpu.node_boxes ? 8 : 16);
+    pl.wf_refill = p->wf_refill > 0 ? p->wf_refill : (mcpt::scene_in_lds(s.gpu) ? 16 : 8);
     // global-memory scenes keep whole image regions together per segment.
     // Round 4 (XCD-aware dealing, 7-entry stacks; C4 1024 spp, G rays/s):
     // 2^8 9.36, 2^9 8.39, 2^10 7.92 / 7.86, 2^11 9.70 / 9.73, 2^12 9.96 / 9.96 /
     // 9.98, 2^13 9.74, 2^14 9.83 / 9.87 / 9.85 (round 1, 256 spp: 2^14 best)
-    pl.wf_group_shift = s.gpu.node_boxes ? static_cast<uint32_t>(p->wf_group_shift > 0 ? p->wf_group_shift : 12) : 6u;
+    const uint32_t group_shift = static_cast<uint32_t>(p->wf_group_shift > 0 ? p->wf_group_shift : 12);
     // tail split: 4 units per lane (a whole frame +0.3% over 6; rank 0 of 8
     // shards at 97.0% of ideal, 6: 96.5%, 8: 95.7%, 10: 94.8%)
     pl.tail_per_lane = p->tail_units_per_lane == 0 ? kTailPerLane : p->tail_units_per_lane;
@@ -308,10 +329,11 @@ Plan make_plan(const mcpt_scene& s, const mcpt_render_params* p) {
     {
         const uint64_t work = std::max<uint64_t>(npix, 1) * std::max<uint64_t>(p->spp, chunk);
         pl.work = npix * p->spp;
-        const int nstr = wavefront_streams(s, work, p);
+        pl.wf_batch_explicit = p->wf_batch != 0;
+        pl.route = plan_route(s, pl, group_shift, false);
+        const int nstr = wavefront_streams(pl.route, work, p);
         pl.wf_streams = nstr;
         pl.wf_capacity = wf_batch_capacity(s, p, work, chunk, nstr);
-        pl.wf_batch_explicit = p->wf_batch != 0;
     }
     return pl;
 }
@@ -325,7 +347,7 @@ Plan make_plan(const mcpt_scene& s, const mcpt_render_params* p) {
 // LDS scenes on 2 streams: 2^28 each (C2 2 x 2^27 12.90, 2 x 2^28 13.03,
 // 3 x 2^27 13.06, 4 x 2^27 12.55 G rays/s, two rounds each; 86 GB of queues)
 uint32_t wf_batch_capacity(const mcpt_scene& s, const mcpt_render_params* p, uint64_t work, uint32_t chunk, int nstr) {
-    const bool big = nstr == 1 || (!s.gpu.node_boxes && nstr == 2);
+    const bool big = nstr == 1 || (mcpt::scene_in_lds(s.gpu) && nstr == 2);
     uint64_t cap = p->wf_batch ? p->wf_batch : (big ? (1u << 28) : (1u << 27));
     // a default batch gives every stream a batch of its own (one rank's C2
     // share at 8 GPUs, 2^27 paths: one 2^27 batch 9.26, two 2^26 12.61, four
@@ -352,6 +374,7 @@ void prepare_wavefront_list(mcpt_scene& s, Plan& pl, const Plan& pass0, uint32_t
     k.div_npix = mcpt::FastDiv::make(n);
     pl.work = uint64_t(n) * k.spp;
     pl.wf_streams = pass0.wf_streams;
+    pl.route = plan_route(s, pl, pl.route.group_shift, true);
     pl.wf_capacity = std::min(wf_batch_capacity(s, p, pl.work, k.chunk, pl.wf_streams), pass0.wf_capacity);
     prepare_workspace(s, pl, false, pl.sets());
     prepare_wavefront(s, pl, pl.sets(), out);
@@ -385,7 +408,7 @@ void fit_wavefront(const mcpt_scene& s, Plan& pl) {
         budget = avail > 0 ? static_cast<uint64_t>(avail) : 0;
         reserved = s.wf_reserved && !pl.wf_batch_explicit;
     }
-    auto need = [&](uint64_t cap) { return uint64_t(wf_layout(s, pl, cap).need) * uint64_t(pl.wf_streams); };
+    auto need = [&](uint64_t cap) { return uint64_t(wf_layout(pl, cap).need) * uint64_t(pl.wf_streams); };
     auto fit = [&](uint64_t b) {
         uint64_t cap = pl.wf_capacity;
         if (!pl.wf_batch_explicit)
@@ -545,21 +568,20 @@ int mcpt_plan_query(mcpt_scene* s, const mcpt_render_params* p, mcpt_plan_info* 
         std::memset(&r, 0, sizeof r);
         const bool wf = pl.pipeline == MCPT_PIPELINE_WAVEFRONT;
         r.pipeline = pl.pipeline;
-        // the wavefront: 4 with the image in LDS beside the extend's counter block, else 5
-        if (wf) r.variant = (!s->gpu.node_boxes && mcpt::lds_bytes_counted_in_lds(s->gpu.image_bytes, 4) <= mcpt::kMaxLds) ? 4 : 5;
+        if (wf) r.variant = pl.route.variant;
         else r.variant = mcpt::megakernel_variant(s->gpu).variant;
         r.wf_streams = wf ? pl.wf_streams : 0;
         r.wf_batch = wf ? pl.wf_capacity : 0;
         r.wf_batch_default = wf ? unfitted : 0;
         r.wf_refill = wf ? pl.wf_refill : 0;
-        r.wf_group_shift = wf ? static_cast<int32_t>(pl.wf_group_shift) : 0;
+        r.wf_group_shift = wf ? static_cast<int32_t>(pl.route.group_shift) : 0;
         r.ready_thresh = wf ? 0 : pl.kp.ready_thresh;
         r.tail_units = wf ? 0 : static_cast<int32_t>(tail_units_for(*s, pl));
         r.work_paths = pl.work;
         // what prepare_render would hold: partial sums, the small block, the spill areas, queues or tail
         uint64_t ws = uint64_t(pl.kp.nchunks) * pl.kp.npix_local * 16 + 256 + spill_bytes(*s, pl.sets());
         if (wf) {
-            r.wf_queue_bytes = uint64_t(wf_layout(*s, pl, pl.wf_capacity).need) * uint64_t(pl.wf_streams);
+            r.wf_queue_bytes = uint64_t(wf_layout(pl, pl.wf_capacity).need) * uint64_t(pl.wf_streams);
             ws += r.wf_queue_bytes;
         }
         else ws += uint64_t(r.tail_units) * pl.kp.chunk * 16;

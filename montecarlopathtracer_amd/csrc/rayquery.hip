@@ -43,6 +43,7 @@ namespace {
 #define MCPT_RQ_GLOBAL_WAVES MCPT_WF_GLOBAL_WAVES
 #endif
 constexpr int kRqLdsS = 4;
+static_assert(kRqLdsS <= 4, "scene_in_lds promises room for 4 stack entries per lane");
 
 // a lane's next ray, loaded a burst ahead
 struct NextRay {
@@ -199,14 +200,12 @@ hipError_t prepare_rq(size_t lds) {
 // code object at the first use of one of its kernels, which allocates): part
 // of the reserve, so that a query after it allocates nothing.
 hipError_t prepare_rayquery(const GpuScene& sc) {
-    if (sc.node_boxes) return prepare_rq<kLayGlobal, MCPT_RQ_GLOBAL_S, kGlobalBlock>(lds_bytes_global(MCPT_RQ_GLOBAL_S, true));
-    const size_t lds = lds_bytes_counted_in_lds(sc.image_bytes, kRqLdsS);
-    if (lds > kMaxLds) return hipErrorInvalidValue;
-    return prepare_rq<kLayLds, kRqLdsS, kLdsBlock>(lds);
+    if (!scene_in_lds(sc)) return prepare_rq<kLayGlobal, MCPT_RQ_GLOBAL_S, kGlobalBlock>(lds_bytes_global(MCPT_RQ_GLOBAL_S, true));
+    return prepare_rq<kLayLds, kRqLdsS, kLdsBlock>(lds_bytes_counted_in_lds(sc.image_bytes, kRqLdsS));
 }
 
 RayQueryGrid rayquery_grid(const GpuScene& sc, uint32_t n, int cus, int max_workgroups) {
-    const bool in_lds = !sc.node_boxes;
+    const bool in_lds = scene_in_lds(sc);
     // never more lanes than the scene's spill area holds (total_lanes_for)
     uint32_t wg = in_lds ? (uint32_t)cus : (uint32_t)cus * (uint32_t)kWfGlobalSegsPerCu;
     if (max_workgroups > 0 && (uint32_t)max_workgroups < wg) wg = (uint32_t)max_workgroups;
@@ -227,14 +226,12 @@ hipError_t launch_rayquery(const RayQueryParams& q_in, bool any, bool lean, int 
     const RayQueryGrid g = rayquery_grid(q.scene, q.n, cus, max_workgroups);
     q.seg = g.seg;
     // the extend's defaults (plan.cpp make_plan wf_refill)
-    if (q.refill <= 0) q.refill = q.scene.node_boxes ? 8 : 16;
-    if (q.scene.node_boxes)
+    if (q.refill <= 0) q.refill = scene_in_lds(q.scene) ? 16 : 8;
+    if (!scene_in_lds(q.scene))
         return launch_rq<kLayGlobal, MCPT_RQ_GLOBAL_S, kGlobalBlock>(q, any, lean, g.workgroups,
                                                                     lds_bytes_global(MCPT_RQ_GLOBAL_S, true), st);
-    // (an image without child boxes fits: scene_image.cpp build_image)
-    const size_t lds = lds_bytes_counted_in_lds(q.scene.image_bytes, kRqLdsS);
-    if (lds > kMaxLds) return hipErrorInvalidValue;
-    return launch_rq<kLayLds, kRqLdsS, kLdsBlock>(q, any, lean, g.workgroups, lds, st);
+    return launch_rq<kLayLds, kRqLdsS, kLdsBlock>(q, any, lean, g.workgroups,
+                                                  lds_bytes_counted_in_lds(q.scene.image_bytes, kRqLdsS), st);
 }
 
 }  // namespace mcpt

@@ -520,20 +520,17 @@ hipError_t launch_megakernel(const KernelParams& kp, const MegakernelVariant& v,
 
 }  // namespace
 
-size_t lds_bytes_in_lds(uint32_t image_bytes, int S) { return (size_t)image_bytes + (size_t)S * kLdsBlock * 16; }
-
 MegakernelVariant megakernel_variant(const GpuScene& sc) {
-    if (!sc.node_boxes) {                          // (else: an image built for global memory)
-        if (lds_bytes_in_lds(sc.image_bytes, 8) <= kMaxLds) return {1, true, 8};
-        if (lds_bytes_in_lds(sc.image_bytes, 4) <= kMaxLds) return {2, true, 4};
-    }
-    return {3, false, 8};
+    if (!scene_in_lds(sc)) return {3, false, 8};
+    // (the stack's depth: the megakernel's own choice, not where the scene lives)
+    if (lds_bytes_in_lds(sc.image_bytes, 8) <= kMaxLds) return {1, true, 8};
+    return {2, true, 4};
 }
 
 hipError_t launch_render(const KernelParams& kp_in, int cus, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
                          hipEvent_t ev2, float4* fb, int* variant_out) {
     KernelParams kp = kp_in;
-    kp.total_lanes = (uint32_t)total_lanes_for(kp.scene.image_bytes, cus);
+    kp.total_lanes = (uint32_t)total_lanes_for(kp.scene, cus);
     hipError_t e = hipMemsetAsync(kp.counter, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
     if (ev0 && (e = hipEventRecord(ev0, st)) != hipSuccess) return e;
@@ -553,7 +550,7 @@ hipError_t launch_render_list(const KernelParams& kp_in, int cus, hipStream_t st
                               int* variant_out) {
     KernelParams kp = kp_in;
     if (!kp.pixel_list || kp.mode == kModeQE || kp.unit_counters) return hipErrorInvalidValue;
-    kp.total_lanes = (uint32_t)total_lanes_for(kp.scene.image_bytes, cus);
+    kp.total_lanes = (uint32_t)total_lanes_for(kp.scene, cus);
     hipError_t e = hipMemsetAsync(kp.counter, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
     if (ev0 && (e = hipEventRecord(ev0, st)) != hipSuccess) return e;
@@ -578,21 +575,20 @@ hipError_t prepare_rad(size_t lds) {
     return e;
 }
 constexpr int kRadLdsS = 4;
+static_assert(kRadLdsS <= 4, "scene_in_lds promises room for 4 stack entries per lane");
 }  // namespace
 
 // The scene's two radiance kernels resolved on the current device (part of the
 // reserve: the runtime loads a code object at the first use of one of its kernels)
 hipError_t prepare_radiance(const GpuScene& sc) {
-    if (sc.node_boxes || lds_bytes_in_lds(sc.image_bytes, kRadLdsS) > kMaxLds)
-        return prepare_rad<false, 8, kGlobalBlock>(lds_bytes_global(8, false));
+    if (!scene_in_lds(sc)) return prepare_rad<false, 8, kGlobalBlock>(lds_bytes_global(8, false));
     return prepare_rad<true, kRadLdsS, kLdsBlock>(lds_bytes_in_lds(sc.image_bytes, kRadLdsS));
 }
 
 // Persistent workgroups as the megakernel's, but no more than the work feeds:
 // at least kRadMinUnits work items each (the ray queries' measured floor)
 uint32_t radiance_grid(const GpuScene& sc, uint64_t items, int cus, int max_workgroups) {
-    const bool in_lds = !sc.node_boxes && lds_bytes_in_lds(sc.image_bytes, kRadLdsS) <= kMaxLds;
-    uint64_t wg = in_lds ? (uint64_t)cus : (uint64_t)cus * kGlobalBlocksPerCu;   // (the spill area's lanes)
+    uint64_t wg = scene_in_lds(sc) ? (uint64_t)cus : (uint64_t)cus * kGlobalBlocksPerCu;   // (the spill area's lanes)
     if (max_workgroups > 0 && (uint64_t)max_workgroups < wg) wg = (uint64_t)max_workgroups;
     const uint64_t fed = (items + kRadMinUnits - 1) / kRadMinUnits;
     if (fed < wg) wg = fed;
@@ -606,11 +602,11 @@ hipError_t launch_radiance(const KernelParams& kp_in, const RayInputs& ri, int c
     KernelParams kp = kp_in;
     if (!kp.npix_local) return hipSuccess;
     if (kp.mode != 0 || kp.unit_counters || kp.pixel_list || !ri.o || !ri.d) return hipErrorInvalidValue;
-    kp.total_lanes = (uint32_t)total_lanes_for(kp.scene.image_bytes, cus);
+    kp.total_lanes = (uint32_t)total_lanes_for(kp.scene, cus);
     hipError_t e = hipMemsetAsync(kp.counter, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
     const uint32_t grid = radiance_grid(kp.scene, kp.total_items, cus, max_workgroups);
-    if (kp.scene.node_boxes || lds_bytes_in_lds(kp.scene.image_bytes, kRadLdsS) > kMaxLds)
+    if (!scene_in_lds(kp.scene))
         e = launch_rad<false, 8, kGlobalBlock>(kp, ri, grid, lds_bytes_global(8, false), st);
     else
         e = launch_rad<true, kRadLdsS, kLdsBlock>(kp, ri, grid, lds_bytes_in_lds(kp.scene.image_bytes, kRadLdsS), st);
@@ -636,7 +632,7 @@ hipError_t launch_reduce(const KernelParams& kp, float4* fb, hipStream_t st) {
 hipError_t launch_query(const QueryParams& q, hipStream_t st) {
     if (!q.n) return hipSuccess;
     const dim3 grid((q.n + kQueryBlock - 1) / kQueryBlock);
-    if (q.scene.node_boxes)
+    if (!scene_in_lds(q.scene))
         hipLaunchKernelGGL((query_kernel<true, 8>), grid, dim3(kQueryBlock), 0, st, q);
     else
         hipLaunchKernelGGL((query_kernel<false, 4>), grid, dim3(kQueryBlock), 0, st, q);
@@ -649,9 +645,11 @@ hipError_t launch_gather(const GatherParams& g, hipStream_t st) {
     return hipGetLastError();
 }
 
-int total_lanes_for(uint32_t image_bytes, int cus) {
-    // an image that fits in LDS is built without leaf boxes (scene_image.cpp build_image)
-    if (lds_bytes_counted_in_lds(image_bytes, 4) <= kMaxLds) return cus * kLdsBlock;
+// (the default four workgroups of 256 per CU are the LDS kernels' 1024 lanes: the
+// count is then the same wherever the scene lives, a small scene forced into
+// global memory included)
+int total_lanes_for(const GpuScene& sc, int cus) {
+    if (scene_in_lds(sc)) return cus * kLdsBlock;
     return cus * (kGlobalBlocksPerCu > kWfGlobalSegsPerCu ? kGlobalBlocksPerCu : kWfGlobalSegsPerCu) * kGlobalBlock;
 }
 

@@ -96,9 +96,6 @@ mcpt::WfStreams wf_streams_on(const mcpt_scene& s, int n, hipStream_t st) {
     }
     return wst;
 }
-int wf_queries(const mcpt::KernelParams& kp) {
-    return kp.mode == MCPT_MODE_QUINENGINE ? 3 * kp.max_depth + 1 : kp.max_depth + 1;
-}
 
 // d_var: also the per-pixel variance of this call's pixel mean (variance.hip),
 // from the partial sums the render's kernels wrote, behind them on st.
@@ -123,8 +120,7 @@ void render_async(mcpt_scene& s, const mcpt_render_params* p, float* d_fb, hipSt
     HIP_TRY(hipMemsetAsync(tile_classes(s), 0, 16, st));
     const Timing t = acquire_timing(s, pl.capturing);
     if (pl.pipeline == MCPT_PIPELINE_WAVEFRONT) {
-        HIP_TRY(mcpt::launch_wavefront(pl.kp, R.wf, wf_streams_on(s, pl.sets(), st), s.cus, wf_queries(pl.kp),
-                                       !pl.wf_batch_explicit, t.e[0], t.e[1], t.e[2],
+        HIP_TRY(mcpt::launch_wavefront(pl.kp, pl.route, R.wf, wf_streams_on(s, pl.sets(), st), t.e[0], t.e[1], t.e[2],
                                        reinterpret_cast<float4*>(d_fb), &s.last_variant));
     } else {
         HIP_TRY(mcpt::launch_render(pl.kp, s.cus, st, t.e[0], t.e[1], t.e[2], reinterpret_cast<float4*>(d_fb),
@@ -475,35 +471,29 @@ void adaptive_async(mcpt_scene& s, const mcpt_render_params* p, const Adaptive& 
         const uint32_t n = *s.ad_host_n;
         if (!n) break;
         if (n > npix) throw mcpt::Error{MCPT_E_DEVICE, "adaptive pixel list longer than the frame"};
+        Prepared R;
+        R.pl = make_plan(s, &pj);
+        mcpt::KernelParams& k = R.pl.kp;
+        Timing t;
         if (wavefront) {
-            Prepared R;
-            R.pl = make_plan(s, &pj);
             prepare_wavefront_list(s, R.pl, pass0, n, &pj, R.wf);
-            mcpt::KernelParams& k = R.pl.kp;
             k.pixel_list = aw.list;
             // (a listed pass uses no primary lists: the scene reports no tile classes after it)
             HIP_TRY(hipMemsetAsync(tile_classes(s), 0, 16, st));
-            const Timing t = acquire_timing(s, false);
-            HIP_TRY(mcpt::launch_wavefront(k, R.wf, wf_streams_on(s, R.pl.sets(), st), s.cus, wf_queries(k),
-                                           !R.pl.wf_batch_explicit, t.e[0], t.e[1], nullptr, nullptr,
-                                           &s.last_variant));
-            HIP_TRY(mcpt::launch_adaptive_merge(k, fb, var, d_count, st));
-            HIP_TRY(hipEventRecord(t.e[2], st));
-            s.pending.push_back(t);
-            s.renders++;
-            continue;
+            t = acquire_timing(s, false);
+            HIP_TRY(mcpt::launch_wavefront(k, R.pl.route, R.wf, wf_streams_on(s, R.pl.sets(), st), t.e[0], t.e[1],
+                                           nullptr, nullptr, &s.last_variant));
+        } else {
+            // a frame of n listed pixels: the unit decode, tail split and partial-sum
+            // layout are the megakernel's own, over n pixels instead of npix_local
+            k.npix_local = n;
+            k.total_units = n * k.nchunks;
+            k.div_npix = mcpt::FastDiv::make(n);
+            prepare_workspace(s, R.pl, true);
+            k.pixel_list = aw.list;
+            t = acquire_timing(s, false);
+            HIP_TRY(mcpt::launch_render_list(k, s.cus, st, t.e[0], t.e[1], &s.last_variant));
         }
-        // a frame of n listed pixels: the unit decode, tail split and partial-sum
-        // layout are the megakernel's own, over n pixels instead of npix_local
-        Plan pl = make_plan(s, &pj);
-        mcpt::KernelParams& k = pl.kp;
-        k.npix_local = n;
-        k.total_units = n * k.nchunks;
-        k.div_npix = mcpt::FastDiv::make(n);
-        prepare_workspace(s, pl, true);
-        k.pixel_list = aw.list;
-        const Timing t = acquire_timing(s, false);
-        HIP_TRY(mcpt::launch_render_list(k, s.cus, st, t.e[0], t.e[1], &s.last_variant));
         HIP_TRY(mcpt::launch_adaptive_merge(k, fb, var, d_count, st));
         HIP_TRY(hipEventRecord(t.e[2], st));
         s.pending.push_back(t);

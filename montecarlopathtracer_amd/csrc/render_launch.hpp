@@ -358,20 +358,20 @@ struct WfParams {
     // its list, 0 = the box's rays walk -- and kDirectK words of direct_list, their
     // record indices (the unit of the image's leaf refs) in image order.
     // direct_counts == 0: no ray is direct and none carries a selector (the lists
-    // are off for the render: plan.cpp prepare_wavefront decides, and nothing
-    // after it asks again).  Behind everything else in the kernel arguments
+    // are off for the render: WfRoute::direct, wf_route.hpp).  Behind everything
+    // else in the kernel arguments
     uint32_t direct_counts;
     uint32_t direct_list[kDirectTableWords];
     // 1: the queue-order shade owns the terminal cull and carries resolved rays
-    // ("Terminal cull", "Direct resolve" above; launch_wavefront decides per
-    // render: lean, scene in LDS with occluder boxes, wf_sort = 0).  The last
-    // kernel argument: no offset an extend reads moves
+    // ("Terminal cull", "Direct resolve" above; the route decides per render,
+    // WfRoute::shade_cull: lean, scene in LDS with occluder boxes, wf_sort = 0).
+    // The last kernel argument: no offset an extend reads moves
     uint32_t shade_cull;
 };
 
 // LDS need of the in-LDS variant for a scene image of `image_bytes`: the
 // stack's S entries per lane, then the image
-size_t lds_bytes_in_lds(uint32_t image_bytes, int S);
+inline size_t lds_bytes_in_lds(uint32_t image_bytes, int S) { return (size_t)image_bytes + (size_t)S * kLdsBlock * 16; }
 // The persistent kernels that hand out slots from an LDS counter (wavefront
 // extends, ray queries) keep it behind the stack and the image, in a 32-B block:
 // LDS bytes of such a workgroup with the scene in LDS, and with it in global memory
@@ -379,25 +379,17 @@ constexpr size_t kLdsCounterBytes = 32;
 inline size_t lds_bytes_counted_in_lds(uint32_t image_bytes, int S) {
     return lds_bytes_in_lds(image_bytes, S) + kLdsCounterBytes;
 }
-// direct lists: the lean LDS extend keeps its table (a clipped ray's listed box)
-// behind the counter block, and the shade's static LDS -- its copy of the lists'
-// records and 64 B of counters -- must fit beside the extend's workgroup.
-// Neither decides where a scene lives: if they do not fit beside the image the
-// scene stays in LDS and its renders make no direct rays and no selectors
-inline bool direct_lists_fit(uint32_t image_bytes, uint32_t node_boxes) {
-    const size_t need = kDirectShadeLds + 64 + kDirectLdsBytes;
-    return !node_boxes && lds_bytes_counted_in_lds(image_bytes, 4) + need <= kMaxLds;
-}
-// dynamic LDS of a wf_primary_shade launch (Primary shade, above): the lean LDS
-// extend's -- stack, image, counter block -- and, where the direct lists are
-// active, its table; the kernel has no static LDS.  launch_wavefront launches
-// with it, mcpt_scene_primary_shade_lds reports it
-inline size_t primary_shade_lds_bytes(uint32_t image_bytes, bool direct) {
-    return lds_bytes_counted_in_lds(image_bytes, 4) + (direct ? kDirectLdsBytes : 0);
-}
 constexpr size_t lds_bytes_global(int S, bool counted) {
     return (size_t)S * kGlobalBlock * 16 + (counted ? kLdsCounterBytes : 0);
 }
+// Where a scene lives.  build_image (scene_image.cpp) alone compares an image's
+// size with kMaxLds, and it fills every GpuScene there is (replicas copy the
+// primary's; a cached KD tree goes through build_image like a built one): an
+// image that does not fit is built with child boxes, so
+//   !node_boxes  implies  lds_bytes_counted_in_lds(image_bytes, 4) <= kMaxLds
+// and every kernel with S = 4 stack entries per lane, counter block or not,
+// has room for an image without them.  No launcher tests the size again.
+inline bool scene_in_lds(const GpuScene& sc) { return !sc.node_boxes; }
 // the megakernel's variant for a scene (mcpt_render_stats::variant): 1 / 2 the
 // image in LDS with S = 8 / 4 stack entries, 3 in global memory (an image built
 // with child boxes, or one too large for LDS)
@@ -407,7 +399,8 @@ struct MegakernelVariant {
     int S;
 };
 MegakernelVariant megakernel_variant(const GpuScene& sc);
-int total_lanes_for(uint32_t image_bytes, int cus);
+// lanes the persistent kernels launch for a scene: they index the spill area
+int total_lanes_for(const GpuScene& sc, int cus);
 #ifdef __HIP__
 // a kernel's dynamic LDS limit raised to lds_bytes; then also its launch
 template <typename K>
@@ -441,14 +434,12 @@ hipError_t launch_query(const QueryParams& q, hipStream_t st);
 void read_lane_use(unsigned long long out[6]);      // diagnostic build only: megakernel
 void read_lane_use_wf(unsigned long long out[6]);   // wavefront extend
 #endif
-// wavefront queue segments (= extend workgroups) for a scene image
-int wavefront_segments(const GpuScene& sc, int cus);
 // wavefront pipeline: generate / extend / shade per bounce / accumulate per
 // batch, then the same reduction (events: ev0 before, ev1 after the batches)
 // wavefront streams: batch i runs on stream i mod n (st[0] = the caller's),
 // forked from and joined back into st[0] with the events of each extra stream.
-// default_batch: the plan chose wf[].capacity (mcpt_render_params::wf_batch 0);
-// the batches of a render that can use the primary lists are then whole tiles.
+// route: the render's (wf_route.hpp), from the plan that filled wf[]; the batches
+// of a default-batch render that can use the primary lists are whole tiles.
 // kp.pixel_list set (adaptive sampling's listed passes): a frame of kp.npix_local
 // listed pixels, CV mode -- wf_generate_list fills an explicit queue 0, bounce 0
 // runs the ordinary extend and shade, no candidate pass; fb == nullptr then skips
@@ -459,8 +450,8 @@ struct WfStreams {
     hipStream_t st[kMaxWfStreams];
     hipEvent_t fork, join[kMaxWfStreams];
 };
-hipError_t launch_wavefront(const KernelParams& kp, const WfParams* wf, const WfStreams& ws, int cus,
-                            int max_bounces, bool default_batch, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2,
-                            float4* fb, int* variant_out);
+struct WfRoute;
+hipError_t launch_wavefront(const KernelParams& kp, const WfRoute& route, const WfParams* wf, const WfStreams& ws,
+                            hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2, float4* fb, int* variant_out);
 
 }  // namespace mcpt

@@ -148,7 +148,8 @@ void build_image(mcpt_scene& s, bool force_global) {
     };
     size_t off_nodes, off_leafs, off_geoms;
     size_t total = image_size(ord, off_nodes, off_leafs, off_geoms);
-    if (mcpt::lds_bytes_in_lds(static_cast<uint32_t>(std::min<size_t>(total, 0xFFFFFFF0u)), 4) + 32 > mcpt::kMaxLds ||
+    // where the scene lives, decided here alone (scene_in_lds, render_launch.hpp, has the invariant)
+    if (mcpt::lds_bytes_counted_in_lds(static_cast<uint32_t>(std::min<size_t>(total, 0xFFFFFFF0u)), 4) > mcpt::kMaxLds ||
         force_global) {
         boxes = true;
         total = image_size(ord, off_nodes, off_leafs, off_geoms);
@@ -549,10 +550,10 @@ uint64_t mcpt_scene_extend_rays(const mcpt_scene* s) { return s ? s->extend_rays
 uint64_t mcpt_scene_clipped_rays(const mcpt_scene* s) { return s ? s->clipped_rays : 0; }
 uint64_t mcpt_scene_primary_shaded(const mcpt_scene* s) { return s ? s->primary_shaded : 0; }
 uint64_t mcpt_scene_primary_shade_lds(const mcpt_scene* s) {
-    if (!s || s->gpu.node_boxes || mcpt::lds_bytes_counted_in_lds(s->gpu.image_bytes, 4) > mcpt::kMaxLds) return 0;
-    // (the lists as prepare_wavefront turns them on for a lean render: plan.cpp)
-    const bool direct = s->n_miss_boxes && s->direct_counts && mcpt::direct_lists_fit(s->gpu.image_bytes, s->gpu.node_boxes);
-    return mcpt::primary_shade_lds_bytes(s->gpu.image_bytes, direct);
+    if (!s) return 0;
+    mcpt::WfFacts f = scene_facts(*s);   // (a lean render's route: the lists as it turns them on)
+    f.lean = true;
+    return mcpt::wf_route(f).primary_shade_lds;
 }
 
 int mcpt_scene_copy_kd(const mcpt_scene* s, uint32_t* nodes, uint32_t* leaf_ids, int32_t* kd_tris, float* geoms) {

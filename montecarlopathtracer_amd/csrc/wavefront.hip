@@ -403,7 +403,7 @@ wf_extend(const KernelParams kp, const WfParams wf) {
 // Queue order (SORTB false): each wave takes the indices of its free lanes from
 // one LDS counter, 64 or fewer at a time, lanes ascending, so the reads stay
 // contiguous; there is no barrier in its loop.  Where wf.shade_cull is set
-// (launch_wavefront: lean, LDS scene with occluder boxes) it also owns the
+// (WfRoute::shade_cull: lean, LDS scene with occluder boxes) it also owns the
 // terminal cull -- a walking ray made for the terminal query goes through
 // terminal_ray_adds, wf_cull_terminal's rule, and is dropped there -- and it
 // carries: a lane whose new ray it resolved keeps ray, path state and hit id
@@ -802,10 +802,6 @@ hipError_t launch_extend(const KernelParams& kp, const WfParams& wf, int grid, s
     return launch_dyn_lds(kern, dim3(grid), dim3(BLOCK), lds, st, kp, wf);
 }
 
-// the scene image (8-B node records) is copied into LDS; an image built with
-// child-box pair records (node_boxes) is always read from global memory
-bool wf_in_lds(const GpuScene& sc) { return !sc.node_boxes && lds_bytes_counted_in_lds(sc.image_bytes, 4) <= kMaxLds; }
-
 }  // namespace
 
 #ifdef MCPT_PHASE_TIMING
@@ -818,75 +814,99 @@ void read_lane_use_wf(unsigned long long out[6]) {   // wavefront extend lane-us
 
 namespace {
 
-// The batch split of a render, one run of chunks at a time: from `chunk` on,
-// ncb chunks of nsc samples each are rendered together (whole-image batches may
-// span several full chunks: fewer, longer launches), in batches of at most
-// nb_max pixels each.  whole: batches that cut the frame hold whole 8x8 tiles
-// (a default batch of a render that can use the primary lists: work / streams
-// pixels are no whole tiles when the tile count is odd, nor is a batch over a
-// chunk length that does not divide it, and such a render would walk every
-// primary ray).
-struct WfSpan {
-    uint32_t nsc, ncb, nb_max;
+// One batch on its stream: what launch_wavefront's steps share
+struct WfBatch {
+    const WfRoute& route;
+    KernelParams kp;                     // the render's, with this stream's spill area
+    WfParams wf;                         // the stream's, with the batch's fields and the bounce under way
+    hipStream_t st;
+    bool lists;                          // bounce 0 reads the primary lists (a batch of whole tiles)
 };
-WfSpan wf_span(const KernelParams& kp, uint32_t capacity, uint32_t chunk, bool whole) {
-    WfSpan s;
-    s.nsc = (kp.spp - chunk * kp.chunk) < kp.chunk ? (kp.spp - chunk * kp.chunk) : kp.chunk;
-    s.ncb = 1;
-    if (s.nsc == kp.chunk && (uint64_t)kp.npix_local * kp.chunk <= capacity) {
-        const uint32_t full = (kp.spp / kp.chunk) - chunk;             // full chunks left
-        const uint32_t fit = (uint32_t)(capacity / ((uint64_t)kp.npix_local * kp.chunk));
-        s.ncb = fit < full ? fit : full;
-    }
-    s.nb_max = capacity / (s.ncb * s.nsc);
-    if (whole && s.nb_max >= 64u && s.nb_max < kp.npix_local) s.nb_max &= ~63u;
-    return s;
+
+// (a frame over a pixel list: its generate looks the pixel up)
+hipError_t launch_generate(const WfBatch& b) {
+    const uint32_t n = b.wf.nb * b.wf.ns, gen_grid = (n + kGenBlock - 1) / kGenBlock, cap = 16u * (uint32_t)b.route.cus;
+    hipLaunchKernelGGL(b.kp.pixel_list ? wf_generate_list : wf_generate, dim3(gen_grid < cap ? gen_grid : cap),
+                       dim3(kGenBlock), 0, b.st, b.kp, b.wf);
+    return hipGetLastError();
 }
-// (a batch whose pixel range is not whole 8x8 tiles keeps the walk: its 64-slot
-// groups would straddle tiles)
-bool whole_tiles(uint32_t v0, uint32_t nb) { return (v0 & 63u) == 0u && (nb & 63u) == 0u; }
-// whether any batch of the split is whole tiles, i.e. can read the primary lists
-bool any_whole_tile_batch(const KernelParams& kp, uint32_t capacity, bool whole) {
-    for (uint32_t chunk = 0; chunk < kp.nchunks;) {
-        const WfSpan s = wf_span(kp, capacity, chunk, whole);
-        chunk += s.ncb;
-        // every batch but the last holds nb_max pixels: whole tiles only if nb_max is (then
-        // all are; npix_local is whole 8x8 tiles); else the last one alone can be, which
-        // ends with the frame, if it starts on a tile
-        const uint32_t last_v0 = (kp.npix_local - 1u) / s.nb_max * s.nb_max;
-        if ((s.nb_max & 63u) == 0u || whole_tiles(last_v0, kp.npix_local - last_v0)) return true;
+
+// The kernel that finds the hits of bounce b.wf.bounce.  Bounce 0 of a batch that reads
+// the primary lists: wf_primary_shade, which also shades it and fills queue 1
+// (*shaded: the bounce has no shade launch), or wf_primary_lists; of any other
+// batch of a render with an implicit queue 0: the packet extend; every other
+// bounce: the extend of where the scene lives.
+enum class Extend { kPrimaryShade, kPrimaryLists, kPacket, kLds, kGlobal };
+Extend extend_form(const WfRoute& r, int bounce, bool lists) {
+    if (bounce == 0 && lists) return r.primary_shade ? Extend::kPrimaryShade : Extend::kPrimaryLists;
+    if (bounce == 0 && r.packet) return Extend::kPacket;
+    return r.in_lds ? Extend::kLds : Extend::kGlobal;
+}
+hipError_t launch_bounce(const WfBatch& b, bool* shaded) {
+    const WfRoute& r = b.route;
+    const WfParams& wf = b.wf;
+    const Extend form = extend_form(r, wf.bounce, b.lists);
+    *shaded = form == Extend::kPrimaryShade;
+    switch (form) {
+        case Extend::kPrimaryShade: return launch_wavefront_primary_shade(b.kp, wf, (int)r.nseg, r.primary_shade_lds, b.st);
+        case Extend::kPrimaryLists: return launch_wavefront_primary_lists(b.kp, wf, (int)r.nseg, r.packet_lds, b.st);
+        case Extend::kPacket: return launch_wavefront_primary(b.kp, wf, (int)r.nseg, r.packet_lds, b.st);
+        case Extend::kLds: return launch_extend<kLayLds, 4, kLdsBlock>(b.kp, wf, (int)r.nseg, r.extend_lds, b.st);
+        default: return launch_extend<kLayGlobal, MCPT_WF_GLOBAL_S, kGlobalBlock>(b.kp, wf, (int)r.nseg, r.extend_lds, b.st);
     }
-    return false;
+}
+
+// Several streams: the shade runs in workgroups that fit on a CU beside the
+// extend's 16 waves (extend <= 88 VGPRs per lane, so 160 of the SIMD's 512 are
+// left: two <= 80-VGPR shade waves; 4 B of LDS): 512 threads for LDS scenes (one
+// 1024-thread extend workgroup with 157 KB of LDS per CU), 256 for global
+// scenes (four 256-thread extend workgroups), so shading fills the
+// extend's idle issue slots instead of waiting for it (C2 wavefront 10.10
+// -> 13.20, C4 at 1024 spp 6.14 -> 8.34 G rays/s).
+hipError_t launch_shade(const WfBatch& b, int streams) {
+    const WfRoute& r = b.route;
+    const bool geo = r.geo_lds != 0, sortb = b.wf.sort != 0;
+    const int block = wf_shade_block(r, streams);
+    // (named in this order: the code of the two smaller kernels depends on which is instantiated first)
+    auto kern = block == 1024 ? shade_kernel<1024>(geo, sortb)
+                : block == MCPT_WF_SHADE_LDS_BLOCK ? shade_kernel<MCPT_WF_SHADE_LDS_BLOCK>(geo, sortb)
+                                                   : shade_kernel<256>(geo, sortb);
+    hipLaunchKernelGGL(kern, dim3(r.nseg), dim3(block), r.geo_lds, b.st, b.kp, b.wf);
+    return hipGetLastError();
+}
+
+// generate (where the route has one), per bounce the extend, the shade and the
+// terminal cull on the bounce the route names, then the accumulate
+hipError_t launch_batch(WfBatch& b, int streams, uint32_t ncb) {
+    const WfRoute& r = b.route;
+    hipError_t e = hipMemsetAsync(b.wf.cnt, 0, sizeof(WfCounters) * (size_t)r.nseg * (size_t)(r.queries + 1), b.st);
+    if (e == hipSuccess && r.generate) e = launch_generate(b);
+    for (int bounce = 0; bounce < r.queries && e == hipSuccess; bounce++) {
+        bool shaded = false;
+        b.wf.bounce = bounce;
+        e = launch_bounce(b, &shaded);
+        if (e == hipSuccess && !shaded) e = launch_shade(b, streams);
+        if (e == hipSuccess && bounce + 1 == r.cull_bounce) {
+            b.wf.bounce = bounce + 1;
+            hipLaunchKernelGGL(wf_cull_terminal, dim3(r.nseg), dim3(kCullBlock), 0, b.st, b.kp, b.wf);
+            e = hipGetLastError();
+        }
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wf_accumulate, dim3((b.wf.nb + 255u) / 256u, ncb), dim3(256), 0, b.st, b.kp, b.wf);
+    return hipGetLastError();
 }
 
 }  // namespace
 
-int wavefront_segments(const GpuScene& sc, int cus) {
-    return wf_in_lds(sc) ? cus : cus * kWfGlobalSegsPerCu;
-}
-// LDS bytes of an LDS-scene extend workgroup: stack + image (or its part from the nodes on) + counters
-size_t wf_lds_extend_bytes(const GpuScene& sc) {
-    return lds_bytes_counted_in_lds(sc.image_bytes, 4);
-}
-
-hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, const WfStreams& ws, int cus,
-                            int max_bounces, bool default_batch, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2,
-                            float4* fb, int* variant_out) {
+hipError_t launch_wavefront(const KernelParams& kp_in, const WfRoute& route, const WfParams* wf_in, const WfStreams& ws,
+                            hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2, float4* fb, int* variant_out) {
     KernelParams kp = kp_in;
-    const uint32_t img = kp.scene.image_bytes;
-    const bool in_lds = wf_in_lds(kp.scene);
-    kp.total_lanes = (uint32_t)total_lanes_for(img, cus);
-    const uint32_t nseg = (uint32_t)wavefront_segments(kp.scene, cus);
+    kp.total_lanes = (uint32_t)total_lanes_for(kp.scene, route.cus);
     // Several streams (ws.n > 1): batch i runs on stream i mod n, each stream
     // with its own queues/counters (wf_in[i]) and stack spill area, so one
-    // batch's shade and the tail of its extend overlap another batch's extend.
-    // The shade then runs in workgroups that fit on a CU beside the extend's 16
-    // waves (extend <= 88 VGPRs per lane, so 160 of the SIMD's 512 are left:
-    // two <= 80-VGPR shade waves; 4 B of LDS): 512 threads for LDS scenes (one
-    // 1024-thread extend workgroup with 157 KB of LDS per CU), 256 for global
-    // scenes (four 256-thread extend workgroups), so shading fills the
-    // extend's idle issue slots instead of waiting for it (C2 wavefront 10.10
-    // -> 13.20, C4 at 1024 spp 6.14 -> 8.34 G rays/s).
+    // batch's shade and the tail of its extend overlap another batch's extend
+    // (launch_shade).
     const int ns = ws.n < 1 ? 1 : (ws.n > kMaxWfStreams ? kMaxWfStreams : ws.n);
     const hipStream_t st = ws.st[0];
     hipError_t e = hipSuccess;
@@ -894,22 +914,14 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
     if (!kp.npix_local) {   // a shard that owns no tile: no batch (the batch split below divides by npix_local)
         if (ev1 && (e = hipEventRecord(ev1, st)) != hipSuccess) return e;
         if (ev2 && (e = hipEventRecord(ev2, st)) != hipSuccess) return e;
-        if (variant_out) *variant_out = in_lds ? 4 : 5;
+        if (variant_out) *variant_out = route.variant;
         return hipSuccess;
     }
-    // primary lists: lean renders where the packet extend runs (CV mode, scene
-    // in LDS, implicit queue 0) whose tiles are 8x8 -- one tile of one sample
-    // per 64-slot group -- and whose scene a per-tile scan of every triangle
-    // suits (kListMaxTris).  The candidate pass runs once, on the caller's
-    // stream, before the batches' streams fork from it -- if the split below
-    // has a batch of whole tiles at all: a render none of whose batches can read
-    // the lists runs no pass and reports no tile classes.
-    const bool can_list = MCPT_WF_PACKET0 && MCPT_WF_GEN0 && MCPT_WF_IMPLICIT0 >= 2 && kp.lean && in_lds &&
-                          implicit0(kp, wf_in[0]) && kp.tile == 8 && kp.scene.n_tris <= kListMaxTris &&
-                          wf_in[0].tile_cand && wf_in[0].tile_classes;
-    // (a batch size the caller asked for is kept as asked)
-    const bool whole = can_list && default_batch;
-    const bool lists = can_list && any_whole_tile_batch(kp, wf_in[0].capacity, whole);
+    // primary lists (WfRoute::can_list): the candidate pass runs once, on the
+    // caller's stream, before the batches' streams fork from it -- if the split
+    // below has a batch of whole tiles at all: a render none of whose batches
+    // can read the lists runs no pass and reports no tile classes.
+    const bool lists = route.can_list && any_whole_tile_batch(kp, wf_in[0].capacity, route.whole);
     if (lists) {
         const uint32_t tiles = kp.npix_local >> 6;
         hipLaunchKernelGGL(wf_tile_candidates, dim3((tiles + kCandBlock / 64 - 1) / (kCandBlock / 64)),
@@ -925,112 +937,15 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
     // stream back into the caller's stream below, so no side stream keeps
     // writing the shared partial sums or spill areas behind a failed call.
     uint32_t batch = 0;
-    for (uint32_t chunk = 0; chunk < kp.nchunks && e == hipSuccess;) {
-        const WfSpan span = wf_span(kp, wf_in[0].capacity, chunk, whole);
-        const uint32_t nsc = span.nsc, ncb = span.ncb, nb_max = span.nb_max;
-        const uint32_t chunk0 = chunk;
-        chunk += ncb;
-        for (uint32_t v0 = 0; v0 < kp.npix_local && e == hipSuccess; v0 += nb_max, ++batch) {
-            const int h = (int)(batch % (uint32_t)ns);
-            const hipStream_t bs = ws.st[h];
-            KernelParams kb = kp;
-            kb.spill = kp.spill + (size_t)h * 32 * kp.total_lanes;       // this stream's spill area
-            WfParams wf = wf_in[h];
-            wf.nseg = nseg;
-            wf.chunk_index = chunk0;
-            wf.s_begin = chunk0 * kp.chunk;
-            wf.nsc = nsc;
-            wf.ns = ncb * nsc;
-            wf.v0 = v0;
-            wf.nb = (kp.npix_local - v0) < nb_max ? (kp.npix_local - v0) : nb_max;
-            const uint32_t n = wf.nb * wf.ns;
-            // direct lists: active where the plan left the counts (plan.cpp prepare_wavefront:
-            // a lean render of an LDS scene with occluder boxes, direct_lists_fit); the
-            // extend then holds the table, for a clipped ray's listed box
-            const bool direct = wf.direct_counts != 0;
-            // the queue-order shade of a lean render of an LDS scene with occluder boxes
-            // culls the terminal query's rays where it makes them and carries the rays it
-            // resolves; queues then hold mixed depths, and no wf_cull_terminal runs
-            wf.shade_cull = (kb.lean && in_lds && wf.sort == 0 && wf.n_miss_boxes != 0) ? 1u : 0u;
-            const size_t direct_lds = direct ? kDirectLdsBytes : 0;
-            // the shade's material table in LDS if it fits beside the extend's
-            // workgroups on a CU (MCPT_WF_GEO_LDS)
-            const size_t ext_lds = in_lds ? wf_lds_extend_bytes(kp.scene) + direct_lds
-                                          : kWfGlobalSegsPerCu * lds_bytes_global(MCPT_WF_GLOBAL_S, true);
-            // (kDirectShadeLds: the shade's copy of the direct lists' records, static LDS)
-            const size_t geo_bytes = (MCPT_WF_GEO_LDS &&
-                                      ext_lds + kDirectShadeLds + 64 * (size_t)kp.scene.n_geoms + 64 <= kLdsPerCu)
-                                         ? 64 * (size_t)kp.scene.n_geoms : 0;
-            // LDS scenes: one 8x8 tile of one sample per group; global-memory
-            // scenes: the planned group size (whole image regions per segment)
-            wf.group_shift = in_lds ? 6u : wf_in[h].group_shift;
-            wf.xcd_deal = in_lds ? 0u : 1u;                                // (seg_of)
-            // whole groups per segment
-            wf.seg = ((((n + (1u << wf.group_shift) - 1u) >> wf.group_shift) + nseg - 1) / nseg) << wf.group_shift;
-            e = hipMemsetAsync(wf.cnt, 0, sizeof(WfCounters) * (size_t)nseg * (size_t)(max_bounces + 1), bs);
-            if (e != hipSuccess) break;
-            // bounce 0 of CV mode (implicit queue 0: every origin is the eye): the
-            // wave-coherent extend, one tree walk per 64-ray tile (MCPT_WF_PACKET0),
-            // which also generates the primary rays (MCPT_WF_GEN0)
-            // (the packet extend stores hit ids only: it needs the queue-order shade)
-            const bool packet = MCPT_WF_PACKET0 && in_lds && MCPT_WF_IMPLICIT0 >= 2 &&
-                                implicit0(kb, wf) && wf.group_shift == 6u;
-            if (!(packet && MCPT_WF_GEN0)) {
-                const uint32_t gen_grid = (n + kGenBlock - 1) / kGenBlock;
-                // (a frame over a pixel list: its generate looks the pixel up)
-                hipLaunchKernelGGL(kb.pixel_list ? wf_generate_list : wf_generate,
-                                   dim3(gen_grid < 16u * (uint32_t)cus ? gen_grid : 16u * (uint32_t)cus),
-                                   dim3(kGenBlock), 0, bs, kb, wf);
-                if ((e = hipGetLastError()) != hipSuccess) break;
-            }
-            for (int b = 0; b < max_bounces && e == hipSuccess; b++) {
-                wf.bounce = b;
-                const size_t llds = in_lds ? wf_lds_extend_bytes(kb.scene) : 0;
-                if (lists && packet && b == 0 && whole_tiles(wf.v0, wf.nb)) {
-                    wf.tile_cand = wf_in[0].tile_cand;
-                    // primary shade: where the queue-order shade culls and carries, the kernel that
-                    // resolves the groups also shades them and fills queue 1 -- no bounce-0 shade
-                    // (LDS: the lean extend's, the table only where the lists are active)
-                    if (wf.shade_cull) {
-                        e = launch_wavefront_primary_shade(kb, wf, (int)nseg,
-                                                           primary_shade_lds_bytes(kb.scene.image_bytes, direct), bs);
-                        continue;
-                    }
-                    e = launch_wavefront_primary_lists(kb, wf, (int)nseg, llds, bs);
-                } else if (packet && b == 0) {
-                    e = launch_wavefront_primary(kb, wf, (int)nseg, llds, bs);
-                } else if (in_lds) {
-                    e = launch_extend<kLayLds, 4, kLdsBlock>(kb, wf, (int)nseg, llds + direct_lds, bs);
-                } else
-                    e = launch_extend<kLayGlobal, MCPT_WF_GLOBAL_S, kGlobalBlock>(
-                        kb, wf, (int)nseg, lds_bytes_global(MCPT_WF_GLOBAL_S, true), bs);
-                if (e != hipSuccess) break;
-                const bool sortb = wf.sort != 0;
-                if (in_lds && ns == 1)   // alone on the GPU: 16 waves per segment keep HBM busy
-                    hipLaunchKernelGGL(shade_kernel<1024>(geo_bytes != 0, sortb), dim3(nseg), dim3(1024), geo_bytes, bs, kb, wf);
-                else if (in_lds)              // beside an extend workgroup: 8 waves (2 x 80 VGPRs per SIMD)
-                    hipLaunchKernelGGL(shade_kernel<MCPT_WF_SHADE_LDS_BLOCK>(geo_bytes != 0, sortb), dim3(nseg),
-                                       dim3(MCPT_WF_SHADE_LDS_BLOCK), geo_bytes, bs, kb, wf);
-                else
-                    hipLaunchKernelGGL(shade_kernel<256>(geo_bytes != 0, sortb), dim3(nseg), dim3(256), geo_bytes, bs, kb, wf);
-                e = hipGetLastError();
-                // the terminal query's queue (CV: a scene with emitter boxes; QE:
-                // every ray) loses the rays whose hit adds nothing; counting
-                // renders keep the full walk, so their visit counters stay the oracle's
-                // (where the shade culls such a ray as it makes it, wf.shade_cull, none is left)
-                const bool qe = kb.mode == kModeQE;
-                if (e == hipSuccess && kb.lean && !wf.shade_cull && b + 1 < max_bounces &&
-                    b + 1 == (qe ? 3 : 1) * kb.max_depth && (qe || wf.n_cull_boxes)) {
-                    wf.bounce = b + 1;
-                    hipLaunchKernelGGL(wf_cull_terminal, dim3(nseg), dim3(kCullBlock), 0, bs, kb, wf);
-                    e = hipGetLastError();
-                }
-            }
-            if (e != hipSuccess) break;
-            hipLaunchKernelGGL(wf_accumulate, dim3((wf.nb + 255u) / 256u, ncb), dim3(256), 0, bs, kb, wf);
-            e = hipGetLastError();
-        }
-    }
+    wf_for_each_batch(kp, wf_in[0].capacity, route.whole, [&](const WfSpan& span, uint32_t chunk0, uint32_t v0) {
+        const int h = (int)(batch++ % (uint32_t)ns);
+        WfBatch b{route, kp, wf_batch_params(wf_in[h], route, kp, span, chunk0, v0), ws.st[h], false};
+        b.kp.spill = kp.spill + (size_t)h * 32 * kp.total_lanes;       // this stream's spill area
+        b.lists = lists && whole_tiles(b.wf.v0, b.wf.nb);
+        if (b.lists) b.wf.tile_cand = wf_in[0].tile_cand;             // (stream 0's records are the render's)
+        e = launch_batch(b, ns, span.ncb);
+        return e == hipSuccess;
+    });
     for (int i = 1; i < ns; i++) {   // join (also after an error)
         hipError_t j = hipEventRecord(ws.join[i], ws.st[i]);
         if (j == hipSuccess) j = hipStreamWaitEvent(st, ws.join[i], 0);
@@ -1042,7 +957,7 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfParams* wf_in, co
     // the partial sums into its pixels, adaptive.hip)
     if (fb) e = launch_reduce(kp, fb, st);
     if (e == hipSuccess && ev2) e = hipEventRecord(ev2, st);
-    if (variant_out) *variant_out = in_lds ? 4 : 5;
+    if (variant_out) *variant_out = route.variant;
     return e;
 }
 

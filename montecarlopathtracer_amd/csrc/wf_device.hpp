@@ -4,7 +4,8 @@
 // primary-list form, compiled with flags of their own) and
 // wavefront_primary_shade.hip (the list form that also shades bounce 0).  The queue layout, the
 // dealing of paths to segments, the MCPT_WF_* tuning macros with their
-// measurements, and the two launch entry points of wavefront_primary.hip.
+// measurements (those the host's route reads: wf_route.hpp), and the two
+// launch entry points of wavefront_primary.hip.
 // rayquery.hip takes the extend's layouts and tuning defaults from here.
 #pragma once
 
@@ -15,6 +16,7 @@
 #include "mcpt_device.hpp"
 #include "render_launch.hpp"
 #include "trace_device.hpp"
+#include "wf_route.hpp"
 
 namespace mcpt {
 
@@ -169,15 +171,9 @@ __device__ __forceinline__ uint32_t seg_queue0_len(const WfParams& wf, uint32_t 
     return len;
 }
 
-// MCPT_WF_IMPLICIT0 = 1: bounce 0's shade (queue order, CV mode) recomputes a
-// primary ray's origin, direction and RNG state from its slot instead of
-// reading them, and generate skips the {throughput, rng} stream (64 B of
-// queue traffic less per path); 2 (default): also the {o, pid} stream
-// (extend's bounce-0 origins are the eye; 32 B more).  With MCPT_WF_NT = 3:
-// level 1 C2 wavefront +0.3%, level 2 +0.9% (C4 +1.4%).
-#ifndef MCPT_WF_IMPLICIT0
-#define MCPT_WF_IMPLICIT0 2
-#endif
+// (MCPT_WF_IMPLICIT0, MCPT_WF_PACKET0, MCPT_WF_GEN0 and the defaults of
+// MCPT_WF_GLOBAL_S, MCPT_WF_SHADE_LDS_BLOCK and MCPT_WF_GEO_LDS: wf_route.hpp,
+// whose host conditions read them)
 // CV mode: every primary ray starts at the eye -- what the extend's bounce 0
 // asks before it takes its origins from the kernel arguments (level 2)
 __host__ __device__ __forceinline__ bool eye_origins0(const KernelParams& kp) {
@@ -231,9 +227,6 @@ constexpr int kWfLdsCap = MCPT_WF_DESCENT_CAP;
 // S = 8, no hint (round 3: 32 KB, four workgroups, 88 VGPRs) 9.46 / 9.47;
 // S = 6 9.61 / 9.63; S = 7 (five workgroups) 9.85 / 9.87; S = 5 9.20; S = 4
 // 8.78 (spills); S = 6 with six workgroups (80 VGPRs) 10.36 / 10.31.
-#ifndef MCPT_WF_GLOBAL_S
-#define MCPT_WF_GLOBAL_S 6
-#endif
 #ifndef MCPT_WF_GLOBAL_WAVES
 #define MCPT_WF_GLOBAL_WAVES 6
 #endif
@@ -247,35 +240,14 @@ static_assert(kGlobalBlock == 256, "MCPT_WF_GLOBAL_WAVES = workgroups per CU onl
 #ifndef MCPT_WF_LDS_WPE
 #define MCPT_WF_LDS_WPE 0
 #endif
-#ifndef MCPT_WF_SHADE_LDS_BLOCK
-#define MCPT_WF_SHADE_LDS_BLOCK 512
-#endif
-#ifndef MCPT_WF_GEO_LDS
-#define MCPT_WF_GEO_LDS 1
-#endif
-constexpr size_t kLdsPerCu = 160 * 1024;
 // scene layouts of the persistent traversal kernels (wf_extend, rq_trace)
 constexpr int kLayGlobal = 0, kLayLds = 1;
 
-// Bounce 0 of CV mode by the wave-coherent packet extend (wavefront_primary.hip)
-#ifndef MCPT_WF_PACKET0
-#define MCPT_WF_PACKET0 1
-#endif
 __device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
 // read-only words another kernel wrote, at wave-uniform addresses: the
 // constant address space (scalar loads; wf_primary_body.hpp)
 typedef const __attribute__((address_space(4))) uint32_t const_u32;
 typedef const __attribute__((address_space(4))) u32x4 const_u32x4;
-
-// MCPT_WF_GEN0 (default 1): no generate kernel before the packet extend -- each
-// lane computes its slot's primary ray itself (the inverse dealing slot_pid
-// and primary_ray, as bounce 0's shade already does), writes the segment's
-// queue length and counts the paths; queue 0 holds no direction stream.
-// Generate was the only kernel of a frame's start (0.9 ms of one rank's 33 ms
-// share at N = 8) and moved 16 B per path through HBM twice.
-#ifndef MCPT_WF_GEN0
-#define MCPT_WF_GEN0 1
-#endif
 
 }  // namespace
 }  // namespace mcpt

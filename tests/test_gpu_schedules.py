@@ -17,7 +17,7 @@ A  the wavefront, scene in LDS: scene01 (five direct-list boxes, the terminal cu
 B  the wavefront, scene in global memory: scene01 forced there, and cornell_bunny70k
 C  the megakernel: scene01 in both layouts
 
-`batch_split` restates launch_wavefront's split (wavefront.hip) and `capacity`
+`batch_split` restates launch_wavefront's split (wf_route.hpp) and `capacity`
 make_plan's batch size (plan.cpp); each schedule's property -- why it is no duplicate of
 the default -- is asserted on them without a GPU, and `capacity` against `Scene.plan`
 with one.
