@@ -344,6 +344,17 @@ uint64_t mcpt_scene_clipped_rays(const mcpt_scene* s);
  * to the record's paths there, 0 for every other render.  (An addition, as the
  * ones above; the ABI stays 9.) */
 uint64_t mcpt_scene_primary_shaded(const mcpt_scene* s);
+/* Sphere clip: the occluder boxes without a list that have a sphere over their
+ * triangles' vertices which cuts something off the box -- bit i of the result:
+ * box i of mcpt_scene_miss_cull_boxes; spheres (NULL, or room for 8 x 4 floats)
+ * receives {centre xyz, radius^2} per box, zeros for a box without one.  A lean
+ * wavefront render of a scene in LDS whose clip walk is active cuts a clipped
+ * ray's walk to its boxes' spheres.  (An addition; the ABI stays 9.) */
+uint32_t mcpt_scene_clip_spheres(const mcpt_scene* s, float* spheres);
+/* Of the clipped rays of the stats record last read, those whose walk was not
+ * started because a sphere left nothing of their interval; 0 for every render
+ * that does not clip to spheres.  (An addition; the ABI stays 9.) */
+uint64_t mcpt_scene_sphere_skips(const mcpt_scene* s);
 /* LDS bytes per workgroup that such a render's bounce-0 kernel is launched
  * with (all of it dynamic: the kernel has no static LDS), from the same
  * function the launch calls; 0 for a scene that is not rendered from LDS.

@@ -18,7 +18,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, os.environ.get("MCPT_LIB_NAME", "libmcpt.so"))
 SOURCES = ["host_model.cpp", "kd_cache.cpp", "capi.cpp", "scene_image.cpp", "plan.cpp", "render_host.cpp", "queries.cpp",
            "render.hip", "wavefront.hip", "wavefront_primary.hip", "wavefront_primary_shade.hip",
-           "aov.hip", "denoise.hip", "variance.hip", "denoise_var.hip", "adaptive.hip", "rayquery.hip"]
+           "wavefront_sphere.hip", "aov.hip", "denoise.hip", "variance.hip", "denoise_var.hip", "adaptive.hip", "rayquery.hip"]
 # per-source code generation (wavefront_primary.hip: the bounce-0 packet extend's
 # wave-uniform control flow as scalar branches; render.hip: GVN hoisting,
 # megakernel +1.4%, no effect on the wavefront kernels, and the global-memory
@@ -32,6 +32,8 @@ SOURCE_FLAGS = {"wavefront_primary.hip": ["-mllvm", "-structurizecfg-skip-unifor
                 # (not the packet extend's option: it miscompiles the divergent shading code)
                 "wavefront_primary_shade.hip": _WF_FLAGS,
                 "wavefront.hip": _WF_FLAGS,
+                # the lean LDS extend's body again: its flags
+                "wavefront_sphere.hip": _WF_FLAGS,
                 # the ray queries' kernel is the extend's loop: it starts from the extend's flags
                 "rayquery.hip": _WF_FLAGS,
                 "render.hip": ["-mllvm", "-enable-gvn-hoist", "-mllvm", "-unroll-threshold=2000"]}
@@ -41,7 +43,7 @@ SOURCE_FLAGS = {"wavefront_primary.hip": ["-mllvm", "-structurizecfg-skip-unifor
 SOURCE_SCHED = {"wavefront_primary_shade.hip": "iterative-minreg"}
 HEADERS = ["capi_internal.hpp", "staging.hpp", "host_model.hpp", "mcpt_device.hpp", "render_launch.hpp", "wf_route.hpp", "trace_device.hpp", "half_box.hpp",
            "aov_device.hpp", "aov_launch.hpp", "variance_launch.hpp", "adaptive_launch.hpp", "partial_sum.hpp", "rayquery_launch.hpp",
-           "wf_device.hpp", "wf_primary_body.hpp", "wf_primary_walk.hpp", "wf_primary_pairs.hpp", "wf_primary_shade_body.hpp", "wf_shade_item.hpp"]
+           "wf_device.hpp", "wf_extend_body.hpp", "wf_primary_body.hpp", "wf_primary_walk.hpp", "wf_primary_pairs.hpp", "wf_primary_shade_body.hpp", "wf_shade_item.hpp"]
 ARCH = os.environ.get("MCPT_OFFLOAD_ARCH", "gfx950")
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-Wall",

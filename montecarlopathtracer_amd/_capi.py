@@ -173,6 +173,8 @@ _SIGS = {
     "mcpt_scene_extend_rays": (C.c_uint64, [_vp]),
     "mcpt_scene_clipped_rays": (C.c_uint64, [_vp]),
     "mcpt_scene_primary_shaded": (C.c_uint64, [_vp]),
+    "mcpt_scene_clip_spheres": (C.c_uint32, [_vp, C.POINTER(C.c_float)]),
+    "mcpt_scene_sphere_skips": (C.c_uint64, [_vp]),
     "mcpt_scene_primary_shade_lds": (C.c_uint64, [_vp]),
     "mcpt_scene_copy_kd": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
                                      C.POINTER(C.c_float)]),

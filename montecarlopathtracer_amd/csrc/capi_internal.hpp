@@ -131,6 +131,12 @@ struct mcpt_scene {
     uint64_t extend_rays = 0;           // likewise: the rays the secondary extends took
     uint64_t clipped_rays = 0;          // likewise: the rays an extend started with a selector (clip walk)
     uint64_t primary_shaded = 0;        // likewise: the paths whose bounce 0 wf_primary_shade shaded
+    // sphere clip: bit i -- box i has no list and a sphere {centre xyz, radius^2} that
+    // cuts something off it (render_launch.hpp "Sphere clip"; host_model.hpp clip_spheres)
+    uint32_t clip_spheres = 0;
+    float clip_sphere[mcpt::kMaxMissBoxes][4] = {};
+    uint64_t sphere_skips = 0;          // of the stats record last read: the selected rays a sphere left no walk
+    bool sphere_clipped = false;        // a render of this scene has issued or captured wf_sphere_clip (sticky)
     mcpt::host::DevBuf d_image, d_normals;
     mcpt::host::Workspace ws;
     std::vector<mcpt::host::Timing> pending, free_timing;

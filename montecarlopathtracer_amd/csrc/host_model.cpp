@@ -674,6 +674,55 @@ void direct_list_assign(const HostScene& hs, const float (*boxes)[6], int n_boxe
     }
 }
 
+uint32_t clip_spheres(const HostScene& hs, const float (*boxes)[6], int n_boxes, const std::vector<int32_t>& tri_box,
+                      uint32_t want, double margin, double max_reach, float (*spheres)[4]) {
+    const size_t nt = hs.kd_verts.size() / 9;
+    double smin[3] = {INFINITY, INFINITY, INFINITY}, smax[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (size_t k = 0; k < nt; ++k)
+        for (int j = 0; j < 9; ++j) {
+            const double v = hs.kd_verts[9 * k + j];
+            smin[j % 3] = std::min(smin[j % 3], v);
+            smax[j % 3] = std::max(smax[j % 3], v);
+        }
+    double diag2 = 0.0;
+    for (int a = 0; a < 3; ++a) diag2 += (smax[a] - smin[a]) * (smax[a] - smin[a]);
+    uint32_t mask = 0;
+    for (int b = 0; b < n_boxes; ++b) {
+        for (int a = 0; a < 4; ++a) spheres[b][a] = 0.0f;
+        if (!((want >> b) & 1u) || tri_box.size() != nt) continue;
+        float c[3];
+        double half2 = 0.0;                               // the half diagonal: the farthest box corner from c
+        for (int a = 0; a < 3; ++a) {
+            c[a] = (boxes[b][a] + boxes[b][3 + a]) * 0.5f;
+            const double h = std::max(double(boxes[b][3 + a]) - c[a], double(c[a]) - boxes[b][a]);
+            half2 += h * h;
+        }
+        double r2 = -1.0;
+        for (size_t k = 0; k < nt; ++k) {
+            if (tri_box[k] != b) continue;
+            for (int j = 0; j < 3; ++j) {
+                double d2 = 0.0;
+                for (int a = 0; a < 3; ++a) {
+                    const double d = double(hs.kd_verts[9 * k + 3 * j + a]) - c[a];
+                    d2 += d * d;
+                }
+                r2 = std::max(r2, d2);
+            }
+        }
+        if (!(r2 > 0.0) || !std::isfinite(r2) || !std::isfinite(half2)) continue;
+        const double r = std::sqrt(r2) * (1.0 + margin);
+        if (!(r * r < half2) || !(diag2 <= max_reach * max_reach * r * r)) continue;
+        // radius^2 rounded up: the next fp32 at or above r * r (r already carries sqrt's rounding
+        // under a margin 2^42 times larger)
+        float r2f = static_cast<float>(r * r);
+        if (double(r2f) < r * r) r2f = std::nextafter(r2f, INFINITY);
+        if (!std::isfinite(r2f) || !std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2])) continue;
+        spheres[b][0] = c[0]; spheres[b][1] = c[1]; spheres[b][2] = c[2]; spheres[b][3] = r2f;
+        mask |= 1u << b;
+    }
+    return mask;
+}
+
 // ---------------------------------------------------------------------------
 // KD build (KDTree.hpp:58-287). Literal std::min/std::max forms keep the
 // signed-zero/NaN behaviour of the reference; float expressions keep its

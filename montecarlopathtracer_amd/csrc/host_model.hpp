@@ -98,6 +98,15 @@ int miss_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes);
 // of several holding boxes a triangle goes to does not matter: a hit on it lies
 // in every one of them, so the ray hits them all.
 void direct_list_assign(const HostScene& hs, const float (*boxes)[6], int n_boxes, std::vector<int32_t>& tri_box);
+// Sphere clip (render_launch.hpp "Sphere clip"): for each box of `want` (bit i: box i),
+// a sphere over the vertices of the triangles tri_box assigns to it -- centre: the
+// box centre as fp32 computes it, (lo + hi) * 0.5f; radius: the largest distance from
+// that centre to such a vertex, in double, times 1 + margin, and spheres[i] = {centre,
+// radius^2 rounded up to fp32}.  The returned mask keeps a box only if its sphere cuts
+// something off it (radius below the box's half diagonal), the scene's diagonal is at
+// most max_reach radii, and every value is finite; the others' entries are zeros.
+uint32_t clip_spheres(const HostScene& hs, const float (*boxes)[6], int n_boxes, const std::vector<int32_t>& tri_box,
+                      uint32_t want, double margin, double max_reach, float (*spheres)[4]);
 // on-disk KD cache (kd_cache.cpp): load returns false unless a valid file exists
 // (files are keyed by the vertices and the build rule)
 bool kd_cache_load(const std::string& dir, const std::vector<float>& tri_verts, std::vector<KdNode>& nodes,

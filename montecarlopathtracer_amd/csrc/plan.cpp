@@ -216,7 +216,10 @@ int ready_thresh_for(const mcpt_scene& s, int32_t asked) { return asked > 0 ? as
 size_t launched_lanes(const mcpt_scene& s) { return static_cast<size_t>(mcpt::total_lanes_for(s.gpu, s.cus)); }
 
 mcpt::WfFacts scene_facts(const mcpt_scene& s) {   // (the render's facts: false / 0)
-    return mcpt::WfFacts{&s.gpu, s.n_miss_boxes, s.direct_counts, s.n_cull_boxes, s.cus};
+    mcpt::WfFacts f{&s.gpu, s.n_miss_boxes, s.direct_counts, s.n_cull_boxes, s.cus};
+    f.clip_spheres = s.clip_spheres;
+    f.clip_sphere = s.clip_sphere;
+    return f;
 }
 
 // The traversal's stack spill area: kSpillEntries 16-B entries per launched

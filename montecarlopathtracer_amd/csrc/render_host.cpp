@@ -120,6 +120,7 @@ void render_async(mcpt_scene& s, const mcpt_render_params* p, float* d_fb, hipSt
     HIP_TRY(hipMemsetAsync(tile_classes(s), 0, 16, st));
     const Timing t = acquire_timing(s, pl.capturing);
     if (pl.pipeline == MCPT_PIPELINE_WAVEFRONT) {
+        s.sphere_clipped = s.sphere_clipped || pl.route.clip.mask != 0;
         HIP_TRY(mcpt::launch_wavefront(pl.kp, pl.route, R.wf, wf_streams_on(s, pl.sets(), st), t.e[0], t.e[1], t.e[2],
                                        reinterpret_cast<float4*>(d_fb), &s.last_variant));
     } else {
@@ -151,11 +152,22 @@ void read_stats(mcpt_scene& s, mcpt_render_stats* out) {
     s.extend_rays = 0;
     s.clipped_rays = 0;
     s.primary_shaded = 0;
+    s.sphere_skips = 0;
     if (s.ws.small.p) {
         unsigned long long st[mcpt::kStatSlots];
         char* const block = static_cast<char*>(s.ws.small.p) + 64;
         HIP_TRY(hipMemcpy(st, block, sizeof st, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemset(block, 0, sizeof st));
+        // the sphere skips, behind the tile classes.  Once a render of the scene has issued or captured
+        // wf_sphere_clip every record reads and clears them, as it does its neighbours: a captured render
+        // sets the flag once and its graph's replays keep counting.  A scene that never launches the
+        // kernel reads and clears its record exactly as before
+        if (s.sphere_clipped) {
+            unsigned long long skips = 0;
+            HIP_TRY(hipMemcpy(&skips, block + 8 * mcpt::kStatSphereSkips, 8, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemset(block + 8 * mcpt::kStatSphereSkips, 0, 8));
+            s.sphere_skips = skips;
+        }
         HIP_TRY(hipStreamSynchronize(nullptr));   // (as in prepare_workspace: before a render on a non-blocking stream)
         if (st[8] | st[9] | st[10] | st[11])   // diagnostic builds (-DMCPT_PHASE_TIMING) only
             std::fprintf(stderr, "mcpt phase cycles (sum over waves): units %llu trav %llu shade %llu burst_iters %llu "
@@ -305,6 +317,7 @@ void read_stats_all(mcpt_scene& s, mcpt_render_stats* out) {
         s.extend_rays += R->extend_rays;
         s.clipped_rays += R->clipped_rays;
         s.primary_shaded += R->primary_shaded;
+        s.sphere_skips += R->sphere_skips;
         r.kernel_ms = std::max(r.kernel_ms, q.kernel_ms);
         r.reduce_ms = std::max(r.reduce_ms, q.reduce_ms);
     }
@@ -481,6 +494,7 @@ void adaptive_async(mcpt_scene& s, const mcpt_render_params* p, const Adaptive& 
             // (a listed pass uses no primary lists: the scene reports no tile classes after it)
             HIP_TRY(hipMemsetAsync(tile_classes(s), 0, 16, st));
             t = acquire_timing(s, false);
+            s.sphere_clipped = s.sphere_clipped || R.pl.route.clip.mask != 0;
             HIP_TRY(mcpt::launch_wavefront(k, R.pl.route, R.wf, wf_streams_on(s, R.pl.sets(), st), t.e[0], t.e[1],
                                            nullptr, nullptr, &s.last_variant));
         } else {

@@ -179,7 +179,32 @@ static_assert(kMaxMissBoxes <= 8, "the clip walk's selector is one byte of box b
 constexpr int kStatClipped = 15;
 // the paths whose bounce 0 wf_primary_shade shaded (Primary shade, above): the slot behind it
 constexpr int kStatPrimaryShaded = 16;
+// Sphere clip (where the clip walk is active and a box without a list has a sphere):
+// an object's box is mostly empty at its corners (a tessellated sphere fills 52% of
+// its box), and a clipped ray that crosses only a corner still descends the tree to
+// find nothing.  The host keeps, per box without a list, a sphere over the vertices
+// of the triangles assigned to it (host_model.cpp clip_spheres: centre at the
+// box centre, the radius inflated by kSphereMargin), and wf_sphere_clip -- the lean
+// LDS extend with this one change -- intersects each unlisted box's slab interval
+// with the ray's interval in that box's sphere (sphere_interval, trace_device.hpp)
+// before the union: a hit the walk could accept lies on a triangle, hence inside its
+// box's sphere, with its t inside the ray's interval there.  Which rays are culled,
+// direct, clipped or walked is the shade's decision and does not change; only where a
+// clipped ray's walk starts and ends does, and a ray with nothing left starts none.
+// The radius' relative margin
+constexpr double kSphereMargin = 1.0 / 1024.0;
+// a sphere is kept only where the scene's diagonal is at most this many radii: a
+// clipped ray's origin lies in the scene, so |centre - o| / R stays below it and
+// the fp32 error of sphere_interval stays a small part of the margin
+constexpr double kSphereMaxReach = 256.0;
 constexpr int kStatSlots = 17;
+// the selected rays whose walk a sphere left nothing of (counted per wave by
+// wf_sphere_clip): the next free 8 bytes of the block KernelParams::stats points
+// into -- behind the kStatSlots slots and the 8 + 16 bytes of the tile classes that
+// follow them (plan.cpp tile_classes), which stay where every render's memset
+// expects them; render_host.cpp reads and clears it with the slots
+constexpr int kStatSphereSkips = kStatSlots + 3;
+static_assert(64 + 8 * (kStatSphereSkips + 1) <= 256, "the scene's small block (plan.cpp prepare_workspace)");
 
 struct GpuGeom {
     float Ka[3], Kd[3], Ks[3];
@@ -367,6 +392,14 @@ struct WfParams {
     // WfRoute::shade_cull: lean, scene in LDS with occluder boxes, wf_sort = 0).
     // The last kernel argument: no offset an extend reads moves
     uint32_t shade_cull;
+};
+// Sphere clip ("Sphere clip" above): bit i of mask -- occluder box i has no list and a
+// sphere {centre xyz, radius^2} over its triangles that cuts something off the box.
+// wf_sphere_clip's third kernel argument, read as scalar operands: a kernel argument
+// of its own behind WfParams, so no argument an existing kernel reads moves or grows
+struct SphereClip {
+    uint32_t mask;
+    float sphere[kMaxMissBoxes][4];
 };
 
 // LDS need of the in-LDS variant for a scene image of `image_bytes`: the

@@ -272,6 +272,12 @@ void build_image(mcpt_scene& s, bool force_global) {
         if (s.box_tris[b] >= 1 && s.box_tris[b] <= mcpt::kDirectK) s.direct_counts |= s.box_tris[b] << (4u * b);
         else std::memset(&s.direct_list[size_t(b) * mcpt::kDirectK], 0, 4 * mcpt::kDirectK);
     }
+    // sphere clip: a sphere over the triangles of every box that has some and no list
+    uint32_t unlisted = 0;
+    for (uint32_t b = 0; b < s.n_miss_boxes; ++b)
+        if (s.box_tris[b] > mcpt::kDirectK) unlisted |= 1u << b;
+    s.clip_spheres = mcpt::clip_spheres(hs, s.miss_box, static_cast<int>(s.n_miss_boxes), s.tri_box, unlisted,
+                                        mcpt::kSphereMargin, mcpt::kSphereMaxReach, s.clip_sphere);
     s.cull_gain = 0.0f;
     for (const mcpt::Geometry& ge : hs.geoms)
         for (float k : {ge.Kd.x, ge.Kd.y, ge.Kd.z, ge.Ks.x, ge.Ks.y, ge.Ks.z})
@@ -328,6 +334,8 @@ int scene_create_impl(const mcpt_model* m, mcpt_scene** out, bool device, const 
                 std::memcpy(R->miss_box, s->miss_box, sizeof s->miss_box);
                 R->direct_counts = s->direct_counts;
                 std::memcpy(R->direct_list, s->direct_list, sizeof s->direct_list);
+                R->clip_spheres = s->clip_spheres;
+                std::memcpy(R->clip_sphere, s->clip_sphere, sizeof s->clip_sphere);
                 upload(*R, devs[i], s->image, nrm);
                 HIP_TRY(hipStreamCreateWithFlags(&R->stream, hipStreamNonBlocking));
                 HIP_TRY(hipEventCreateWithFlags(&R->done, hipEventDisableTiming));
@@ -549,6 +557,12 @@ uint64_t mcpt_scene_direct_rays(const mcpt_scene* s) { return s ? s->direct_rays
 uint64_t mcpt_scene_extend_rays(const mcpt_scene* s) { return s ? s->extend_rays : 0; }
 uint64_t mcpt_scene_clipped_rays(const mcpt_scene* s) { return s ? s->clipped_rays : 0; }
 uint64_t mcpt_scene_primary_shaded(const mcpt_scene* s) { return s ? s->primary_shaded : 0; }
+uint64_t mcpt_scene_sphere_skips(const mcpt_scene* s) { return s ? s->sphere_skips : 0; }
+uint32_t mcpt_scene_clip_spheres(const mcpt_scene* s, float* spheres) {
+    if (!s) return 0;
+    if (spheres) std::memcpy(spheres, s->clip_sphere, sizeof s->clip_sphere);
+    return s->clip_spheres;
+}
 uint64_t mcpt_scene_primary_shade_lds(const mcpt_scene* s) {
     if (!s) return 0;
     mcpt::WfFacts f = scene_facts(*s);   // (a lean render's route: the lists as it turns them on)

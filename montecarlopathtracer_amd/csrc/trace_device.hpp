@@ -358,6 +358,28 @@ __device__ __forceinline__ void box_interval(V3 o, V3 d, V3 inv, float best_init
     lo = max_qnan(max3_qnan(0.0f, nx ? bx : ax, ny ? by : ay), nz ? bz : az);
     hi = min_qnan(min3_qnan(best_init, nx ? ax : bx, ny ? ay : by), nz ? az : bz);
 }
+// Sphere clip (render_launch.hpp "Sphere clip"): [lo, hi] cut to the interval of ray
+// (o, d) in the sphere s = {centre xyz, radius^2}.  With m = centre - o and tc =
+// (m.d)/(d.d), the line's closest point to the centre, the half chord is
+// sqrt((R^2 - |m - tc d|^2) / (d.d)): the distance to the line is taken from the
+// perpendicular itself, whose error grows with |m| and not with |m|^2 as the textbook
+// discriminant's does.  Plain fp32 in this order, one IEEE division and square root
+// (tests/test_sphere_clip_cpu.py restates it).  A line that misses the sphere leaves
+// the empty interval [FLT_MAX, 0]; a NaN anywhere (a zero or non-finite direction)
+// constrains nothing, by the NaN-passing max / min.
+__device__ __forceinline__ void sphere_interval(V3 o, V3 d, const float (&s)[4], float& lo, float& hi) {
+    const float mx = s[0] - o.x, my = s[1] - o.y, mz = s[2] - o.z;
+    const float a = (d.x * d.x + d.y * d.y) + d.z * d.z;
+    const float b = (mx * d.x + my * d.y) + mz * d.z;
+    const float ia = 1.0f / a;
+    const float tc = b * ia;
+    const float px = mx - tc * d.x, py = my - tc * d.y, pz = mz - tc * d.z;
+    const float q = s[3] - ((px * px + py * py) + pz * pz);
+    const float h = sqrt_rn(q * ia);
+    const bool miss = q < 0.0f;
+    lo = miss ? kFltMax : max_qnan(lo, tc - h);
+    hi = miss ? 0.0f : min_qnan(hi, tc + h);
+}
 // Miss cull and direct lists (render_launch.hpp "Miss cull", "Direct lists"): which
 // of the scene's n occluder boxes can ray (o, d) hit?  slab_hit on the segment
 // (0, best_init] against each box, fp32 bounds taken from the vertices unrounded

@@ -32,6 +32,10 @@ hipError_t launch_wavefront_primary_lists(const KernelParams& kp, const WfParams
 // ... and the list form that also shades bounce 0 (lds: the lean LDS extend's with its direct table)
 hipError_t launch_wavefront_primary_shade(const KernelParams& kp, const WfParams& wf, int grid, size_t lds,
                                           hipStream_t st);
+// wavefront_sphere.hip: the lean LDS extend that cuts a clipped ray's walk to its
+// boxes' spheres (lds: the lean LDS extend's)
+hipError_t launch_wavefront_sphere_clip(const KernelParams& kp, const WfParams& wf, const SphereClip& clip, int grid,
+                                        size_t lds, hipStream_t st);
 
 namespace {
 

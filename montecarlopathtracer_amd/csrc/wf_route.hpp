@@ -72,6 +72,9 @@ struct WfFacts {
     bool tile_records;                   // the workspace has the primary lists' tile records (wf_layout)
     int tile, max_depth;
     uint32_t group_shift;                // the plan's, for a scene in global memory
+    // sphere clip: the scene's mask and spheres (mcpt_scene::clip_spheres, ::clip_sphere; null: none)
+    uint32_t clip_spheres;
+    const float (*clip_sphere)[4];
 };
 
 struct WfRoute {
@@ -98,6 +101,8 @@ struct WfRoute {
     // extend (with the direct table where the lists are active: direct_lds);
     // wf_primary_shade; the shade's material table (0: read from global memory)
     size_t packet_lds, extend_lds, direct_lds, primary_shade_lds, geo_lds;
+    // sphere clip: the scene's spheres where the secondary extends are wf_sphere_clip, else mask 0
+    SphereClip clip;
 };
 
 inline WfRoute wf_route(const WfFacts& f) {
@@ -122,6 +127,14 @@ inline WfRoute wf_route(const WfFacts& f) {
     // resolves; queues then hold mixed depths, and no wf_cull_terminal runs
     r.shade_cull = f.lean && r.in_lds && !f.sort && r.n_miss_boxes != 0;
     r.carry = r.shade_cull && r.direct;
+    // sphere clip: where the lean LDS extend clips walks (the lists active, the
+    // queue-order shade, CV mode) and a box without a list has a sphere, the
+    // secondary extends also cut a clipped ray's walk to its boxes' spheres
+    if (r.direct && f.lean && r.in_lds && !f.sort && !f.qe && f.clip_sphere) {
+        r.clip.mask = f.clip_spheres;
+        for (int b = 0; b < kMaxMissBoxes; b++)
+            for (int a = 0; a < 4; a++) r.clip.sphere[b][a] = f.clip_sphere[b][a];
+    }
     // LDS scenes: one 8x8 tile of one sample per group; global-memory scenes:
     // the planned group size (whole image regions per segment), dealt by XCD (seg_of)
     r.group_shift = r.in_lds ? 6u : f.group_shift;

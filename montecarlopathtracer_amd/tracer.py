@@ -339,6 +339,12 @@ class Scene:
                 "list_kd": list_kd[: 8 * k].reshape(8, k)[: len(box_tris)] if k else list_kd[:0].reshape(0, 0),
                 "counts": counts}
 
+    def clip_spheres(self) -> dict:
+        """The sphere clip's spheres: {"mask" (bit i: occluder box i has one), "spheres" ((8, 4)
+        float32 {centre xyz, radius^2}, zeros for a box without one)}."""
+        sp = np.zeros((8, 4), np.float32)
+        return {"mask": int(lib().mcpt_scene_clip_spheres(self.handle, _fptr(sp))), "spheres": sp}
+
     def _render_stats(self, st) -> dict:
         d = st.as_dict()
         # secondary rays resolved from a box's list instead of a walk (lean wavefront renders)
@@ -349,6 +355,8 @@ class Scene:
         d["clipped_rays"] = int(lib().mcpt_scene_clipped_rays(self.handle))
         # paths whose bounce 0 the kernel that resolved their primary rays also shaded (0: every other render)
         d["primary_shaded"] = int(lib().mcpt_scene_primary_shaded(self.handle))
+        # clipped rays whose walk a box's sphere left nothing of (0: a render that does not clip to spheres)
+        d["sphere_skips"] = int(lib().mcpt_scene_sphere_skips(self.handle))
         return d
 
     def primary_tile_classes(self):

@@ -15,7 +15,7 @@ def kernel_class(name):
         return "extend0+shade0"
     if "wf_extend_primary" in name or "wf_primary_lists" in name:
         return "extend0"
-    if "wf_extend" in name:
+    if "wf_extend" in name or "wf_sphere_clip" in name:   # (the secondary extend that clips walks to spheres)
         return "extend"
     if "wf_shade" in name:
         return "shade"

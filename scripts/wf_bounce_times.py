@@ -6,7 +6,8 @@ wf_primary_lists, which resolves the tiles' candidate lists, or wf_primary_shade
 which also shades bounce 0 and is reported as bounce 0's extend with a shade of
 0, so that the two together compare with earlier rows -- starts one) and
 indexed by bounce; wf_cull_terminal (the terminal cull in front of the last
-extend) and wf_tile_candidates (the primary lists' candidate pass, once per
+extend; wf_sphere_clip, the secondary extend that also clips walks to
+spheres, counts as its bounce's extend) and wf_tile_candidates (the primary lists' candidate pass, once per
 render) are summed on their own.  usage: wf_bounce_times.py DIR"""
 import csv
 import glob
@@ -41,7 +42,7 @@ def main(d):
             cull.append((t1 - t0) / 1e6)
         elif "wf_tile_candidates" in name:
             cand.append((t1 - t0) / 1e6)
-        elif "wf_extend" in name or "wf_primary_lists" in name:
+        elif "wf_extend" in name or "wf_primary_lists" in name or "wf_sphere_clip" in name:
             b_ext += 1
             ext[b_ext].append((t1 - t0) / 1e6)
         elif "wf_shade" in name:
