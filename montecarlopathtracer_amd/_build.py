@@ -41,7 +41,7 @@ SOURCE_FLAGS = {"wavefront_primary.hip": ["-mllvm", "-structurizecfg-skip-unifor
 # register-minimising scheduler holds its 88-VGPR budget without scratch; MCPT_SCHED, the
 # A/B variable, does not reach such a source -- any other scheduler gives it scratch)
 SOURCE_SCHED = {"wavefront_primary_shade.hip": "iterative-minreg"}
-HEADERS = ["capi_internal.hpp", "staging.hpp", "host_model.hpp", "mcpt_device.hpp", "render_launch.hpp", "wf_route.hpp", "trace_device.hpp", "half_box.hpp",
+HEADERS = ["capi_internal.hpp", "staging.hpp", "host_model.hpp", "mcpt_device.hpp", "render_launch.hpp", "stat_blocks.hpp", "wf_route.hpp", "trace_device.hpp", "half_box.hpp",
            "aov_device.hpp", "aov_launch.hpp", "variance_launch.hpp", "adaptive_launch.hpp", "partial_sum.hpp", "rayquery_launch.hpp",
            "wf_device.hpp", "wf_extend_body.hpp", "wf_primary_body.hpp", "wf_primary_walk.hpp", "wf_primary_pairs.hpp", "wf_primary_shade_body.hpp", "wf_shade_item.hpp"]
 ARCH = os.environ.get("MCPT_OFFLOAD_ARCH", "gfx950")

@@ -83,7 +83,7 @@ struct TempDev {
 
 struct Workspace {
     DevBuf partial;
-    DevBuf small;        // counter (64 B) + stats (kStatSlots x 8 B) + tile classes
+    DevBuf small;        // one mcpt::RenderBlock (stat_blocks.hpp): work-unit counter, stats, tile classes
     DevBuf spill;
     DevBuf fb;           // mcpt_render staging framebuffer
     DevBuf wf;           // wavefront queues / path state (one allocation)
@@ -92,6 +92,48 @@ struct Workspace {
 
 struct Timing {
     hipEvent_t e[3];
+};
+
+// What build_image's scene gives the wavefront's routes (route_tables, scene_image.cpp,
+// fills it from the host scene and the image's triangle order; a replica copies the
+// primary's whole).  A new table is a member here and its lines in route_tables
+struct RouteTables {
+    // terminal cull: emitter boxes as box_hit reads them (fp16 rounded outward);
+    // n_cull_boxes == 0: the scene does not allow the cull (host_model.hpp)
+    uint32_t n_cull_boxes = 0;
+    uint32_t cull_box[mcpt::kMaxCullBoxes][3] = {};
+    float cull_gain = 0.0f;             // the largest |Kd| or |Ks| component (finite when there are boxes)
+    // miss cull: occluder boxes {lo xyz, hi xyz}; n_miss_boxes == 0: none for the scene (host_model.hpp)
+    uint32_t n_miss_boxes = 0;
+    float miss_box[mcpt::kMaxMissBoxes][6] = {};
+    // direct lists: kd id -> its box; triangles per box; the small boxes' counts
+    // (4 bits each) and lists as the kernels take them (render_launch.hpp WfParams)
+    std::vector<int32_t> tri_box;
+    uint32_t box_tris[mcpt::kMaxMissBoxes] = {};
+    uint32_t direct_counts = 0;
+    uint32_t direct_list[mcpt::kMaxMissBoxes * 16] = {};
+    // sphere clip: bit i -- box i has no list and a sphere {centre xyz, radius^2} that
+    // cuts something off it (render_launch.hpp "Sphere clip"; host_model.hpp clip_spheres)
+    uint32_t clip_spheres = 0;
+    float clip_sphere[mcpt::kMaxMissBoxes][4] = {};
+};
+
+// The routes a wavefront render's rays took, of the stats record last read (read_stats
+// fills it from the kStat* slots of the same names; include/mcpt.h has each accessor's account)
+struct RouteCounts {
+    uint64_t direct_rays = 0;           // rays resolved from a box's list
+    uint64_t extend_rays = 0;           // rays the secondary extends took
+    uint64_t clipped_rays = 0;          // of those, the rays an extend started with a selector (clip walk)
+    uint64_t primary_shaded = 0;        // paths whose bounce 0 wf_primary_shade shaded
+    uint64_t sphere_skips = 0;          // the selected rays a sphere left no walk
+    RouteCounts& operator+=(const RouteCounts& o) {
+        direct_rays += o.direct_rays;
+        extend_rays += o.extend_rays;
+        clipped_rays += o.clipped_rays;
+        primary_shaded += o.primary_shaded;
+        sphere_skips += o.sphere_skips;
+        return *this;
+    }
 };
 
 // Restores the calling thread's current HIP device on every exit path
@@ -113,30 +155,8 @@ struct mcpt_scene {
     std::vector<unsigned char> image;   // host copy of the device image
     std::vector<uint32_t> tri_order;    // image triangle slot -> kd id
     mcpt::GpuScene gpu{};
-    // terminal cull: emitter boxes as box_hit reads them (fp16 rounded outward);
-    // n_cull_boxes == 0: the scene does not allow the cull (host_model.hpp)
-    uint32_t n_cull_boxes = 0;
-    uint32_t cull_box[mcpt::kMaxCullBoxes][3] = {};
-    float cull_gain = 0.0f;             // the largest |Kd| or |Ks| component (finite when there are boxes)
-    // miss cull: occluder boxes {lo xyz, hi xyz}; n_miss_boxes == 0: none for the scene (host_model.hpp)
-    uint32_t n_miss_boxes = 0;
-    float miss_box[mcpt::kMaxMissBoxes][6] = {};
-    // direct lists: kd id -> its box; triangles per box; the small boxes' counts
-    // (4 bits each) and lists as the kernels take them (render_launch.hpp WfParams)
-    std::vector<int32_t> tri_box;
-    uint32_t box_tris[mcpt::kMaxMissBoxes] = {};
-    uint32_t direct_counts = 0;
-    uint32_t direct_list[mcpt::kMaxMissBoxes * 16] = {};
-    uint64_t direct_rays = 0;           // of the stats record last read
-    uint64_t extend_rays = 0;           // likewise: the rays the secondary extends took
-    uint64_t clipped_rays = 0;          // likewise: the rays an extend started with a selector (clip walk)
-    uint64_t primary_shaded = 0;        // likewise: the paths whose bounce 0 wf_primary_shade shaded
-    // sphere clip: bit i -- box i has no list and a sphere {centre xyz, radius^2} that
-    // cuts something off it (render_launch.hpp "Sphere clip"; host_model.hpp clip_spheres)
-    uint32_t clip_spheres = 0;
-    float clip_sphere[mcpt::kMaxMissBoxes][4] = {};
-    uint64_t sphere_skips = 0;          // of the stats record last read: the selected rays a sphere left no walk
-    bool sphere_clipped = false;        // a render of this scene has issued or captured wf_sphere_clip (sticky)
+    mcpt::host::RouteTables tables;     // the culls' boxes, the direct lists, the clip spheres
+    mcpt::host::RouteCounts routes;     // of the stats record last read
     mcpt::host::DevBuf d_image, d_normals;
     mcpt::host::Workspace ws;
     std::vector<mcpt::host::Timing> pending, free_timing;
@@ -179,11 +199,11 @@ struct mcpt_scene {
     mcpt::host::DevBuf ad_list, ad_flags, ad_blocks;
     uint32_t* ad_host_n = nullptr;
     // device ray queries (mcpt_trace_device, mcpt_occluded_device): tri_order on
-    // the device, and the queries' own counters -- two 64-B blocks, the device
-    // entries' (mcpt_trace_stats_read) and the synchronous host entry's
+    // the device, and the queries' own counters -- one mcpt::QueryBlocks, the device
+    // entries' block (mcpt_trace_stats_read) and the synchronous host entries'
     mcpt::host::DevBuf rq_order, rq_stats;
     // device radiance queries (mcpt_radiance_device): partial sums [chunk][ray],
-    // the tail samples and the work-unit counter (counters: rq_stats)
+    // the tail samples and the work-unit counter (kUnitCounterBytes; counters: rq_stats)
     mcpt::host::DevBuf rad_partial, rad_tail, rad_small;
 
     // every device buffer of the scene: what the destructor frees (a new buffer
@@ -196,6 +216,12 @@ struct mcpt_scene {
 };
 
 namespace mcpt::host {
+
+// the scene's counter blocks on its device (null before the first render / query): addresses only
+inline mcpt::RenderBlock* render_block(const mcpt_scene& s) { return static_cast<mcpt::RenderBlock*>(s.ws.small.p); }
+inline mcpt::QueryBlocks* query_blocks(const mcpt_scene& s) { return static_cast<mcpt::QueryBlocks*>(s.rq_stats.p); }
+// the last render's tile classes (primary lists)
+inline uint32_t* tile_classes(const mcpt_scene& s) { return render_block(s)->tile_classes; }
 
 struct Plan {
     mcpt::KernelParams kp;
@@ -251,7 +277,8 @@ void prepare_wavefront_list(mcpt_scene& s, Plan& pl, const Plan& pass0, uint32_t
                             mcpt::WfParams* out);
 void fit_wavefront(const mcpt_scene& s, Plan& pl);
 void prepare_workspace(mcpt_scene& s, Plan& pl, bool tail_split = false, int spill_sets = 1);
-uint32_t* tile_classes(const mcpt_scene& s);
+// the eight Counters of a block as the record's fields of the same names (devices 1, all else 0)
+void stats_from_counters(const unsigned long long c[mcpt::kStatCounters], mcpt_render_stats& st);
 void prepare_render(mcpt_scene& s, const mcpt_render_params* p, bool capturing, bool unit_counters, Prepared& out);
 bool multi_device(const mcpt_scene& s, const mcpt_render_params* p, const uint32_t* d_unit_counters);
 mcpt_render_params shard_params(const mcpt_render_params& p, int n, int r);

@@ -62,7 +62,7 @@ mcpt::WfRoute plan_route(const mcpt_scene& s, const Plan& pl, uint32_t group_shi
     // a culled ray stands for color * (0 * illum) = 0: illum must be finite,
     // and so must the throughput, a product of at most max_depth Kd / Ks
     // components (each rounding grows it by 2^-24 at most: 2^127 leaves room)
-    const bool zero = std::isfinite(k.illum) && std::log2(std::max(1.0, double(s.cull_gain))) * k.max_depth < 127.0;
+    const bool zero = std::isfinite(k.illum) && std::log2(std::max(1.0, double(s.tables.cull_gain))) * k.max_depth < 127.0;
     if (!zero) f.n_cull_boxes = 0;
     f.lean = k.lean != 0;
     f.sort = pl.wf_sort != 0;
@@ -136,11 +136,12 @@ void prepare_wavefront(mcpt_scene& s, const Plan& pl, int sets, mcpt::WfParams* 
         w.xcd_deal = r.xcd_deal;
         w.shade_cull = r.shade_cull ? 1u : 0u;
         w.n_cull_boxes = r.n_cull_boxes;
-        std::memcpy(w.cull_box, s.cull_box, sizeof w.cull_box);
+        const RouteTables& t = s.tables;
+        std::memcpy(w.cull_box, t.cull_box, sizeof w.cull_box);
         w.n_miss_boxes = r.n_miss_boxes;
-        std::memcpy(w.miss_box, s.miss_box, sizeof w.miss_box);
+        std::memcpy(w.miss_box, t.miss_box, sizeof w.miss_box);
         w.direct_counts = r.direct_counts;
-        std::memcpy(w.direct_list, s.direct_list, sizeof w.direct_list);
+        std::memcpy(w.direct_list, t.direct_list, sizeof w.direct_list);
     }
 }
 
@@ -216,9 +217,10 @@ int ready_thresh_for(const mcpt_scene& s, int32_t asked) { return asked > 0 ? as
 size_t launched_lanes(const mcpt_scene& s) { return static_cast<size_t>(mcpt::total_lanes_for(s.gpu, s.cus)); }
 
 mcpt::WfFacts scene_facts(const mcpt_scene& s) {   // (the render's facts: false / 0)
-    mcpt::WfFacts f{&s.gpu, s.n_miss_boxes, s.direct_counts, s.n_cull_boxes, s.cus};
-    f.clip_spheres = s.clip_spheres;
-    f.clip_sphere = s.clip_sphere;
+    const RouteTables& t = s.tables;
+    mcpt::WfFacts f{&s.gpu, t.n_miss_boxes, t.direct_counts, t.n_cull_boxes, s.cus};
+    f.clip_spheres = t.clip_spheres;
+    f.clip_sphere = t.clip_sphere;
     return f;
 }
 
@@ -458,8 +460,8 @@ void prepare_workspace(mcpt_scene& s, Plan& pl, bool tail_split, int spill_sets)
     mcpt::KernelParams& k = pl.kp;
     grow_ws(s, s.ws.partial, size_t(k.nchunks) * k.npix_local * 16, pl.capturing);
     if (!s.ws.small.p) {
-        HIP_TRY(hipMalloc(&s.ws.small.p, 256));
-        HIP_TRY(hipMemset(s.ws.small.p, 0, 256));
+        HIP_TRY(hipMalloc(&s.ws.small.p, sizeof(mcpt::RenderBlock)));
+        HIP_TRY(hipMemset(s.ws.small.p, 0, sizeof(mcpt::RenderBlock)));
         // (the fill may still be in flight on the null stream, which a replica's
         // non-blocking stream does not wait for: its kernel's counters must land after it)
         HIP_TRY(hipStreamSynchronize(nullptr));
@@ -467,8 +469,8 @@ void prepare_workspace(mcpt_scene& s, Plan& pl, bool tail_split, int spill_sets)
     // (the wavefront's streams run extends concurrently: one spill area each)
     grow_spill(s, spill_sets, pl.capturing);
     k.partial = static_cast<float4*>(s.ws.partial.p);
-    k.counter = static_cast<uint32_t*>(s.ws.small.p);
-    k.stats = reinterpret_cast<unsigned long long*>(static_cast<char*>(s.ws.small.p) + 64);
+    k.counter = render_block(s)->counter;
+    k.stats = render_block(s)->stats;
     k.spill = static_cast<uint4*>(s.ws.spill.p);
     k.tail_units = k.total_units;
     k.total_items = k.total_units;
@@ -484,10 +486,12 @@ void prepare_workspace(mcpt_scene& s, Plan& pl, bool tail_split, int spill_sets)
     }
 }
 
-// the last render's tile classes (primary lists): three counters behind the
-// render counters in the scene's small block (prepare_workspace)
-uint32_t* tile_classes(const mcpt_scene& s) {
-    return reinterpret_cast<uint32_t*>(static_cast<char*>(s.ws.small.p) + 64 + 8 * mcpt::kStatSlots + 8);
+void stats_from_counters(const unsigned long long c[mcpt::kStatCounters], mcpt_render_stats& st) {
+    std::memset(&st, 0, sizeof st);
+    st.devices = 1;
+    st.rays = c[mcpt::kStatRays]; st.inner_visits = c[mcpt::kStatInnerVisits]; st.leaf_visits = c[mcpt::kStatLeafVisits];
+    st.leaf_refs = c[mcpt::kStatLeafRefs]; st.tri_tests = c[mcpt::kStatTriTests]; st.stack_spills = c[mcpt::kStatStackSpills];
+    st.paths = c[mcpt::kStatPaths]; st.shades = c[mcpt::kStatShades];   // (the hit queries leave them 0)
 }
 
 // What a render of p allocates and creates on the scene's (current) device,
@@ -582,7 +586,7 @@ int mcpt_plan_query(mcpt_scene* s, const mcpt_render_params* p, mcpt_plan_info* 
         r.tail_units = wf ? 0 : static_cast<int32_t>(tail_units_for(*s, pl));
         r.work_paths = pl.work;
         // what prepare_render would hold: partial sums, the small block, the spill areas, queues or tail
-        uint64_t ws = uint64_t(pl.kp.nchunks) * pl.kp.npix_local * 16 + 256 + spill_bytes(*s, pl.sets());
+        uint64_t ws = uint64_t(pl.kp.nchunks) * pl.kp.npix_local * 16 + sizeof(mcpt::RenderBlock) + spill_bytes(*s, pl.sets());
         if (wf) {
             r.wf_queue_bytes = uint64_t(wf_layout(pl, pl.wf_capacity).need) * uint64_t(pl.wf_streams);
             ws += r.wf_queue_bytes;

@@ -52,8 +52,8 @@ void ensure_rays(mcpt_scene& s, bool capturing) {
         s.rq_order.p = t.release();
     }
     if (!s.rq_stats.p) {
-        TempDev t(128);
-        HIP_TRY(hipMemset(t.p, 0, 128));
+        TempDev t(sizeof(mcpt::QueryBlocks));
+        HIP_TRY(hipMemset(t.p, 0, sizeof(mcpt::QueryBlocks)));
         HIP_TRY(mcpt::prepare_rayquery(s.gpu));   // (the kernels' code object loaded now)
         s.rq_stats.p = t.release();
     }
@@ -75,19 +75,11 @@ void rays_async(mcpt_scene& s, const mcpt_trace_params& q, int64_t n, const floa
     rq.tri_order = static_cast<const uint32_t*>(s.rq_order.p);
     rq.spill = static_cast<uint4*>(s.ws.spill.p);
     rq.spill_stride = static_cast<uint32_t>(launched_lanes(s));
-    rq.stats = static_cast<unsigned long long*>(s.rq_stats.p) + (host_block ? 8 : 0);
+    rq.stats = host_block ? query_blocks(s)->host : query_blocks(s)->device;
     rq.n = static_cast<uint32_t>(n);
     rq.refill = q.refill;
     rq.best_init = q.t_max;
     HIP_TRY(mcpt::launch_rayquery(rq, d_occ != nullptr, q.lean != 0, s.cus, q.workgroups, st));
-}
-
-void stats_from_counters(const unsigned long long c[8], mcpt_render_stats& st) {
-    std::memset(&st, 0, sizeof st);
-    st.devices = 1;
-    st.rays = c[0]; st.inner_visits = c[2]; st.leaf_visits = c[3]; st.leaf_refs = c[4];
-    st.tri_tests = c[5]; st.stack_spills = c[7];
-    st.paths = c[1]; st.shades = c[6];   // (radiance queries; the hit queries leave them 0)
 }
 
 // ---- device radiance queries (render.hip radiance_kernel) -----------------------
@@ -172,8 +164,8 @@ void ensure_radiance(mcpt_scene& s, mcpt::KernelParams& k, uint64_t tail, bool h
                                         "mcpt_scene_reserve_radiance before capturing a graph"};
     ensure_rays(s, capturing);
     if (!s.rad_small.p) {
-        TempDev t(64);
-        HIP_TRY(hipMemset(t.p, 0, 64));
+        TempDev t(mcpt::kUnitCounterBytes);
+        HIP_TRY(hipMemset(t.p, 0, mcpt::kUnitCounterBytes));
         HIP_TRY(mcpt::prepare_radiance(s.gpu));   // (the kernels' code object loaded now)
         s.rad_small.p = t.release();
     }
@@ -182,7 +174,7 @@ void ensure_radiance(mcpt_scene& s, mcpt::KernelParams& k, uint64_t tail, bool h
     k.partial = static_cast<float4*>(s.rad_partial.p);
     k.tail_buf = tail ? static_cast<float4*>(s.rad_tail.p) : nullptr;
     k.counter = static_cast<uint32_t*>(s.rad_small.p);
-    k.stats = static_cast<unsigned long long*>(s.rq_stats.p) + (host_block ? 8 : 0);
+    k.stats = host_block ? query_blocks(s)->host : query_blocks(s)->device;
     k.spill = static_cast<uint4*>(s.ws.spill.p);
 }
 
@@ -197,8 +189,8 @@ void radiance_async(mcpt_scene& s, const Radiance& R, int64_t n, const float* d_
 
 // the synchronous host entries' counter block (behind the device entries'), cleared
 unsigned long long* clear_host_block(mcpt_scene& s) {
-    unsigned long long* blk = static_cast<unsigned long long*>(s.rq_stats.p) + 8;
-    HIP_TRY(hipMemset(blk, 0, 64));
+    unsigned long long* blk = query_blocks(s)->host;
+    HIP_TRY(hipMemset(blk, 0, sizeof(mcpt::QueryBlocks::host)));
     return blk;
 }
 
@@ -310,7 +302,7 @@ int mcpt_occluded(mcpt_scene* s, const mcpt_trace_params* p, int64_t n, const fl
             rays_async(*s, q, n, d_o, d_d, t_max ? d_t : nullptr, nullptr, nullptr, d_occ, true, nullptr);
             HIP_TRY(hipStreamSynchronize(nullptr));
             HIP_TRY(hipMemcpy(occluded, d_occ, N, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(c, blk, 64, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(c, blk, sizeof c, hipMemcpyDeviceToHost));
         }
         if (stats) stats_from_counters(c, *stats);
         return MCPT_OK;
@@ -326,8 +318,8 @@ int mcpt_trace_stats_read(mcpt_scene* s, mcpt_render_stats* out) {
             set_device(*s);
             // the queries may run on any stream: wait for the device, then read and clear
             HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(hipMemcpy(c, s->rq_stats.p, 64, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemset(s->rq_stats.p, 0, 64));
+            HIP_TRY(hipMemcpy(c, query_blocks(*s)->device, sizeof c, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemset(query_blocks(*s)->device, 0, sizeof c));
         }
         if (out) stats_from_counters(c, *out);
         return MCPT_OK;
@@ -390,7 +382,7 @@ int mcpt_radiance(mcpt_scene* s, const mcpt_radiance_params* p, int64_t n, const
             radiance_async(*s, R, n, d_o, d_d, stream ? d_s : nullptr, d_out, true, nullptr);
             HIP_TRY(hipStreamSynchronize(nullptr));
             HIP_TRY(hipMemcpy(rgba.data(), d_out, N * 16, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(c, blk, 64, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(c, blk, sizeof c, hipMemcpyDeviceToHost));
             rgba_to_rgb(rgba.data(), N, radiance);
         }
         if (stats) stats_from_counters(c, *stats);

@@ -330,11 +330,11 @@ __device__ __forceinline__ void path_body(const KernelParams kp, const RayInputs
 
 #ifdef MCPT_PHASE_TIMING
     if (lane == 0) {
-        atomicAdd(kp.stats + 8, tm_units);
-        atomicAdd(kp.stats + 9, tm_trav);
-        atomicAdd(kp.stats + 10, tm_shade);
-        atomicAdd(kp.stats + 11, tm_iters);
-        atomicAdd(kp.stats + 12, tm_scatter);
+        atomicAdd(kp.stats + kStatPhaseUnits, tm_units);
+        atomicAdd(kp.stats + kStatPhaseTrav, tm_trav);
+        atomicAdd(kp.stats + kStatPhaseShade, tm_shade);
+        atomicAdd(kp.stats + kStatPhaseIters, tm_iters);
+        atomicAdd(kp.stats + kStatPhaseScatter, tm_scatter);
     }
     {
         unsigned long long* g = reinterpret_cast<unsigned long long*>(&g_lane_use);

@@ -117,10 +117,9 @@ void render_async(mcpt_scene& s, const mcpt_render_params* p, float* d_fb, hipSt
     pl.kp.unit_counters = d_unit_counters;
     if (fitted) *fitted = pl;
     // (a render without primary lists reports none)
-    HIP_TRY(hipMemsetAsync(tile_classes(s), 0, 16, st));
+    HIP_TRY(hipMemsetAsync(tile_classes(s), 0, sizeof(mcpt::RenderBlock::tile_classes), st));
     const Timing t = acquire_timing(s, pl.capturing);
     if (pl.pipeline == MCPT_PIPELINE_WAVEFRONT) {
-        s.sphere_clipped = s.sphere_clipped || pl.route.clip.mask != 0;
         HIP_TRY(mcpt::launch_wavefront(pl.kp, pl.route, R.wf, wf_streams_on(s, pl.sets(), st), t.e[0], t.e[1], t.e[2],
                                        reinterpret_cast<float4*>(d_fb), &s.last_variant));
     } else {
@@ -135,8 +134,6 @@ void render_async(mcpt_scene& s, const mcpt_render_params* p, float* d_fb, hipSt
 
 void read_stats(mcpt_scene& s, mcpt_render_stats* out) {
     set_device(s);
-    mcpt_render_stats r;
-    std::memset(&r, 0, sizeof r);
     double kms = 0, rms = 0;
     for (auto& t : s.pending) {
         HIP_TRY(hipEventSynchronize(t.e[2]));
@@ -148,30 +145,18 @@ void read_stats(mcpt_scene& s, mcpt_render_stats* out) {
         s.free_timing.push_back(t);
     }
     s.pending.clear();
-    s.direct_rays = 0;
-    s.extend_rays = 0;
-    s.clipped_rays = 0;
-    s.primary_shaded = 0;
-    s.sphere_skips = 0;
+    unsigned long long st[mcpt::kStatSlots] = {};
     if (s.ws.small.p) {
-        unsigned long long st[mcpt::kStatSlots];
-        char* const block = static_cast<char*>(s.ws.small.p) + 64;
-        HIP_TRY(hipMemcpy(st, block, sizeof st, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemset(block, 0, sizeof st));
-        // the sphere skips, behind the tile classes.  Once a render of the scene has issued or captured
-        // wf_sphere_clip every record reads and clears them, as it does its neighbours: a captured render
-        // sets the flag once and its graph's replays keep counting.  A scene that never launches the
-        // kernel reads and clears its record exactly as before
-        if (s.sphere_clipped) {
-            unsigned long long skips = 0;
-            HIP_TRY(hipMemcpy(&skips, block + 8 * mcpt::kStatSphereSkips, 8, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemset(block + 8 * mcpt::kStatSphereSkips, 0, 8));
-            s.sphere_skips = skips;
-        }
+        // the whole record in one copy and one clear (the tile classes behind it are a render's to clear)
+        unsigned long long* const d_stats = render_block(s)->stats;
+        HIP_TRY(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemset(d_stats, 0, sizeof st));
         HIP_TRY(hipStreamSynchronize(nullptr));   // (as in prepare_workspace: before a render on a non-blocking stream)
-        if (st[8] | st[9] | st[10] | st[11])   // diagnostic builds (-DMCPT_PHASE_TIMING) only
+        if (st[mcpt::kStatPhaseUnits] | st[mcpt::kStatPhaseTrav] | st[mcpt::kStatPhaseShade] | st[mcpt::kStatPhaseIters])
+            // diagnostic builds (-DMCPT_PHASE_TIMING) only
             std::fprintf(stderr, "mcpt phase cycles (sum over waves): units %llu trav %llu shade %llu burst_iters %llu "
-                         "scatter %llu\n", st[8], st[9], st[10], st[11], st[12]);
+                         "scatter %llu\n", st[mcpt::kStatPhaseUnits], st[mcpt::kStatPhaseTrav], st[mcpt::kStatPhaseShade],
+                         st[mcpt::kStatPhaseIters], st[mcpt::kStatPhaseScatter]);
 #ifdef MCPT_PHASE_TIMING
         {
             unsigned long long lu[6], lw[6];
@@ -183,15 +168,12 @@ void read_stats(mcpt_scene& s, mcpt_render_stats* out) {
                          lu[2], lu[4] ? double(lu[5]) / (64.0 * lu[4]) : 0.0, lu[4]);
         }
 #endif
-        r.rays = st[0]; r.paths = st[1]; r.inner_visits = st[2]; r.leaf_visits = st[3];
-        r.leaf_refs = st[4]; r.tri_tests = st[5]; r.shades = st[6]; r.stack_spills = st[7];
-        s.direct_rays = st[mcpt::kStatDirect];
-        s.extend_rays = st[mcpt::kStatExtend];
-        s.clipped_rays = st[mcpt::kStatClipped];
-        s.primary_shaded = st[mcpt::kStatPrimaryShaded];
     }
+    mcpt_render_stats r;
+    stats_from_counters(st, r);
+    s.routes = RouteCounts{st[mcpt::kStatDirect], st[mcpt::kStatExtend], st[mcpt::kStatClipped], st[mcpt::kStatPrimaryShaded],
+                           st[mcpt::kStatSphereSkips]};
     r.renders = s.renders;
-    r.devices = 1;
     s.renders = 0;
     r.kernel_ms = kms;
     r.reduce_ms = rms;
@@ -313,11 +295,7 @@ void read_stats_all(mcpt_scene& s, mcpt_render_stats* out) {
         r.rays += q.rays; r.paths += q.paths; r.inner_visits += q.inner_visits; r.leaf_visits += q.leaf_visits;
         r.leaf_refs += q.leaf_refs; r.tri_tests += q.tri_tests; r.shades += q.shades;
         r.stack_spills += q.stack_spills;
-        s.direct_rays += R->direct_rays;
-        s.extend_rays += R->extend_rays;
-        s.clipped_rays += R->clipped_rays;
-        s.primary_shaded += R->primary_shaded;
-        s.sphere_skips += R->sphere_skips;
+        s.routes += R->routes;
         r.kernel_ms = std::max(r.kernel_ms, q.kernel_ms);
         r.reduce_ms = std::max(r.reduce_ms, q.reduce_ms);
     }
@@ -492,9 +470,8 @@ void adaptive_async(mcpt_scene& s, const mcpt_render_params* p, const Adaptive& 
             prepare_wavefront_list(s, R.pl, pass0, n, &pj, R.wf);
             k.pixel_list = aw.list;
             // (a listed pass uses no primary lists: the scene reports no tile classes after it)
-            HIP_TRY(hipMemsetAsync(tile_classes(s), 0, 16, st));
+            HIP_TRY(hipMemsetAsync(tile_classes(s), 0, sizeof(mcpt::RenderBlock::tile_classes), st));
             t = acquire_timing(s, false);
-            s.sphere_clipped = s.sphere_clipped || R.pl.route.clip.mask != 0;
             HIP_TRY(mcpt::launch_wavefront(k, R.pl.route, R.wf, wf_streams_on(s, R.pl.sets(), st), t.e[0], t.e[1],
                                            nullptr, nullptr, &s.last_variant));
         } else {

@@ -25,6 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "stat_blocks.hpp"
+
 namespace mcpt {
 
 constexpr int kLdsBlock = 1024;          // in-LDS variant: one 16-wave workgroup per CU
@@ -124,9 +126,6 @@ static_assert(kDirectK >= 1 && kDirectK <= 15, "a box's count is carried in 4 bi
 // and one 16-B unit more (the leaf branch reads its refs in pairs)
 constexpr uint32_t kDirectTableWords = kMaxMissBoxes * kDirectK;
 constexpr size_t kDirectLdsBytes = (size_t(kDirectTableWords) * 4 + 16 + 15) & ~size_t(15);
-// the render's direct rays, counted by the shades: a slot of KernelParams::stats
-// behind the eight counters (and the diagnostic builds' five)
-constexpr int kStatDirect = 13;
 // Direct resolve (where the direct lists are active): the shade that makes a
 // direct ray also finds its hit -- begin_ray's root clip and test_tri_pair over
 // the box's list, the extend's own operations -- and writes ray and hit id to
@@ -150,9 +149,6 @@ constexpr int kStatDirect = 13;
 // L2-resident global image the C2 frame gained 1.2% instead of 5.0%, row 179)
 constexpr size_t kDirectShadeLds = size_t(kDirectTableWords) * (48 + 4);
 static_assert(kDirectTableWords * 3 <= 256, "the shade's smallest workgroup copies one record part per thread");
-// the rays the secondary extends (bounce >= 1) took, one atomic per workgroup:
-// the next slot of KernelParams::stats
-constexpr int kStatExtend = 14;
 // Clip walk (where the direct resolve is active): the rays the secondary extends
 // still walk are almost all rays through a large box (scene01: one of the two
 // 420-triangle objects, usually with one wall behind it).  The shade's box test
@@ -175,10 +171,7 @@ constexpr uint32_t kDirectShift = 24, kDepthMask = (1u << kDirectShift) - 1u;
 constexpr int kMaxDepthParam = 1000;
 static_assert(3u * kMaxDepthParam + 1u < kDepthMask, "a ray's depth must fit under its selector");
 static_assert(kMaxMissBoxes <= 8, "the clip walk's selector is one byte of box bits");
-// the rays an extend started with a selector: the next slot of KernelParams::stats
-constexpr int kStatClipped = 15;
-// the paths whose bounce 0 wf_primary_shade shaded (Primary shade, above): the slot behind it
-constexpr int kStatPrimaryShaded = 16;
+// (what the shades and extends count of all this per render: stat_blocks.hpp, kStatDirect and on)
 // Sphere clip (where the clip walk is active and a box without a list has a sphere):
 // an object's box is mostly empty at its corners (a tessellated sphere fills 52% of
 // its box), and a clipped ray that crosses only a corner still descends the tree to
@@ -197,14 +190,6 @@ constexpr double kSphereMargin = 1.0 / 1024.0;
 // clipped ray's origin lies in the scene, so |centre - o| / R stays below it and
 // the fp32 error of sphere_interval stays a small part of the margin
 constexpr double kSphereMaxReach = 256.0;
-constexpr int kStatSlots = 17;
-// the selected rays whose walk a sphere left nothing of (counted per wave by
-// wf_sphere_clip): the next free 8 bytes of the block KernelParams::stats points
-// into -- behind the kStatSlots slots and the 8 + 16 bytes of the tile classes that
-// follow them (plan.cpp tile_classes), which stay where every render's memset
-// expects them; render_host.cpp reads and clears it with the slots
-constexpr int kStatSphereSkips = kStatSlots + 3;
-static_assert(64 + 8 * (kStatSphereSkips + 1) <= 256, "the scene's small block (plan.cpp prepare_workspace)");
 
 struct GpuGeom {
     float Ka[3], Kd[3], Ks[3];
@@ -263,8 +248,8 @@ struct KernelParams {
     float eye[3], fwd[3], up[3], right[3];
     uint32_t key;                        // TEA-16 key of the 64-bit seed
     float4* partial;                     // [nchunks][npix_local]
-    uint32_t* counter;                   // work-unit counter
-    unsigned long long* stats;           // 8 counters, then the slots kStat* name (kStatSlots in all)
+    uint32_t* counter;                   // work-unit counter (RenderBlock::counter)
+    unsigned long long* stats;           // RenderBlock::stats: the slots StatSlot names (stat_blocks.hpp)
     uint4* spill;                        // traversal-stack spill [32][total_lanes]
     uint32_t total_lanes;
     uint32_t* unit_counters;             // optional [total_units][4]: rays, inner, leaf, tests

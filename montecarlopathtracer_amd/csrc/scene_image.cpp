@@ -241,47 +241,53 @@ void build_image(mcpt_scene& s, bool force_global) {
     if (nn) {
         for (int a = 0; a < 3; ++a) { gs.root_min[a] = hs.nodes[0].bmin[a]; gs.root_max[a] = hs.nodes[0].bmax[a]; }
     }
+}
+
+// The route tables of a scene (RouteTables, capi_internal.hpp) from its host scene
+// and the image's triangle order (build_image): slot -> kd id
+void route_tables(const mcpt::HostScene& hs, const std::vector<uint32_t>& tri_order, RouteTables& t) {
+    const uint32_t nt = static_cast<uint32_t>(hs.kd_tris.size());
     // terminal cull: the emitter boxes, packed like a pair record's child box
     // (lo.x lo.y | lo.z hi.x | hi.y hi.z)
     float eb[mcpt::kMaxCullBoxes][6];
-    s.n_cull_boxes = static_cast<uint32_t>(mcpt::terminal_cull_boxes(hs, eb, mcpt::kMaxCullBoxes));
-    for (uint32_t b = 0; b < s.n_cull_boxes; ++b) {
+    t.n_cull_boxes = static_cast<uint32_t>(mcpt::terminal_cull_boxes(hs, eb, mcpt::kMaxCullBoxes));
+    for (uint32_t b = 0; b < t.n_cull_boxes; ++b) {
         uint16_t hb[6];
         for (int a = 0; a < 3; ++a) {
             hb[a] = mcpt::f32_to_f16_dir(eb[b][a], -1);
             hb[3 + a] = mcpt::f32_to_f16_dir(eb[b][3 + a], +1);
         }
-        std::memcpy(s.cull_box[b], hb, 12);
+        std::memcpy(t.cull_box[b], hb, 12);
     }
-    s.n_miss_boxes = static_cast<uint32_t>(mcpt::miss_cull_boxes(hs, s.miss_box, mcpt::kMaxMissBoxes));
+    t.n_miss_boxes = static_cast<uint32_t>(mcpt::miss_cull_boxes(hs, t.miss_box, mcpt::kMaxMissBoxes));
     // direct lists: every triangle to one box that holds it; a box with 1..kDirectK
     // triangles is small and gets their record indices (the leaf refs' unit) in
     // image order.  (Kept for every scene with boxes; direct_lists_fit and the
     // render's kind decide whether a render uses them.)
-    mcpt::direct_list_assign(hs, s.miss_box, static_cast<int>(s.n_miss_boxes), s.tri_box);
-    s.direct_counts = 0;
-    std::memset(s.direct_list, 0, sizeof s.direct_list);
-    std::memset(s.box_tris, 0, sizeof s.box_tris);
-    for (uint32_t slot = 0; slot < nt && s.n_miss_boxes; ++slot) {
-        const int32_t b = s.tri_box[s.tri_order[slot]];
+    mcpt::direct_list_assign(hs, t.miss_box, static_cast<int>(t.n_miss_boxes), t.tri_box);
+    t.direct_counts = 0;
+    std::memset(t.direct_list, 0, sizeof t.direct_list);
+    std::memset(t.box_tris, 0, sizeof t.box_tris);
+    for (uint32_t slot = 0; slot < nt && t.n_miss_boxes; ++slot) {
+        const int32_t b = t.tri_box[tri_order[slot]];
         if (b < 0) throw mcpt::Error{MCPT_E_INVALID, "a triangle outside every occluder box"};
-        if (s.box_tris[b] < mcpt::kDirectK) s.direct_list[size_t(b) * mcpt::kDirectK + s.box_tris[b]] = 3u * slot;
-        s.box_tris[b]++;
+        if (t.box_tris[b] < mcpt::kDirectK) t.direct_list[size_t(b) * mcpt::kDirectK + t.box_tris[b]] = 3u * slot;
+        t.box_tris[b]++;
     }
-    for (uint32_t b = 0; b < s.n_miss_boxes; ++b) {
-        if (s.box_tris[b] >= 1 && s.box_tris[b] <= mcpt::kDirectK) s.direct_counts |= s.box_tris[b] << (4u * b);
-        else std::memset(&s.direct_list[size_t(b) * mcpt::kDirectK], 0, 4 * mcpt::kDirectK);
+    for (uint32_t b = 0; b < t.n_miss_boxes; ++b) {
+        if (t.box_tris[b] >= 1 && t.box_tris[b] <= mcpt::kDirectK) t.direct_counts |= t.box_tris[b] << (4u * b);
+        else std::memset(&t.direct_list[size_t(b) * mcpt::kDirectK], 0, 4 * mcpt::kDirectK);
     }
     // sphere clip: a sphere over the triangles of every box that has some and no list
     uint32_t unlisted = 0;
-    for (uint32_t b = 0; b < s.n_miss_boxes; ++b)
-        if (s.box_tris[b] > mcpt::kDirectK) unlisted |= 1u << b;
-    s.clip_spheres = mcpt::clip_spheres(hs, s.miss_box, static_cast<int>(s.n_miss_boxes), s.tri_box, unlisted,
-                                        mcpt::kSphereMargin, mcpt::kSphereMaxReach, s.clip_sphere);
-    s.cull_gain = 0.0f;
+    for (uint32_t b = 0; b < t.n_miss_boxes; ++b)
+        if (t.box_tris[b] > mcpt::kDirectK) unlisted |= 1u << b;
+    t.clip_spheres = mcpt::clip_spheres(hs, t.miss_box, static_cast<int>(t.n_miss_boxes), t.tri_box, unlisted,
+                                        mcpt::kSphereMargin, mcpt::kSphereMaxReach, t.clip_sphere);
+    t.cull_gain = 0.0f;
     for (const mcpt::Geometry& ge : hs.geoms)
         for (float k : {ge.Kd.x, ge.Kd.y, ge.Kd.z, ge.Ks.x, ge.Ks.y, ge.Ks.z})
-            if (std::fabs(k) > s.cull_gain) s.cull_gain = std::fabs(k);
+            if (std::fabs(k) > t.cull_gain) t.cull_gain = std::fabs(k);
 }
 
 // device copies of the scene image and the shading normals on `device`
@@ -312,6 +318,7 @@ int scene_create_impl(const mcpt_model* m, mcpt_scene** out, bool device, const 
         if (s->hs.kd_tris.empty()) return fail(MCPT_E_INVALID, "scene has no triangles");
         if (layout != MCPT_LAYOUT_AUTO && layout != MCPT_LAYOUT_GLOBAL) return fail(MCPT_E_INVALID, "unknown layout");
         build_image(*s, layout == MCPT_LAYOUT_GLOBAL);
+        route_tables(s->hs, s->tri_order, s->tables);
         if (device) {
             const size_t nt = s->hs.kd_tris.size();
             std::vector<float> nrm(nt * 12, 0.0f);
@@ -327,15 +334,7 @@ int scene_create_impl(const mcpt_model* m, mcpt_scene** out, bool device, const 
             for (size_t i = 1; i < devs.size(); ++i) {
                 auto R = std::make_unique<mcpt_scene>();
                 R->gpu = s->gpu;
-                R->n_cull_boxes = s->n_cull_boxes;
-                std::memcpy(R->cull_box, s->cull_box, sizeof s->cull_box);
-                R->cull_gain = s->cull_gain;
-                R->n_miss_boxes = s->n_miss_boxes;
-                std::memcpy(R->miss_box, s->miss_box, sizeof s->miss_box);
-                R->direct_counts = s->direct_counts;
-                std::memcpy(R->direct_list, s->direct_list, sizeof s->direct_list);
-                R->clip_spheres = s->clip_spheres;
-                std::memcpy(R->clip_sphere, s->clip_sphere, sizeof s->clip_sphere);
+                R->tables = s->tables;
                 upload(*R, devs[i], s->image, nrm);
                 HIP_TRY(hipStreamCreateWithFlags(&R->stream, hipStreamNonBlocking));
                 HIP_TRY(hipEventCreateWithFlags(&R->done, hipEventDisableTiming));
@@ -522,46 +521,47 @@ int mcpt_scene_primary_tile_classes(mcpt_scene* s, uint32_t out[4]) {
         if (!s->on_device || !s->ws.small.p) return MCPT_OK;
         set_device(*s);
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(out, tile_classes(*s), 12, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, tile_classes(*s), 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
         return MCPT_OK;
     });
 }
 
 int mcpt_scene_terminal_cull_boxes(const mcpt_scene* s) {
-    return s ? static_cast<int>(s->n_cull_boxes) : 0;
+    return s ? static_cast<int>(s->tables.n_cull_boxes) : 0;
 }
 
 int mcpt_scene_miss_cull_boxes(const mcpt_scene* s, float* boxes) {
     if (!s) return 0;
-    if (boxes) std::memcpy(boxes, s->miss_box, sizeof(float) * 6 * s->n_miss_boxes);
-    return static_cast<int>(s->n_miss_boxes);
+    if (boxes) std::memcpy(boxes, s->tables.miss_box, sizeof(float) * 6 * s->tables.n_miss_boxes);
+    return static_cast<int>(s->tables.n_miss_boxes);
 }
 
 int mcpt_scene_direct_lists(const mcpt_scene* s, int32_t* tri_box, uint32_t* box_tris, uint32_t* lists,
                             int32_t* list_kd) {
     if (!s) return 0;
+    const RouteTables& t = s->tables;
     if (list_kd)
         for (uint32_t b = 0; b < mcpt::kMaxMissBoxes; ++b)
             for (uint32_t j = 0; j < mcpt::kDirectK; ++j) {
-                const bool have = j < ((s->direct_counts >> (4u * b)) & 15u);
+                const bool have = j < ((t.direct_counts >> (4u * b)) & 15u);
                 list_kd[b * mcpt::kDirectK + j] =
-                    have ? static_cast<int32_t>(s->tri_order[s->direct_list[b * mcpt::kDirectK + j] / 3u]) : -1;
+                    have ? static_cast<int32_t>(s->tri_order[t.direct_list[b * mcpt::kDirectK + j] / 3u]) : -1;
             }
-    if (tri_box && !s->tri_box.empty()) std::memcpy(tri_box, s->tri_box.data(), 4 * s->tri_box.size());
-    if (box_tris) std::memcpy(box_tris, s->box_tris, 4 * mcpt::kMaxMissBoxes);
-    if (lists) std::memcpy(lists, s->direct_list, 4 * mcpt::kDirectTableWords);
+    if (tri_box && !t.tri_box.empty()) std::memcpy(tri_box, t.tri_box.data(), 4 * t.tri_box.size());
+    if (box_tris) std::memcpy(box_tris, t.box_tris, 4 * mcpt::kMaxMissBoxes);
+    if (lists) std::memcpy(lists, t.direct_list, 4 * mcpt::kDirectTableWords);
     return static_cast<int>(mcpt::kDirectK);
 }
 
-uint64_t mcpt_scene_direct_rays(const mcpt_scene* s) { return s ? s->direct_rays : 0; }
-uint64_t mcpt_scene_extend_rays(const mcpt_scene* s) { return s ? s->extend_rays : 0; }
-uint64_t mcpt_scene_clipped_rays(const mcpt_scene* s) { return s ? s->clipped_rays : 0; }
-uint64_t mcpt_scene_primary_shaded(const mcpt_scene* s) { return s ? s->primary_shaded : 0; }
-uint64_t mcpt_scene_sphere_skips(const mcpt_scene* s) { return s ? s->sphere_skips : 0; }
+uint64_t mcpt_scene_direct_rays(const mcpt_scene* s) { return s ? s->routes.direct_rays : 0; }
+uint64_t mcpt_scene_extend_rays(const mcpt_scene* s) { return s ? s->routes.extend_rays : 0; }
+uint64_t mcpt_scene_clipped_rays(const mcpt_scene* s) { return s ? s->routes.clipped_rays : 0; }
+uint64_t mcpt_scene_primary_shaded(const mcpt_scene* s) { return s ? s->routes.primary_shaded : 0; }
+uint64_t mcpt_scene_sphere_skips(const mcpt_scene* s) { return s ? s->routes.sphere_skips : 0; }
 uint32_t mcpt_scene_clip_spheres(const mcpt_scene* s, float* spheres) {
     if (!s) return 0;
-    if (spheres) std::memcpy(spheres, s->clip_sphere, sizeof s->clip_sphere);
-    return s->clip_spheres;
+    if (spheres) std::memcpy(spheres, s->tables.clip_sphere, sizeof s->tables.clip_sphere);
+    return s->tables.clip_spheres;
 }
 uint64_t mcpt_scene_primary_shade_lds(const mcpt_scene* s) {
     if (!s) return 0;

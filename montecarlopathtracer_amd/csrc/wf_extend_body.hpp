@@ -137,7 +137,7 @@
         mode = (depth != kNoRay && live) ? kTrav : kReady;
     };
 #ifdef MCPT_PHASE_TIMING
-    // stats[8] setup, [9] traversal bursts, [10] hand-offs, [11] burst iterations
+    // the five phase slots (stat_blocks.hpp): setup, traversal bursts, hand-offs, burst iterations, hand-off count
     unsigned long long tm_setup = 0, tm_trav = 0, tm_hand = 0, tm_iters = 0, tm_hands = 0,
                        tm_t0 = __builtin_amdgcn_s_memtime();
 #define WF_STAMP(acc) do { unsigned long long t1_ = __builtin_amdgcn_s_memtime(); acc += t1_ - tm_t0; tm_t0 = t1_; } while (0)
@@ -239,11 +239,11 @@
     }
 #ifdef MCPT_PHASE_TIMING
     if ((threadIdx.x & 63u) == 0) {
-        atomicAdd(kp.stats + 8, tm_setup);
-        atomicAdd(kp.stats + 9, tm_trav);
-        atomicAdd(kp.stats + 10, tm_hand);
-        atomicAdd(kp.stats + 11, tm_iters);
-        atomicAdd(kp.stats + 12, tm_hands);
+        atomicAdd(kp.stats + kStatPhaseUnits, tm_setup);
+        atomicAdd(kp.stats + kStatPhaseTrav, tm_trav);
+        atomicAdd(kp.stats + kStatPhaseShade, tm_hand);
+        atomicAdd(kp.stats + kStatPhaseIters, tm_iters);
+        atomicAdd(kp.stats + kStatPhaseScatter, tm_hands);
     }
     {
         unsigned long long* gl = reinterpret_cast<unsigned long long*>(&g_lane_use);

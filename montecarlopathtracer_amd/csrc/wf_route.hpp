@@ -59,8 +59,8 @@ inline bool direct_lists_fit(uint32_t image_bytes, uint32_t node_boxes) {
     return !node_boxes && lds_bytes_counted_in_lds(image_bytes, 4) + kShadeStaticLds + kDirectLdsBytes <= kMaxLds;
 }
 
-// What the route is computed from.  The scene: its GpuScene and what
-// build_image found for the culls (n_cull_boxes as far as the render may use
+// What the route is computed from.  The scene: its GpuScene and what its
+// route tables hold for the culls (n_cull_boxes as far as the render may use
 // them: plan.cpp plan_route).  The render: its parameters as make_plan read them
 struct WfFacts {
     const GpuScene* scene;
@@ -72,7 +72,7 @@ struct WfFacts {
     bool tile_records;                   // the workspace has the primary lists' tile records (wf_layout)
     int tile, max_depth;
     uint32_t group_shift;                // the plan's, for a scene in global memory
-    // sphere clip: the scene's mask and spheres (mcpt_scene::clip_spheres, ::clip_sphere; null: none)
+    // sphere clip: the scene's mask and spheres (RouteTables::clip_spheres, ::clip_sphere; null: none)
     uint32_t clip_spheres;
     const float (*clip_sphere)[4];
 };

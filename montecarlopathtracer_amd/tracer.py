@@ -347,16 +347,19 @@ class Scene:
 
     def _render_stats(self, st) -> dict:
         d = st.as_dict()
-        # secondary rays resolved from a box's list instead of a walk (lean wavefront renders)
-        d["direct_rays"] = int(lib().mcpt_scene_direct_rays(self.handle))
-        # rays the wavefront's secondary extends walked (0: megakernel, or built without the direct resolve)
-        d["extend_rays"] = int(lib().mcpt_scene_extend_rays(self.handle))
-        # of those, the rays an extend started with a box selector (0: built without the clip walk)
-        d["clipped_rays"] = int(lib().mcpt_scene_clipped_rays(self.handle))
-        # paths whose bounce 0 the kernel that resolved their primary rays also shaded (0: every other render)
-        d["primary_shaded"] = int(lib().mcpt_scene_primary_shaded(self.handle))
-        # clipped rays whose walk a box's sphere left nothing of (0: a render that does not clip to spheres)
-        d["sphere_skips"] = int(lib().mcpt_scene_sphere_skips(self.handle))
+        for name in (
+            # secondary rays resolved from a box's list instead of a walk (lean wavefront renders)
+            "direct_rays",
+            # rays the wavefront's secondary extends walked (0: megakernel, or built without the direct resolve)
+            "extend_rays",
+            # of those, the rays an extend started with a box selector (0: built without the clip walk)
+            "clipped_rays",
+            # paths whose bounce 0 the kernel that resolved their primary rays also shaded (0: every other render)
+            "primary_shaded",
+            # clipped rays whose walk a box's sphere left nothing of (0: a render that does not clip to spheres)
+            "sphere_skips",
+        ):
+            d[name] = int(getattr(lib(), "mcpt_scene_" + name)(self.handle))
         return d
 
     def primary_tile_classes(self):
