@@ -694,7 +694,8 @@ int mcpt_scene_reserve_rays(mcpt_scene*);
  * for n >= 2^31 / 3 or n x chunks >= 2^31; MCPT_E_INVALID for a host-only scene
  * and for an output that overlaps an input.  n = 0 is a no-op.  A multi-device
  * scene runs the query on devices[0].  Not offered:
- * QuinEngine mode, a wavefront form, batches sharded over devices.
+ * QuinEngine mode, batches sharded over devices.  The wavefront form:
+ * mcpt_radiance_ex[_device], below.
  * Workspace, the scene's: the renders' stack spill area (run the queries on the
  * stream of the scene's renders, or synchronize), 16 B per (ray, chunk) of
  * partial sums, the tail samples' buffer and a work-unit counter.  After
@@ -726,6 +727,64 @@ int mcpt_radiance(mcpt_scene*, const mcpt_radiance_params* p, int64_t n, const f
                   const uint32_t* stream, float* radiance, mcpt_render_stats* stats);
 /* allocate what a radiance query of n rays with these params needs (above) */
 int mcpt_scene_reserve_radiance(mcpt_scene*, const mcpt_radiance_params* p, int64_t n);
+
+/* ---- radiance queries on either pipeline ---------------------------------------- */
+/* The radiance queries with the pipeline as a parameter.  pipeline =
+ * MCPT_PIPELINE_MEGAKERNEL (the default; p = NULL means the defaults) is exactly
+ * mcpt_radiance[_device]: same code path, same bits, same counters.
+ * MCPT_PIPELINE_WAVEFRONT runs the rays as a wavefront render of n "pixels": a
+ * generate kernel fills the first ray queue from the buffers, bounce 0's extend
+ * reads its origins from that queue, and every later kernel, route and cull is the
+ * wavefront renders' (miss cull, direct lists and resolve, clip walk, sphere clip,
+ * terminal cull, the co-resident shade).  Semantics, preconditions, accumulation,
+ * the running mean, stream ids and the output layout are mcpt_radiance[_device]'s,
+ * and the result is bit for bit what the megakernel form writes for the same rays
+ * and `base`; the pipeline, batch split, streams, refill, group shift, sort and
+ * layout never change a result.
+ * Checks: mcpt_radiance's up to the work-unit limit, in its order; then the
+ * wavefront fields with the ranges and messages of mcpt_render_params
+ * (MCPT_E_INVALID, the message names the field); then the host-only scene and the
+ * overlap check.  All before anything is launched or allocated.
+ * Counters: the device entry adds its eight counters to the block
+ * mcpt_trace_stats_read reports, the host entry reports its own call and leaves
+ * that block alone.  On the wavefront a lean query counts rays, paths and shades
+ * and its traversal counters read 0 (the wavefront renders' rule, not the lean
+ * megakernel's); a counting query reports the megakernel query's counters, and the
+ * host entry's stats->variant is 4 (scene in LDS) or 5 (in global memory).  The
+ * render stats, mcpt_scene_direct_rays and its siblings and
+ * mcpt_scene_primary_tile_classes are never touched by a query.
+ * Workspace, wavefront: the scene's wavefront workspace (queues, partial sums,
+ * spill areas, side streams), shared with the renders and planned as for a frame of
+ * n pixels x spp -- run the queries on the stream of the scene's renders, or
+ * synchronize -- plus the queries' counter blocks.  After
+ * mcpt_scene_reserve_radiance_ex(p, n) a query that needs no more allocates
+ * nothing; on a capturing stream the wavefront form follows a wavefront
+ * mcpt_render_device: growth there is MCPT_E_NOMEM before any launch.  A
+ * multi-device scene answers on devices[0].
+ * A wavefront reservation bounds the default batches of later queries as
+ * mcpt_scene_reserve's bounds a render's: reserve for the largest query.
+ * Measured at 16 spp, lean ("The wavefront form"): the
+ * wavefront form takes 0.52x the megakernel form's time on scene01 at 2^22 rays and
+ * 0.73x at 2^20, 0.62x on the 70k mesh at both.  It does not win at 2^16 rays
+ * (2^20 paths): there a query is a few dozen launches of ~1 ms in all, and the
+ * wavefront form takes 2.0x (scene01) and 2.7x (70k mesh) the megakernel's time --
+ * small batches belong on the megakernel. */
+typedef struct {
+    mcpt_radiance_params base;   /* as mcpt_radiance*; workgroups and ready_thresh are checked, and ignored on the wavefront */
+    int32_t  pipeline;           /* MCPT_PIPELINE_*; megakernel (0): exactly mcpt_radiance[_device] */
+    uint32_t wf_batch;           /* as mcpt_render_params: max paths per batch and stream, 0 = automatic */
+    int32_t  wf_streams, wf_refill, wf_group_shift, wf_sort;   /* as mcpt_render_params, 0 = its defaults */
+    uint64_t wf_mem_limit;       /* as mcpt_render_params */
+} mcpt_radiance_ex_params;
+void mcpt_radiance_ex_params_default(mcpt_radiance_ex_params*);   /* base: mcpt_radiance_params_default; the rest 0 */
+int mcpt_radiance_ex_device(mcpt_scene*, const mcpt_radiance_ex_params*, int64_t n, const float* d_o, const float* d_d,
+                            const uint32_t* d_stream, float* d_radiance, void* hip_stream);
+int mcpt_radiance_ex(mcpt_scene*, const mcpt_radiance_ex_params*, int64_t n, const float* o, const float* d,
+                     const uint32_t* stream, float* radiance, mcpt_render_stats* stats);
+int mcpt_scene_reserve_radiance_ex(mcpt_scene*, const mcpt_radiance_ex_params*, int64_t n);
+/* {direct, extend, clipped, sphere_skips} rays of the wavefront radiance queries in the record
+   mcpt_trace_stats_read last read (zeros for megakernel queries and the hit queries) */
+int mcpt_scene_query_route_rays(const mcpt_scene*, uint64_t out[4]);
 
 #ifdef __cplusplus
 }

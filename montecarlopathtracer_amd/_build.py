@@ -18,7 +18,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, os.environ.get("MCPT_LIB_NAME", "libmcpt.so"))
 SOURCES = ["host_model.cpp", "kd_cache.cpp", "capi.cpp", "scene_image.cpp", "plan.cpp", "render_host.cpp", "queries.cpp",
            "render.hip", "wavefront.hip", "wavefront_primary.hip", "wavefront_primary_shade.hip",
-           "wavefront_sphere.hip", "aov.hip", "denoise.hip", "variance.hip", "denoise_var.hip", "adaptive.hip", "rayquery.hip"]
+           "wavefront_sphere.hip", "wavefront_rays.hip", "aov.hip", "denoise.hip", "variance.hip", "denoise_var.hip", "adaptive.hip", "rayquery.hip"]
 # per-source code generation (wavefront_primary.hip: the bounce-0 packet extend's
 # wave-uniform control flow as scalar branches; render.hip: GVN hoisting,
 # megakernel +1.4%, no effect on the wavefront kernels, and the global-memory
@@ -34,6 +34,8 @@ SOURCE_FLAGS = {"wavefront_primary.hip": ["-mllvm", "-structurizecfg-skip-unifor
                 "wavefront.hip": _WF_FLAGS,
                 # the lean LDS extend's body again: its flags
                 "wavefront_sphere.hip": _WF_FLAGS,
+                # ... and the extends' body with queue origins (the wavefront radiance queries)
+                "wavefront_rays.hip": _WF_FLAGS,
                 # the ray queries' kernel is the extend's loop: it starts from the extend's flags
                 "rayquery.hip": _WF_FLAGS,
                 "render.hip": ["-mllvm", "-enable-gvn-hoist", "-mllvm", "-unroll-threshold=2000"]}

@@ -118,6 +118,12 @@ class RadianceParamsC(C.Structure):
                 ("ready_thresh", C.c_int32)]
 
 
+class RadianceExParamsC(C.Structure):
+    _fields_ = [("base", RadianceParamsC), ("pipeline", C.c_int32), ("wf_batch", C.c_uint32),
+                ("wf_streams", C.c_int32), ("wf_refill", C.c_int32), ("wf_group_shift", C.c_int32),
+                ("wf_sort", C.c_int32), ("wf_mem_limit", C.c_uint64)]
+
+
 TRACE_CLOSEST = 0
 TRACE_ANY = 1
 OBJ_CVMCTRACER = 0
@@ -226,6 +232,13 @@ _SIGS = {
                                 C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_float),
                                 C.POINTER(RenderStats)]),
     "mcpt_scene_reserve_radiance": (C.c_int, [_vp, C.POINTER(RadianceParamsC), C.c_int64]),
+    "mcpt_radiance_ex_params_default": (None, [C.POINTER(RadianceExParamsC)]),
+    "mcpt_radiance_ex_device": (C.c_int, [_vp, C.POINTER(RadianceExParamsC), C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "mcpt_radiance_ex": (C.c_int, [_vp, C.POINTER(RadianceExParamsC), C.c_int64, C.POINTER(C.c_float),
+                                   C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                                   C.POINTER(RenderStats)]),
+    "mcpt_scene_reserve_radiance_ex": (C.c_int, [_vp, C.POINTER(RadianceExParamsC), C.c_int64]),
+    "mcpt_scene_query_route_rays": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

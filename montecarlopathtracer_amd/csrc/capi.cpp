@@ -243,6 +243,12 @@ void mcpt_radiance_params_default(mcpt_radiance_params* p) {
     p->seed = 0x4D435054ull;                          // mcpt_render_params_default's
 }
 
+void mcpt_radiance_ex_params_default(mcpt_radiance_ex_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof *p);                     // the megakernel; every wavefront field automatic
+    mcpt_radiance_params_default(&p->base);
+}
+
 int mcpt_denoise_device(const mcpt_denoise_params* p, const float* d_color_rgba, const float* d_albedo_cov,
                         const float* d_normal_depth, float* d_out_rgba, float* d_scratch_rgba, void* hip_stream) {
     return guarded([&]() -> int {

@@ -205,12 +205,18 @@ struct mcpt_scene {
     // device radiance queries (mcpt_radiance_device): partial sums [chunk][ray],
     // the tail samples and the work-unit counter (kUnitCounterBytes; counters: rq_stats)
     mcpt::host::DevBuf rad_partial, rad_tail, rad_small;
+    // their wavefront form (mcpt_radiance_ex_device): one mcpt::WfQueryBlock, the counter
+    // block of the query under way and the device entries' route-ray record; and that
+    // record as mcpt_trace_stats_read last read it (mcpt_scene_query_route_rays)
+    mcpt::host::DevBuf rad_wf_stats;
+    uint64_t query_routes[mcpt::kQueryRoutes] = {};
 
     // every device buffer of the scene: what the destructor frees (a new buffer
     // is declared above and listed here)
     std::vector<mcpt::host::DevBuf*> buffers() {
         return {&d_image, &d_normals, &ws.partial, &ws.small, &ws.spill, &ws.fb, &ws.wf, &ws.tail, &gather, &gather_send,
-                &ad_list, &ad_flags, &ad_blocks, &rq_order, &rq_stats, &rad_partial, &rad_tail, &rad_small};
+                &ad_list, &ad_flags, &ad_blocks, &rq_order, &rq_stats, &rad_partial, &rad_tail, &rad_small,
+                &rad_wf_stats};
     }
     ~mcpt_scene();   // scene_image.cpp
 };
@@ -220,6 +226,7 @@ namespace mcpt::host {
 // the scene's counter blocks on its device (null before the first render / query): addresses only
 inline mcpt::RenderBlock* render_block(const mcpt_scene& s) { return static_cast<mcpt::RenderBlock*>(s.ws.small.p); }
 inline mcpt::QueryBlocks* query_blocks(const mcpt_scene& s) { return static_cast<mcpt::QueryBlocks*>(s.rq_stats.p); }
+inline mcpt::WfQueryBlock* wf_query_block(const mcpt_scene& s) { return static_cast<mcpt::WfQueryBlock*>(s.rad_wf_stats.p); }
 // the last render's tile classes (primary lists)
 inline uint32_t* tile_classes(const mcpt_scene& s) { return render_block(s)->tile_classes; }
 
@@ -272,10 +279,13 @@ void grow_spill(mcpt_scene& s, int sets, bool capturing);
 uint64_t tail_split(uint64_t lanes, int64_t per_lane, int64_t exact, uint32_t total_units, uint32_t chunk);
 uint64_t tail_units_for(const mcpt_scene& s, const Plan& pl);
 Plan make_plan(const mcpt_scene& s, const mcpt_render_params* p);
+void plan_wavefront(const mcpt_scene& s, Plan& pl, const mcpt_render_params* p, bool listed);
 uint32_t wf_batch_capacity(const mcpt_scene& s, const mcpt_render_params* p, uint64_t work, uint32_t chunk, int nstr);
 void prepare_wavefront_list(mcpt_scene& s, Plan& pl, const Plan& pass0, uint32_t n, const mcpt_render_params* p,
                             mcpt::WfParams* out);
 void fit_wavefront(const mcpt_scene& s, Plan& pl);
+void prepare_wavefront_rays(mcpt_scene& s, const mcpt::KernelParams& k, const mcpt_render_params* p, bool capturing,
+                            Prepared& out);
 void prepare_workspace(mcpt_scene& s, Plan& pl, bool tail_split = false, int spill_sets = 1);
 // the eight Counters of a block as the record's fields of the same names (devices 1, all else 0)
 void stats_from_counters(const unsigned long long c[mcpt::kStatCounters], mcpt_render_stats& st);
@@ -285,5 +295,6 @@ mcpt_render_params shard_params(const mcpt_render_params& p, int n, int r);
 
 // ---- render_host.cpp ----------------------------------------------------------
 void destroy_comms(mcpt_scene& s);
+mcpt::WfStreams wf_streams_on(const mcpt_scene& s, int n, hipStream_t st);
 
 }  // namespace mcpt::host

@@ -316,6 +316,20 @@ Plan make_plan(const mcpt_scene& s, const mcpt_render_params* p) {
     if (p->pipeline != MCPT_PIPELINE_MEGAKERNEL && p->pipeline != MCPT_PIPELINE_WAVEFRONT)
         throw mcpt::Error{MCPT_E_INVALID, "unknown pipeline"};
     pl.pipeline = p->pipeline;
+    // tail split: 4 units per lane (a whole frame +0.3% over 6; rank 0 of 8
+    // shards at 97.0% of ideal, 6: 96.5%, 8: 95.7%, 10: 94.8%)
+    pl.tail_per_lane = p->tail_units_per_lane == 0 ? kTailPerLane : p->tail_units_per_lane;
+    pl.tail_exact = p->tail_units;
+    plan_wavefront(s, pl, p, false);
+    return pl;
+}
+
+// The wavefront fields of the plan of a frame whose kp make_plan (or a radiance query,
+// queries.cpp) has filled: knobs, route, streams and the batch before it is fitted to
+// memory.  listed: a frame with an explicit queue 0 (WfFacts::listed)
+void plan_wavefront(const mcpt_scene& s, Plan& pl, const mcpt_render_params* p, bool listed) {
+    const uint64_t npix = pl.kp.npix_local;
+    const uint32_t chunk = pl.kp.chunk;
     pl.wf_sort = p->wf_sort ? 1 : 0;
     // idle lanes before an extend wave refills: 16 for scenes in LDS (C2 sweep
     // 8 / 16 / 24: 10.08 / 10.28 / 10.19 G rays/s), 8 for scenes in global
@@ -326,21 +340,14 @@ Plan make_plan(const mcpt_scene& s, const mcpt_render_params* p) {
     // 2^8 9.36, 2^9 8.39, 2^10 7.92 / 7.86, 2^11 9.70 / 9.73, 2^12 9.96 / 9.96 /
     // 9.98, 2^13 9.74, 2^14 9.83 / 9.87 / 9.85 (round 1, 256 spp: 2^14 best)
     const uint32_t group_shift = static_cast<uint32_t>(p->wf_group_shift > 0 ? p->wf_group_shift : 12);
-    // tail split: 4 units per lane (a whole frame +0.3% over 6; rank 0 of 8
-    // shards at 97.0% of ideal, 6: 96.5%, 8: 95.7%, 10: 94.8%)
-    pl.tail_per_lane = p->tail_units_per_lane == 0 ? kTailPerLane : p->tail_units_per_lane;
-    pl.tail_exact = p->tail_units;
     pl.wf_mem_limit = p->wf_mem_limit;
-    {
-        const uint64_t work = std::max<uint64_t>(npix, 1) * std::max<uint64_t>(p->spp, chunk);
-        pl.work = npix * p->spp;
-        pl.wf_batch_explicit = p->wf_batch != 0;
-        pl.route = plan_route(s, pl, group_shift, false);
-        const int nstr = wavefront_streams(pl.route, work, p);
-        pl.wf_streams = nstr;
-        pl.wf_capacity = wf_batch_capacity(s, p, work, chunk, nstr);
-    }
-    return pl;
+    const uint64_t work = std::max<uint64_t>(npix, 1) * std::max<uint64_t>(p->spp, chunk);
+    pl.work = npix * p->spp;
+    pl.wf_batch_explicit = p->wf_batch != 0;
+    pl.route = plan_route(s, pl, group_shift, listed);
+    const int nstr = wavefront_streams(pl.route, work, p);
+    pl.wf_streams = nstr;
+    pl.wf_capacity = wf_batch_capacity(s, p, work, chunk, nstr);
 }
 
 // Paths per wavefront batch of a frame of `work` paths (pixels x samples) on nstr
@@ -383,6 +390,29 @@ void prepare_wavefront_list(mcpt_scene& s, Plan& pl, const Plan& pass0, uint32_t
     pl.wf_capacity = std::min(wf_batch_capacity(s, p, pl.work, k.chunk, pl.wf_streams), pass0.wf_capacity);
     prepare_workspace(s, pl, false, pl.sets());
     prepare_wavefront(s, pl, pl.sets(), out);
+    ensure_wf_streams(s, pl.sets());
+}
+
+// A ray frame (a wavefront radiance query, render_launch.hpp "Ray frames") of the n =
+// k.npix_local rays of k, which queries.cpp filled as for the megakernel query; p carries
+// the query's wavefront fields and its spp.  Planned as a frame of n pixels x spp with an
+// explicit queue 0, fitted to memory as a render is, in the scene's wavefront workspace
+// -- the renders' partial sums, spill areas, queues, streams and events; the render's
+// counter block is allocated with them and not written (the caller points kp.stats at the
+// query's own).  What a query and mcpt_scene_reserve_radiance_ex both run.
+void prepare_wavefront_rays(mcpt_scene& s, const mcpt::KernelParams& k, const mcpt_render_params* p, bool capturing,
+                            Prepared& out) {
+    Plan& pl = out.pl;
+    pl.kp = k;
+    pl.out_pixels = k.npix_local;
+    pl.capturing = capturing;
+    pl.pipeline = MCPT_PIPELINE_WAVEFRONT;
+    pl.tail_per_lane = -1;
+    pl.tail_exact = 0;
+    plan_wavefront(s, pl, p, true);
+    fit_wavefront(s, pl);
+    prepare_workspace(s, pl, false, pl.sets());
+    prepare_wavefront(s, pl, pl.sets(), out.wf);
     ensure_wf_streams(s, pl.sets());
 }
 

@@ -1,6 +1,7 @@
 // queries.cpp -- the ray entries of the C ABI (include/mcpt.h): closest-hit and
 // any-hit queries over ray buffers (rayquery.hip), path-traced radiance over
-// ray buffers (render.hip radiance_kernel), and mcpt_intersect on the older
+// ray buffers (render.hip radiance_kernel; on the wavefront pipeline as a ray
+// frame, wavefront_rays.hip), and mcpt_intersect on the older
 // closest-hit kernel the ray-query tests compare against.
 #include <algorithm>
 #include <cfloat>
@@ -88,9 +89,9 @@ struct Radiance {
     uint32_t chunk;
     uint64_t nchunks;
 };
-// The checks of a radiance query that need no device, in the header's order; p
-// resolved (NULL = the defaults)
-Radiance radiance_resolve(const mcpt_scene* s, const mcpt_radiance_params* p, int64_t n, bool ptrs) {
+// The checks of a radiance query that need no device, in the header's order, up to
+// the work-unit limit; p resolved (NULL = the defaults)
+Radiance radiance_checks(const mcpt_scene* s, const mcpt_radiance_params* p, int64_t n, bool ptrs) {
     if (!s) throw mcpt::Error{MCPT_E_INVALID, "NULL scene"};
     if (n < 0) throw mcpt::Error{MCPT_E_INVALID, "n must be >= 0"};
     if (n && !ptrs) throw mcpt::Error{MCPT_E_INVALID, "NULL ray or result buffer"};
@@ -114,8 +115,38 @@ Radiance radiance_resolve(const mcpt_scene* s, const mcpt_radiance_params* p, in
     if (n >= (int64_t(1) << 31) / 3) throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many rays for one call"};
     if (uint64_t(n) * R.nchunks >= (uint64_t(1) << 31))
         throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many work units (rays x chunks) for one call"};
+    return R;
+}
+// ... and the host-only scene behind them
+Radiance radiance_resolve(const mcpt_scene* s, const mcpt_radiance_params* p, int64_t n, bool ptrs) {
+    const Radiance R = radiance_checks(s, p, n, ptrs);
     if (!s->on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
     return R;
+}
+// A query with its pipeline (mcpt_radiance_ex*): mcpt_radiance's checks, then the
+// wavefront fields with mcpt_render_params' ranges and messages (plan.cpp make_plan),
+// then the host-only scene; x resolved (NULL = the defaults, the megakernel)
+struct RadianceEx {
+    Radiance R;
+    mcpt_radiance_ex_params x;
+    bool wavefront() const { return x.pipeline == MCPT_PIPELINE_WAVEFRONT; }
+};
+RadianceEx radiance_ex_resolve(const mcpt_scene* s, const mcpt_radiance_ex_params* p, int64_t n, bool ptrs) {
+    RadianceEx E;
+    mcpt_radiance_ex_params_default(&E.x);
+    if (p) E.x = *p;
+    E.R = radiance_checks(s, &E.x.base, n, ptrs);
+    const mcpt_radiance_ex_params& x = E.x;
+    if (x.pipeline != MCPT_PIPELINE_MEGAKERNEL && x.pipeline != MCPT_PIPELINE_WAVEFRONT)
+        throw mcpt::Error{MCPT_E_INVALID, "unknown pipeline"};
+    if (x.wf_streams < 0 || x.wf_streams > mcpt::kMaxWfStreams)
+        throw mcpt::Error{MCPT_E_INVALID, "wf_streams must be 0 (automatic) or 1..4"};
+    if (x.wf_refill < 0 || x.wf_refill > 64)
+        throw mcpt::Error{MCPT_E_INVALID, "wf_refill / ready_thresh must be 0 (automatic) or 1..64"};
+    if (x.wf_group_shift != 0 && (x.wf_group_shift < 6 || x.wf_group_shift > 14))
+        throw mcpt::Error{MCPT_E_INVALID, "wf_group_shift must be 0 (automatic) or 6..14"};
+    if (!s->on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
+    return E;
 }
 
 // The kernel parameters of a query: a packed frame of n rays (no pixel decode
@@ -187,11 +218,125 @@ void radiance_async(mcpt_scene& s, const Radiance& R, int64_t n, const float* d_
     HIP_TRY(mcpt::launch_radiance(k, ri, s.cus, R.q.workgroups, reinterpret_cast<float4*>(d_out), st));
 }
 
+// ---- the wavefront form (wavefront_rays.hip, render_launch.hpp "Ray frames") ------
+// What a wavefront query of n rays needs on the scene's (current) device, in place:
+// the queries' counter blocks and its own, and the ray frame planned inside the
+// scene's wavefront workspace (plan.cpp prepare_wavefront_rays).  The query and
+// mcpt_scene_reserve_radiance_ex both run it, so the two agree
+void prepare_radiance_wf(mcpt_scene& s, const RadianceEx& E, int64_t n, bool capturing, Prepared& P) {
+    if (capturing && (!s.rq_order.p || !s.rq_stats.p || !s.rad_wf_stats.p))
+        throw mcpt::Error{MCPT_E_NOMEM, "the first wavefront radiance query of a scene allocates: call "
+                                        "mcpt_scene_reserve_radiance_ex before capturing a graph"};
+    ensure_rays(s, capturing);
+    if (!s.rad_wf_stats.p) {
+        TempDev t(sizeof(mcpt::WfQueryBlock));
+        HIP_TRY(hipMemset(t.p, 0, sizeof(mcpt::WfQueryBlock)));
+        HIP_TRY(hipStreamSynchronize(nullptr));   // (as prepare_workspace: before a query on a non-blocking stream)
+        s.rad_wf_stats.p = t.release();
+    }
+    uint64_t tail = 0;                    // (the megakernel's split: a ray frame has none)
+    const mcpt::KernelParams k = radiance_plan(s, E.R, n, &tail);
+    // the render parameters the wavefront's plan reads: the query's samples and its wavefront fields
+    mcpt_render_params rp;
+    mcpt_render_params_default(&rp);
+    rp.pipeline = MCPT_PIPELINE_WAVEFRONT;
+    rp.spp = E.R.q.spp;
+    rp.wf_batch = E.x.wf_batch;
+    rp.wf_streams = E.x.wf_streams;
+    rp.wf_refill = E.x.wf_refill;
+    rp.wf_group_shift = E.x.wf_group_shift;
+    rp.wf_sort = E.x.wf_sort;
+    rp.wf_mem_limit = E.x.wf_mem_limit;
+    prepare_wavefront_rays(s, k, &rp, capturing, P);
+}
+
+// One wavefront query on st; returns the route's variant (4 in LDS, 5 in global memory).
+// The kernels count into the query's own block of kStatSlots words -- the shades and
+// extends also add to the route slots behind the eight Counters, which would overrun a
+// QueryBlocks member -- cleared on st in front of them and folded on st behind the join
+int radiance_wf_async(mcpt_scene& s, const RadianceEx& E, int64_t n, const float* d_o, const float* d_d,
+                      const uint32_t* d_stream, float* d_out, bool host_block, hipStream_t st) {
+    Prepared P;
+    prepare_radiance_wf(s, E, n, stream_capturing(st), P);
+    mcpt::WfQueryBlock* blk = wf_query_block(s);
+    mcpt::KernelParams& k = P.pl.kp;
+    k.stats = blk->stats;
+    // "queue 0 is explicit" (implicit0): a valid device address that no kernel of a ray frame reads
+    k.pixel_list = reinterpret_cast<const uint32_t*>(blk);
+    HIP_TRY(hipMemsetAsync(blk->stats, 0, sizeof blk->stats, st));
+    const mcpt::RayInputs ri{d_o, d_d, d_stream};
+    int variant = 0;
+    HIP_TRY(mcpt::launch_wavefront(k, P.pl.route, P.wf, wf_streams_on(s, P.pl.sets(), st), nullptr, nullptr, nullptr,
+                                   reinterpret_cast<float4*>(d_out), &variant, &ri));
+    HIP_TRY(mcpt::launch_wavefront_ray_fold(blk->stats, host_block ? query_blocks(s)->host : query_blocks(s)->device,
+                                            host_block ? nullptr : blk->routes, st));
+    return variant;
+}
+
 // the synchronous host entries' counter block (behind the device entries'), cleared
 unsigned long long* clear_host_block(mcpt_scene& s) {
     unsigned long long* blk = query_blocks(s)->host;
     HIP_TRY(hipMemset(blk, 0, sizeof(mcpt::QueryBlocks::host)));
     return blk;
+}
+
+// The synchronous host entry of a radiance query (arguments checked): rays, stream ids
+// and the result are staged in the scene's host-render buffer; run(d_o, d_d, d_stream,
+// d_out) is the query on the null stream, counting into the host entries' block, and
+// returns the record's variant
+template <typename Run>
+int radiance_host(mcpt_scene* s, const Radiance& R, int64_t n, const float* o, const float* d, const uint32_t* stream,
+                  float* radiance, mcpt_render_stats* stats, Run&& run) {
+    const size_t N = static_cast<size_t>(n);
+    if (ranges_overlap(radiance, N * 12, o, N * 12) || ranges_overlap(radiance, N * 12, d, N * 12) ||
+        ranges_overlap(radiance, N * 12, stream, stream ? N * 4 : 0))
+        return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+    unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int variant = 0;
+    if (n) {
+        set_device(*s);
+        const auto part = carve({N * 16, N * 12, N * 12, N * 4});
+        ensure_buf(s->ws.fb, part.total);
+        float* d_out = part.at<float>(s->ws.fb.p, 0);
+        float* d_o = part.at<float>(s->ws.fb.p, 1);
+        float* d_d = part.at<float>(s->ws.fb.p, 2);
+        uint32_t* d_s = part.at<uint32_t>(s->ws.fb.p, 3);
+        HIP_TRY(hipMemcpy(d_o, o, N * 12, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_d, d, N * 12, hipMemcpyHostToDevice));
+        if (stream) HIP_TRY(hipMemcpy(d_s, stream, N * 4, hipMemcpyHostToDevice));
+        std::vector<float> rgba(N * 4, 0.0f);
+        if (R.q.prev_count) {
+            rgb_to_rgba(radiance, N, rgba.data());
+            HIP_TRY(hipMemcpy(d_out, rgba.data(), N * 16, hipMemcpyHostToDevice));
+        }
+        ensure_rays(*s, false);       // (the counter blocks exist before the host entry's is cleared)
+        unsigned long long* blk = clear_host_block(*s);
+        variant = run(d_o, d_d, stream ? d_s : nullptr, d_out);
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        HIP_TRY(hipMemcpy(rgba.data(), d_out, N * 16, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c, blk, sizeof c, hipMemcpyDeviceToHost));
+        rgba_to_rgb(rgba.data(), N, radiance);
+    }
+    if (stats) {
+        stats_from_counters(c, *stats);
+        stats->variant = variant;
+    }
+    return MCPT_OK;
+}
+
+// the device entry of a radiance query behind its parameter checks; wf: the wavefront form's query, or null
+int radiance_device(mcpt_scene* s, const Radiance& R, const RadianceEx* wf, int64_t n, const float* d_o,
+                    const float* d_d, const uint32_t* d_stream, float* d_radiance, void* hip_stream) {
+    const size_t N = static_cast<size_t>(n);
+    if (ranges_overlap(d_radiance, N * 16, d_o, N * 12) || ranges_overlap(d_radiance, N * 16, d_d, N * 12) ||
+        ranges_overlap(d_radiance, N * 16, d_stream, d_stream ? N * 4 : 0))
+        return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+    if (!n) return MCPT_OK;
+    set_device(*s);                   // (a multi-device scene: devices[0], the primary)
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (wf) (void)radiance_wf_async(*s, *wf, n, d_o, d_d, d_stream, d_radiance, false, st);
+    else radiance_async(*s, R, n, d_o, d_d, d_stream, d_radiance, false, st);
+    return MCPT_OK;
 }
 
 }  // namespace
@@ -313,6 +458,8 @@ int mcpt_trace_stats_read(mcpt_scene* s, mcpt_render_stats* out) {
     return guarded([&]() -> int {
         if (!s || !s->on_device) return fail(MCPT_E_INVALID, "scene is not on a device");
         unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        // ... and with them the routes the wavefront radiance queries' rays took (mcpt_scene_query_route_rays)
+        unsigned long long r[mcpt::kQueryRoutes] = {};
         if (s->rq_stats.p) {              // (no query yet: zeros)
             DeviceGuard guard;
             set_device(*s);
@@ -320,7 +467,12 @@ int mcpt_trace_stats_read(mcpt_scene* s, mcpt_render_stats* out) {
             HIP_TRY(hipDeviceSynchronize());
             HIP_TRY(hipMemcpy(c, query_blocks(*s)->device, sizeof c, hipMemcpyDeviceToHost));
             HIP_TRY(hipMemset(query_blocks(*s)->device, 0, sizeof c));
+            if (s->rad_wf_stats.p) {
+                HIP_TRY(hipMemcpy(r, wf_query_block(*s)->routes, sizeof r, hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemset(wf_query_block(*s)->routes, 0, sizeof r));
+            }
         }
+        for (int i = 0; i < mcpt::kQueryRoutes; i++) s->query_routes[i] = r[i];
         if (out) stats_from_counters(c, *out);
         return MCPT_OK;
     });
@@ -340,53 +492,19 @@ int mcpt_radiance_device(mcpt_scene* s, const mcpt_radiance_params* p, int64_t n
                          const uint32_t* d_stream, float* d_radiance, void* hip_stream) {
     return guarded([&]() -> int {
         const Radiance R = radiance_resolve(s, p, n, d_o && d_d && d_radiance);
-        const size_t N = static_cast<size_t>(n);
-        if (ranges_overlap(d_radiance, N * 16, d_o, N * 12) || ranges_overlap(d_radiance, N * 16, d_d, N * 12) ||
-            ranges_overlap(d_radiance, N * 16, d_stream, d_stream ? N * 4 : 0))
-            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
-        if (!n) return MCPT_OK;
-        set_device(*s);                   // (a multi-device scene: devices[0], the primary)
-        radiance_async(*s, R, n, d_o, d_d, d_stream, d_radiance, false, static_cast<hipStream_t>(hip_stream));
-        return MCPT_OK;
+        return radiance_device(s, R, nullptr, n, d_o, d_d, d_stream, d_radiance, hip_stream);
     });
 }
 
-// rays, stream ids and the result are staged in the scene's host-render buffer
 int mcpt_radiance(mcpt_scene* s, const mcpt_radiance_params* p, int64_t n, const float* o, const float* d,
                   const uint32_t* stream, float* radiance, mcpt_render_stats* stats) {
     return guarded([&]() -> int {
         const Radiance R = radiance_resolve(s, p, n, o && d && radiance);
-        const size_t N = static_cast<size_t>(n);
-        if (ranges_overlap(radiance, N * 12, o, N * 12) || ranges_overlap(radiance, N * 12, d, N * 12) ||
-            ranges_overlap(radiance, N * 12, stream, stream ? N * 4 : 0))
-            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
-        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (n) {
-            set_device(*s);
-            const auto part = carve({N * 16, N * 12, N * 12, N * 4});
-            ensure_buf(s->ws.fb, part.total);
-            float* d_out = part.at<float>(s->ws.fb.p, 0);
-            float* d_o = part.at<float>(s->ws.fb.p, 1);
-            float* d_d = part.at<float>(s->ws.fb.p, 2);
-            uint32_t* d_s = part.at<uint32_t>(s->ws.fb.p, 3);
-            HIP_TRY(hipMemcpy(d_o, o, N * 12, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d_d, d, N * 12, hipMemcpyHostToDevice));
-            if (stream) HIP_TRY(hipMemcpy(d_s, stream, N * 4, hipMemcpyHostToDevice));
-            std::vector<float> rgba(N * 4, 0.0f);
-            if (R.q.prev_count) {
-                rgb_to_rgba(radiance, N, rgba.data());
-                HIP_TRY(hipMemcpy(d_out, rgba.data(), N * 16, hipMemcpyHostToDevice));
-            }
-            ensure_rays(*s, false);       // (the counter blocks exist before the host entry's is cleared)
-            unsigned long long* blk = clear_host_block(*s);
-            radiance_async(*s, R, n, d_o, d_d, stream ? d_s : nullptr, d_out, true, nullptr);
-            HIP_TRY(hipStreamSynchronize(nullptr));
-            HIP_TRY(hipMemcpy(rgba.data(), d_out, N * 16, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(c, blk, sizeof c, hipMemcpyDeviceToHost));
-            rgba_to_rgb(rgba.data(), N, radiance);
-        }
-        if (stats) stats_from_counters(c, *stats);
-        return MCPT_OK;
+        return radiance_host(s, R, n, o, d, stream, radiance, stats,
+                             [&](const float* d_o, const float* d_d, const uint32_t* d_s, float* d_out) {
+                                 radiance_async(*s, R, n, d_o, d_d, d_s, d_out, true, nullptr);
+                                 return 0;
+                             });
     });
 }
 
@@ -400,6 +518,59 @@ int mcpt_scene_reserve_radiance(mcpt_scene* s, const mcpt_radiance_params* p, in
         ensure_radiance(*s, k, tail, false, false);
         return MCPT_OK;
     });
+}
+
+int mcpt_radiance_ex_device(mcpt_scene* s, const mcpt_radiance_ex_params* p, int64_t n, const float* d_o,
+                            const float* d_d, const uint32_t* d_stream, float* d_radiance, void* hip_stream) {
+    return guarded([&]() -> int {
+        const RadianceEx E = radiance_ex_resolve(s, p, n, d_o && d_d && d_radiance);
+        return radiance_device(s, E.R, E.wavefront() ? &E : nullptr, n, d_o, d_d, d_stream, d_radiance, hip_stream);
+    });
+}
+
+int mcpt_radiance_ex(mcpt_scene* s, const mcpt_radiance_ex_params* p, int64_t n, const float* o, const float* d,
+                     const uint32_t* stream, float* radiance, mcpt_render_stats* stats) {
+    return guarded([&]() -> int {
+        const RadianceEx E = radiance_ex_resolve(s, p, n, o && d && radiance);
+        return radiance_host(s, E.R, n, o, d, stream, radiance, stats,
+                             [&](const float* d_o, const float* d_d, const uint32_t* d_s, float* d_out) {
+                                 if (E.wavefront()) return radiance_wf_async(*s, E, n, d_o, d_d, d_s, d_out, true, nullptr);
+                                 radiance_async(*s, E.R, n, d_o, d_d, d_s, d_out, true, nullptr);
+                                 return 0;
+                             });
+    });
+}
+
+// (the wavefront form reserves as mcpt_scene_reserve does for a render: the workspace is
+// the renders', and from here on a buffer that grows is retired, not freed)
+int mcpt_scene_reserve_radiance_ex(mcpt_scene* s, const mcpt_radiance_ex_params* p, int64_t n) {
+    return guarded([&]() -> int {
+        const RadianceEx E = radiance_ex_resolve(s, p, n, true);
+        DeviceGuard guard;
+        set_device(*s);
+        if (!E.wavefront()) {
+            uint64_t tail = 0;
+            mcpt::KernelParams k = radiance_plan(*s, E.R, n, &tail);
+            ensure_radiance(*s, k, tail, false, false);
+            return MCPT_OK;
+        }
+        if (!n) return MCPT_OK;
+        s->reserved = true;
+        Prepared P;
+        prepare_radiance_wf(*s, E, n, false, P);
+        // (the kernels' code objects loaded now: the reduce's, the pipeline's, the ray frame's)
+        HIP_TRY(mcpt::prepare_radiance(s->gpu));
+        HIP_TRY(mcpt::load_wavefront(P.pl.route));
+        HIP_TRY(mcpt::load_wavefront_rays());
+        s->wf_reserved = std::max(s->wf_reserved, s->ws.wf.bytes);
+        return MCPT_OK;
+    });
+}
+
+int mcpt_scene_query_route_rays(const mcpt_scene* s, uint64_t out[4]) {
+    if (!s || !out) return fail(MCPT_E_INVALID, "NULL argument");
+    for (int i = 0; i < mcpt::kQueryRoutes; i++) out[i] = s->query_routes[i];
+    return MCPT_OK;
 }
 
 }  // extern "C"

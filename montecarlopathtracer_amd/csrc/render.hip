@@ -611,6 +611,11 @@ hipError_t launch_radiance(const KernelParams& kp_in, const RayInputs& ri, int c
     else
         e = launch_rad<true, kRadLdsS, kLdsBlock>(kp, ri, grid, lds_bytes_in_lds(kp.scene.image_bytes, kRadLdsS), st);
     if (e != hipSuccess) return e;
+    return launch_radiance_reduce(kp, out, st);
+}
+
+hipError_t launch_radiance_reduce(const KernelParams& kp, float4* out, hipStream_t st) {
+    if (!kp.npix_local) return hipSuccess;
     hipLaunchKernelGGL(radiance_reduce_kernel, dim3((kp.npix_local + 255u) / 256u), dim3(256), 0, st, kp, out);
     return hipGetLastError();
 }

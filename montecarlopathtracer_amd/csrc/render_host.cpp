@@ -15,6 +15,23 @@
 
 using namespace mcpt::host;
 
+namespace mcpt::host {
+
+// the wavefront's streams for a render on st: the caller's, then the scene's side streams
+mcpt::WfStreams wf_streams_on(const mcpt_scene& s, int n, hipStream_t st) {
+    mcpt::WfStreams wst{};
+    wst.n = n;
+    wst.st[0] = st;
+    wst.fork = s.wf_fork;
+    for (int i = 1; i < wst.n; i++) {
+        wst.st[i] = s.wf_stream[i];
+        wst.join[i] = s.wf_join[i];
+    }
+    return wst;
+}
+
+}  // namespace mcpt::host
+
 namespace {
 
 // RCCL, resolved from librccl at the first render that asks for its gather
@@ -82,19 +99,6 @@ Timing acquire_timing(mcpt_scene& s, bool capturing) {
         for (auto& ev : t.e) HIP_TRY(hipEventCreate(&ev));
     }
     return t;
-}
-
-// the wavefront's streams for a render on st: the caller's, then the scene's side streams
-mcpt::WfStreams wf_streams_on(const mcpt_scene& s, int n, hipStream_t st) {
-    mcpt::WfStreams wst{};
-    wst.n = n;
-    wst.st[0] = st;
-    wst.fork = s.wf_fork;
-    for (int i = 1; i < wst.n; i++) {
-        wst.st[i] = s.wf_stream[i];
-        wst.join[i] = s.wf_join[i];
-    }
-    return wst;
 }
 
 // d_var: also the per-pixel variance of this call's pixel mean (variance.hip),

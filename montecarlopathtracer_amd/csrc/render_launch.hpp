@@ -271,7 +271,9 @@ struct KernelParams {
     int32_t raw_mean;
     // pixel-list kernels (adaptive sampling; the megakernel's list kernel and the
     // wavefront's wf_generate_list): packed pixel index of listed pixel i;
-    // npix_local is then the list's length
+    // npix_local is then the list's length.  To the wavefront's other kernels a non-null
+    // pointer only says "queue 0 is explicit" (implicit0, wf_device.hpp): a ray frame sets
+    // one that nothing dereferences ("Ray frames" below)
     const uint32_t* pixel_list;
 };
 
@@ -284,6 +286,14 @@ struct RayInputs {
     const float* d;
     const uint32_t* stream;
 };
+// Ray frames (the wavefront form of the radiance queries, mcpt_radiance_ex_device): a
+// wavefront render of n "pixels" that are the caller's rays, planned as a frame over a
+// pixel list is (WfFacts::listed: no packet extend, no primary lists).  wf_ray_generate
+// (wavefront_rays.hip) fills an explicit queue 0 from RayInputs as path_body's RAYS form
+// starts its paths; bounce 0's extend is wf_ray_extend0, the extend reading its origins
+// from the queue; every later kernel is the renders' -- a path is its pid, pid % nb its
+// column of the [chunk][ray] partial sums -- and radiance_reduce_kernel ends the frame.
+// kp.pixel_list is non-null and never dereferenced; kp.stats is a WfQueryBlock's.
 // fewest work items (ray, chunk) a workgroup of the automatic grid gets, so the
 // grid shrinks with the work (the ray queries' floor, rayquery_launch.hpp)
 constexpr uint32_t kRadMinUnits = 64;
@@ -446,6 +456,17 @@ hipError_t prepare_radiance(const GpuScene& sc);
 uint32_t radiance_grid(const GpuScene& sc, uint64_t items, int cus, int max_workgroups);
 hipError_t launch_radiance(const KernelParams& kp, const RayInputs& ri, int cus, int max_workgroups, float4* out,
                            hipStream_t st);
+// the wavefront's kernels a ray frame of this route launches, and wavefront_rays.hip's,
+// resolved on the current device (mcpt_scene_reserve_radiance_ex: as prepare_radiance)
+struct WfRoute;
+hipError_t load_wavefront(const WfRoute& route);
+hipError_t load_wavefront_rays();
+// the query's reduce alone (a ray frame's, behind the wavefront's batches)
+hipError_t launch_radiance_reduce(const KernelParams& kp, float4* out, hipStream_t st);
+// wavefront_rays.hip: a wavefront query's counter block (WfQueryBlock::stats) folded into
+// the eight counters of a QueryBlocks member and, unless null, the route-ray record
+hipError_t launch_wavefront_ray_fold(const unsigned long long* blk, unsigned long long* counters,
+                                     unsigned long long* routes, hipStream_t st);
 hipError_t launch_gather(const GatherParams& g, hipStream_t st);
 hipError_t launch_query(const QueryParams& q, hipStream_t st);
 #ifdef MCPT_PHASE_TIMING
@@ -462,6 +483,8 @@ void read_lane_use_wf(unsigned long long out[6]);   // wavefront extend
 // listed pixels, CV mode -- wf_generate_list fills an explicit queue 0, bounce 0
 // runs the ordinary extend and shade, no candidate pass; fb == nullptr then skips
 // the reduction (the caller merges the partial sums, launch_adaptive_merge)
+// rays set: a ray frame ("Ray frames" above) -- generate and bounce 0 read *rays, and fb
+// is the query's output, written by the radiance queries' reduction
 constexpr int kMaxWfStreams = 4;
 struct WfStreams {
     int n;
@@ -470,6 +493,7 @@ struct WfStreams {
 };
 struct WfRoute;
 hipError_t launch_wavefront(const KernelParams& kp, const WfRoute& route, const WfParams* wf, const WfStreams& ws,
-                            hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2, float4* fb, int* variant_out);
+                            hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2, float4* fb, int* variant_out,
+                            const RayInputs* rays = nullptr);
 
 }  // namespace mcpt

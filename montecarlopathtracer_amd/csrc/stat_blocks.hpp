@@ -57,6 +57,18 @@ static_assert(offsetof(RenderBlock, stats) % 8 == 0 && alignof(RenderBlock) >= 8
 struct QueryBlocks {
     unsigned long long device[kStatCounters], host[kStatCounters];
 };
+// A wavefront radiance query's block (mcpt_radiance_ex_device, mcpt_scene::rad_wf_stats).
+// stats: the KernelParams::stats of the query's kernels -- all kStatSlots of them: the
+// wavefront's shades and extends also add to the route slots behind the eight Counters,
+// which a QueryBlocks member has no room for.  Cleared on the query's stream in front of
+// it and folded behind it (wf_ray_fold_stats): the Counters into QueryBlocks::device or
+// ::host, the routes of a device-entry query into `routes`, {direct, extend, clipped,
+// sphere_skips}, which mcpt_trace_stats_read reads and clears with the device block
+constexpr int kQueryRoutes = 4;
+struct WfQueryBlock {
+    unsigned long long stats[kStatSlots];
+    unsigned long long routes[kQueryRoutes];
+};
 // a work-unit counter on its own (the radiance queries': mcpt_scene::rad_small)
 constexpr size_t kUnitCounterBytes = sizeof(RenderBlock::counter);
 

@@ -159,6 +159,7 @@ __global__ void __launch_bounds__(BLOCK, (LAY == kLayGlobal && !COUNT && MCPT_WF
                                                     ? MCPT_WF_LDS_WPE : 1))   // (waves per SIMD)
 wf_extend(const KernelParams kp, const WfParams wf) {
     constexpr bool SPHERE = false;
+    constexpr bool RAYS0 = false;
     constexpr SphereClip sphc = {};      // (never read: SPHERE is false)
 #include "wf_extend_body.hpp"
 }
@@ -594,10 +595,12 @@ struct WfBatch {
     WfParams wf;                         // the stream's, with the batch's fields and the bounce under way
     hipStream_t st;
     bool lists;                          // bounce 0 reads the primary lists (a batch of whole tiles)
+    const RayInputs* rays;               // a ray frame: the caller's rays (else null)
 };
 
-// (a frame over a pixel list: its generate looks the pixel up)
+// (a frame over a pixel list: its generate looks the pixel up; a ray frame: the ray)
 hipError_t launch_generate(const WfBatch& b) {
+    if (b.rays) return launch_wavefront_ray_generate(b.kp, b.wf, *b.rays, b.route.cus, b.st);
     const uint32_t n = b.wf.nb * b.wf.ns, gen_grid = (n + kGenBlock - 1) / kGenBlock, cap = 16u * (uint32_t)b.route.cus;
     hipLaunchKernelGGL(b.kp.pixel_list ? wf_generate_list : wf_generate, dim3(gen_grid < cap ? gen_grid : cap),
                        dim3(kGenBlock), 0, b.st, b.kp, b.wf);
@@ -611,9 +614,11 @@ hipError_t launch_generate(const WfBatch& b) {
 // bounce: the extend of where the scene lives.
 // A secondary extend of a render that clips to spheres (WfRoute::clip: lean,
 // so the kernel has no counting form): wf_sphere_clip.  Bounce 0's rays carry no
-// selector and keep the plain extend.
-enum class Extend { kPrimaryShade, kPrimaryLists, kPacket, kLds, kSphereClip, kGlobal };
-Extend extend_form(const WfRoute& r, int bounce, bool lists) {
+// selector and keep the plain extend.  Bounce 0 of a ray frame: wf_ray_extend0, the
+// extend of where the scene lives reading its origins from the queue.
+enum class Extend { kPrimaryShade, kPrimaryLists, kPacket, kLds, kSphereClip, kGlobal, kRays0 };
+Extend extend_form(const WfRoute& r, int bounce, bool lists, bool rays) {
+    if (bounce == 0 && rays) return Extend::kRays0;
     if (bounce == 0 && lists) return r.primary_shade ? Extend::kPrimaryShade : Extend::kPrimaryLists;
     if (bounce == 0 && r.packet) return Extend::kPacket;
     if (bounce > 0 && r.clip.mask) return Extend::kSphereClip;
@@ -622,7 +627,7 @@ Extend extend_form(const WfRoute& r, int bounce, bool lists) {
 hipError_t launch_bounce(const WfBatch& b, bool* shaded) {
     const WfRoute& r = b.route;
     const WfParams& wf = b.wf;
-    const Extend form = extend_form(r, wf.bounce, b.lists);
+    const Extend form = extend_form(r, wf.bounce, b.lists, b.rays != nullptr);
     *shaded = form == Extend::kPrimaryShade;
     switch (form) {
         case Extend::kPrimaryShade: return launch_wavefront_primary_shade(b.kp, wf, (int)r.nseg, r.primary_shade_lds, b.st);
@@ -630,6 +635,7 @@ hipError_t launch_bounce(const WfBatch& b, bool* shaded) {
         case Extend::kPacket: return launch_wavefront_primary(b.kp, wf, (int)r.nseg, r.packet_lds, b.st);
         case Extend::kLds: return launch_extend<kLayLds, 4, kLdsBlock>(b.kp, wf, (int)r.nseg, r.extend_lds, b.st);
         case Extend::kSphereClip: return launch_wavefront_sphere_clip(b.kp, wf, r.clip, (int)r.nseg, r.extend_lds, b.st);
+        case Extend::kRays0: return launch_wavefront_ray_extend0(b.kp, wf, r.in_lds, (int)r.nseg, r.extend_lds, b.st);
         default: return launch_extend<kLayGlobal, MCPT_WF_GLOBAL_S, kGlobalBlock>(b.kp, wf, (int)r.nseg, r.extend_lds, b.st);
     }
 }
@@ -677,8 +683,18 @@ hipError_t launch_batch(WfBatch& b, int streams, uint32_t ncb) {
 
 }  // namespace
 
+// The pipeline's kernels resolved on the current device (a reserve that wants its first
+// launch to load no code object: one kernel per translation unit)
+hipError_t load_wavefront(const WfRoute& route) {
+    hipFuncAttributes a;
+    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(wf_accumulate));
+    if (e == hipSuccess && route.clip.mask) e = load_wavefront_sphere_clip();
+    return e;
+}
+
 hipError_t launch_wavefront(const KernelParams& kp_in, const WfRoute& route, const WfParams* wf_in, const WfStreams& ws,
-                            hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2, float4* fb, int* variant_out) {
+                            hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2, float4* fb, int* variant_out,
+                            const RayInputs* rays) {
     KernelParams kp = kp_in;
     kp.total_lanes = (uint32_t)total_lanes_for(kp.scene, route.cus);
     // Several streams (ws.n > 1): batch i runs on stream i mod n, each stream
@@ -717,7 +733,7 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfRoute& route, con
     uint32_t batch = 0;
     wf_for_each_batch(kp, wf_in[0].capacity, route.whole, [&](const WfSpan& span, uint32_t chunk0, uint32_t v0) {
         const int h = (int)(batch++ % (uint32_t)ns);
-        WfBatch b{route, kp, wf_batch_params(wf_in[h], route, kp, span, chunk0, v0), ws.st[h], false};
+        WfBatch b{route, kp, wf_batch_params(wf_in[h], route, kp, span, chunk0, v0), ws.st[h], false, rays};
         b.kp.spill = kp.spill + (size_t)h * 32 * kp.total_lanes;       // this stream's spill area
         b.lists = lists && whole_tiles(b.wf.v0, b.wf.nb);
         if (b.lists) b.wf.tile_cand = wf_in[0].tile_cand;             // (stream 0's records are the render's)
@@ -733,7 +749,8 @@ hipError_t launch_wavefront(const KernelParams& kp_in, const WfRoute& route, con
     if (ev1 && (e = hipEventRecord(ev1, st)) != hipSuccess) return e;
     // (fb == nullptr: no reduction -- a frame over a pixel list, whose caller merges
     // the partial sums into its pixels, adaptive.hip)
-    if (fb) e = launch_reduce(kp, fb, st);
+    // (a ray frame: the radiance queries' reduction into out[ray])
+    if (fb) e = rays ? launch_radiance_reduce(kp, fb, st) : launch_reduce(kp, fb, st);
     if (e == hipSuccess && ev2) e = hipEventRecord(ev2, st);
     if (variant_out) *variant_out = route.variant;
     return e;

@@ -20,10 +20,16 @@ wf_sphere_clip(const KernelParams kp, const WfParams wf, const SphereClip sphc) 
     constexpr int LAY = kLayLds;
     constexpr bool COUNT = false;
     constexpr bool SPHERE = true;
+    constexpr bool RAYS0 = false;
 #include "wf_extend_body.hpp"
 }
 
 }  // namespace
+
+hipError_t load_wavefront_sphere_clip() {
+    hipFuncAttributes a;
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(wf_sphere_clip<4, kLdsBlock>));
+}
 
 hipError_t launch_wavefront_sphere_clip(const KernelParams& kp, const WfParams& wf, const SphereClip& clip, int grid,
                                         size_t lds, hipStream_t st) {

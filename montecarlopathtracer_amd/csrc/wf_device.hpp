@@ -36,6 +36,13 @@ hipError_t launch_wavefront_primary_shade(const KernelParams& kp, const WfParams
 // boxes' spheres (lds: the lean LDS extend's)
 hipError_t launch_wavefront_sphere_clip(const KernelParams& kp, const WfParams& wf, const SphereClip& clip, int grid,
                                         size_t lds, hipStream_t st);
+hipError_t load_wavefront_sphere_clip();   // (its code object loaded now)
+// wavefront_rays.hip: a ray frame's generate over the caller's ray buffers and its
+// bounce-0 extend, which reads its origins from the queue (lds: WfRoute::extend_lds)
+hipError_t launch_wavefront_ray_generate(const KernelParams& kp, const WfParams& wf, const RayInputs& ri, int cus,
+                                         hipStream_t st);
+hipError_t launch_wavefront_ray_extend0(const KernelParams& kp, const WfParams& wf, bool in_lds, int grid, size_t lds,
+                                        hipStream_t st);
 
 namespace {
 
@@ -188,6 +195,10 @@ __host__ __device__ __forceinline__ bool eye_origins0(const KernelParams& kp) {
 // generate writes all three streams, the host launches no packet extend and the
 // shade reads its state.  (A test of a kernel argument: a scalar compare.)  Its
 // origins are the eye all the same: the extend keeps eye_origins0 and its code.
+// The pointer also marks "explicit queue 0" for a ray frame (the wavefront radiance
+// queries, render_launch.hpp "Ray frames"): its host sets a non-null pixel_list that
+// no kernel of its route dereferences, so the shades read bounce 0's state from the
+// queue; its origins are the caller's, and its bounce 0 has an extend of its own.
 __host__ __device__ __forceinline__ bool implicit0(const KernelParams& kp, const WfParams& wf) {
     return eye_origins0(kp) && kp.pixel_list == nullptr;
 }

@@ -5,6 +5,9 @@
 // function, so that wf_extend's code stays what it was.  The includer defines LAY, S,
 // BLOCK, COUNT and SPHERE (compile-time), has kp and wf as the kernel's arguments and
 // sphc, the SphereClip the SPHERE form reads (its kernel argument; wf_extend: none).
+// wavefront_rays.hip includes it into wf_ray_extend0 with RAYS0 defined true: bounce 0
+// of a ray frame (the wavefront radiance queries), whose origins are the caller's and
+// are read from the queue; the other two define it false.
     constexpr bool IN_LDS = LAY != kLayGlobal;            // node words in LDS
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t g = blockIdx.x;
@@ -150,8 +153,9 @@
     int refill;
     asm volatile("s_mov_b32 %0, %1" : "=s"(refill) : "s"(wf.refill_thresh));
     // MCPT_WF_IMPLICIT0 >= 2: bounce 0's origins are the eye (CV mode), not read
-    // (also over a pixel list, whose generate writes the eye into every slot)
-    const bool eye0 = MCPT_WF_IMPLICIT0 >= 2 && wf.bounce == 0 && eye_origins0(kp);
+    // (also over a pixel list, whose generate writes the eye into every slot; never
+    // in a ray frame's bounce 0, RAYS0)
+    const bool eye0 = !RAYS0 && MCPT_WF_IMPLICIT0 >= 2 && wf.bounce == 0 && eye_origins0(kp);
     const float4 eye4 = make_float4(kp.eye[0], kp.eye[1], kp.eye[2], 0.0f);
     auto ld_o = [&](uint32_t sl) { return eye0 ? eye4 : ldq(&qb[qf(seg0 + sl, kQO, qs)]); };
     if (slot < count) start(ld_o(slot), ldq(&qb[qf(seg0 + slot, kQD, qs)]));

@@ -67,7 +67,8 @@ struct WfFacts {
     uint32_t n_miss_boxes, direct_counts, n_cull_boxes;
     int cus;
     bool lean, sort, qe;
-    bool listed;                         // a frame over a pixel list (KernelParams::pixel_list)
+    bool listed;                         // a frame with an explicit queue 0: over a pixel list
+                                         // (KernelParams::pixel_list) or over ray buffers (a ray frame)
     bool default_batch;                  // the plan chose the batch (mcpt_render_params::wf_batch 0)
     bool tile_records;                   // the workspace has the primary lists' tile records (wf_layout)
     int tile, max_depth;

@@ -503,6 +503,52 @@ class Scene:
         (mcpt_scene_reserve_radiance): a later query that needs no more allocates nothing."""
         check(lib().mcpt_scene_reserve_radiance(self.handle, C.byref(radiance_params(**params)), int(n)))
 
+    def radiance_ex_device(self, n: int, o_ptr: int, d_ptr: int, out_ptr: int, stream_ids_ptr: int = 0,
+                           stream_ptr: int = 0, **params):
+        """``radiance_device`` with the pipeline as a parameter (mcpt_radiance_ex_device).  params:
+        the fields of ``radiance_ex_params`` -- those of ``radiance_params``, ``pipeline``
+        ("megakernel", the default: exactly ``radiance_device``; "wavefront": the rays run as a
+        wavefront render of n pixels, same bits) and the wavefront's wf_batch, wf_streams,
+        wf_refill, wf_group_shift, wf_sort, wf_mem_limit (scheduling only).  Counted in
+        ``trace_stats``; on the wavefront a lean query counts rays, paths and shades."""
+        check(lib().mcpt_radiance_ex_device(self.handle, C.byref(radiance_ex_params(**params)), int(n),
+                                            C.c_void_p(o_ptr), C.c_void_p(d_ptr), C.c_void_p(stream_ids_ptr),
+                                            C.c_void_p(out_ptr), C.c_void_p(stream_ptr)))
+
+    def radiance_ex(self, o: np.ndarray, d: np.ndarray, stream_ids=None, prev=None, **params):
+        """``radiance`` with the pipeline as a parameter (mcpt_radiance_ex), synchronous: ((n, 3)
+        float32, counters of this call; ``variant`` 4 / 5 on the wavefront)."""
+        o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise McptError(-1, "o and d must have the same shape")
+        n = o.shape[0]
+        ids = None
+        if stream_ids is not None:
+            ids = np.ascontiguousarray(stream_ids, np.uint32).reshape(-1)
+            if ids.shape[0] != n:
+                raise McptError(-1, "stream_ids must hold one value per ray")
+        out = np.zeros((n, 3), np.float32)
+        if prev is not None:
+            out[...] = np.asarray(prev, np.float32).reshape(n, 3)
+        st = RenderStats()
+        check(lib().mcpt_radiance_ex(self.handle, C.byref(radiance_ex_params(**params)), n, _fptr(o), _fptr(d),
+                                     ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None,
+                                     _fptr(out), C.byref(st)))
+        return out, st.as_dict()
+
+    def reserve_radiance_ex(self, n: int, **params):
+        """Allocate what a query of n rays with these ``radiance_ex_params`` needs
+        (mcpt_scene_reserve_radiance_ex): a later query that needs no more allocates nothing."""
+        check(lib().mcpt_scene_reserve_radiance_ex(self.handle, C.byref(radiance_ex_params(**params)), int(n)))
+
+    def query_route_rays(self):
+        """(direct, extend, clipped, sphere_skips) rays of the wavefront radiance queries in the
+        record ``trace_stats`` last read (mcpt_scene_query_route_rays)."""
+        out = (C.c_uint64 * 4)()
+        check(lib().mcpt_scene_query_route_rays(self.handle, out))
+        return tuple(int(v) for v in out)
+
     def render_unit_counters(self, params: RenderParams):
         """Synchronous render returning (fb, per-unit counters (units, 4): rays, inner, leaf, tests)."""
         n = params.output_pixels()
@@ -697,6 +743,26 @@ def radiance_params(**kw) -> "_capi.RadianceParamsC":
         if k not in names:
             raise McptError(-1, f"unknown radiance parameter {k!r}")
         setattr(p, k, float(v) if k == "illum" else int(v))
+    return p
+
+
+def radiance_ex_params(**kw) -> "_capi.RadianceExParamsC":
+    """mcpt_radiance_ex_params: the library's defaults (``radiance_params``' in ``base``, the
+    megakernel, every wavefront field automatic), then the fields of either struct given by name;
+    pipeline: "megakernel" / "wavefront" or the constant."""
+    p = _capi.RadianceExParamsC()
+    lib().mcpt_radiance_ex_params_default(C.byref(p))
+    base = {n for n, _ in _capi.RadianceParamsC._fields_}
+    own = {n for n, _ in _capi.RadianceExParamsC._fields_} - {"base"}
+    for k, v in kw.items():
+        if k in base:
+            setattr(p.base, k, float(v) if k == "illum" else int(v))
+        elif k == "pipeline":
+            p.pipeline = PIPELINES[v] if isinstance(v, str) else int(v)
+        elif k in own:
+            setattr(p, k, int(v))
+        else:
+            raise McptError(-1, f"unknown radiance parameter {k!r}")
     return p
 
 

@@ -15,6 +15,13 @@ each call, after a warm-up of both, until each has filled a window of at least -
 seconds; ms = the median, spread = (max - min) / median.  Rays are counted by the kernels
 (lean kernels count rays only), so G rays/s is each side's own rays over its own time.
 One JSON line per scene and n is printed and appended to --out.
+
+    python scripts/bench_radiance.py --pipeline wavefront [--out profiles/radiance/bench_wf.jsonl]
+
+times the wavefront form of the query (mcpt_radiance_ex_device, pipeline = wavefront, every
+wavefront field automatic) beside the megakernel form on the same rays and parameters, the
+two alternated call by call in the same way; the two outputs are compared bit for bit once
+("same_bits") and ratio_time is wavefront ms / megakernel ms.
 """
 import argparse
 import json
@@ -109,6 +116,46 @@ def measure(scene, name, log2n, spp, window):
             "mean_radiance": round(float(out[:, :3].mean()), 5), "mean_render": round(float(fb[:, :3].mean()), 5)}
 
 
+def measure_wavefront(scene, name, log2n, spp, window):
+    """the wavefront query beside the megakernel query, same rays, same parameters"""
+    n = 1 << log2n
+    side = 1 << (log2n // 2)
+    assert side * side == n, "n must be an even power of two"
+    st = torch.cuda.current_stream().cuda_stream
+    o, d = pixel_centre_rays(side)
+    out = torch.empty((n, 4), dtype=torch.float32, device="cuda")
+    out_wf = torch.empty((n, 4), dtype=torch.float32, device="cuda")
+    scene.reserve_radiance(n, spp=spp)
+    scene.reserve_radiance_ex(n, pipeline="wavefront", spp=spp, lean=1)
+
+    def megakernel():
+        scene.radiance_device(n, o.data_ptr(), d.data_ptr(), out.data_ptr(), 0, st, spp=spp, lean=1)
+
+    def wavefront():
+        scene.radiance_ex_device(n, o.data_ptr(), d.data_ptr(), out_wf.data_ptr(), 0, st, pipeline="wavefront", spp=spp,
+                                 lean=1)
+
+    rays = []
+    for fn in (megakernel, wavefront):          # rays of one call of each (the kernels' own counts)
+        scene.trace_stats()
+        fn()
+        torch.cuda.synchronize()
+        rays.append(scene.trace_stats()["rays"])
+    routes = scene.query_route_rays()
+    same = bool(torch.equal(out.view(torch.int32), out_wf.view(torch.int32)))
+    m, w = timed_alternately([megakernel, wavefront], window)
+    scene.trace_stats()
+    for rec, r in ((m, rays[0]), (w, rays[1])):
+        rec["rays"] = int(r)
+        rec["Grays_s"] = round(r / (rec["ms"] * 1e-3) / 1e9, 4)
+        rec["Mpaths_s"] = round(n * spp / (rec["ms"] * 1e-3) / 1e6, 2)
+    return {"bench": "radiance_wf", "scene": name, "layout": "global" if scene.info()["node_boxes"] else "lds",
+            "n": n, "log2n": log2n, "spp": spp, "paths": n * spp, "megakernel": m, "wavefront": w,
+            "ratio_time": round(w["ms"] / m["ms"], 4), "sum_spreads": round(m["spread"] + w["spread"], 4),
+            "wavefront_faster_by": round(1.0 - w["ms"] / m["ms"], 4), "same_bits": same,
+            "route_rays": {"direct": routes[0], "extend": routes[1], "clipped": routes[2], "sphere_skips": routes[3]}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", type=float, default=0.5)
@@ -116,6 +163,8 @@ def main():
     ap.add_argument("--sizes", default="16,20,22", help="log2 of the ray counts (even)")
     ap.add_argument("--spp", type=int, default=16)
     ap.add_argument("--scenes", default=",".join(SCENES))
+    ap.add_argument("--pipeline", default="megakernel", choices=["megakernel", "wavefront"],
+                    help="wavefront: the wavefront query beside the megakernel query")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     torch.cuda.set_device(0)
@@ -123,7 +172,14 @@ def main():
     for name in [s for s in a.scenes.split(",") if s]:
         scene = M.Scene(M.ObjModel(M.scene_path(name)))
         for s in [int(x) for x in a.sizes.split(",") if x]:
-            lines.append(measure(scene, name, s, a.spp, a.window))
+            if a.pipeline == "wavefront":
+                # a scene per size: a wavefront reservation bounds the default batches of later,
+                # larger queries (as mcpt_scene_reserve's does), and each size is to run in its own
+                sized = M.Scene(M.ObjModel(M.scene_path(name)))
+                lines.append(measure_wavefront(sized, name, s, a.spp, a.window))
+                del sized
+            else:
+                lines.append(measure(scene, name, s, a.spp, a.window))
             torch.cuda.empty_cache()
         del scene
     torch.cuda.synchronize()
