@@ -786,6 +786,91 @@ int mcpt_scene_reserve_radiance_ex(mcpt_scene*, const mcpt_radiance_ex_params*, 
    mcpt_trace_stats_read last read (zeros for megakernel queries and the hit queries) */
 int mcpt_scene_query_route_rays(const mcpt_scene*, uint64_t out[4]);
 
+/* ---- ambient-occlusion queries: hemisphere visibility of points and of pixels ---- */
+/* Between the hit queries and the radiance queries: for every point, the share
+ * of spp cosine-hemisphere rays of length `radius` that reach nothing (1 = open).
+ * The library makes the rays -- the renders' RNG, hemisphere sampler and origin
+ * rule -- and walks them with mcpt_occluded_device's any-hit walk; no buffer of
+ * rays or flags exists.  All float arithmetic is fp32, one rounding per
+ * operation.  CVMCTracer mode.
+ * Point form (mcpt_ao[_device]): points p_i and normals n_i (unit length, used
+ * as given), stream id id_i = d_stream[i], or i without d_stream.  Sample s of
+ * point i, s in [0, spp): sd = rng_init(id_i, TEA16(seed), spp_offset + s), the
+ * renders' and the radiance queries' stream; two uniforms are drawn and dropped
+ * (a render's jitter, as mcpt_radiance_device); x, y the next two; h = the
+ * renders' hemisphere sample of (x, y) about n_i (the reference's sampleHemi);
+ * origin p_i + bias * h, direction h; the sample is occluded iff
+ * mcpt_occluded_device answers 1 for that ray with t_max = radius.
+ * Pixel form (mcpt_render_ao[_device]): sample s of pixel (px, py) of a frame is
+ * the render's primary ray of sample spp_offset + s -- same stream, jitter and
+ * reprojection as the renders and mcpt_render_aov -- and its closest hit.  A miss
+ * counts as unoccluded and traces no second ray.  A hit forms what a render's
+ * diffuse scatter forms there, whatever the material (emitters, glass and Phong
+ * alike; the material is not read): the normalized shading normal nrm, flip =
+ * dot(d, nrm) > 0, h = the hemisphere sample of the stream's next two draws
+ * about nrm, dir = flip ? -h : h, origin (o + t * d) + 0.01 * dir; then the
+ * any-hit walk with t_max = radius.
+ * Value: v = (float)unoccluded / (float)spp; with prev_count > 0 the output is
+ * read first and (old * (float)prev_count + v) / (float)(prev_count + 1) is
+ * written (the feature buffers' linear running mean).  The unoccluded samples
+ * are counted in integers, so the scheduling fields, the layout and any split of
+ * a point's samples over lanes never change a bit.
+ * The pixel form reads width, height, spp, spp_offset, seed, prev_count, fov_deg,
+ * eye, dir, up and tile from the render params (the rest is ignored, as
+ * mcpt_render_aov does) and only radius, lean, workgroups, refill and
+ * unit_samples from the AO params: their spp, spp_offset, bias, seed and
+ * prev_count are checked and otherwise ignored.
+ * Checks, before anything is launched or allocated and in this order:
+ * MCPT_E_INVALID for a NULL scene, n < 0, a NULL required pointer with n > 0, a
+ * field out of range (the message names it); MCPT_E_UNSUPPORTED for n (or width x
+ * height) >= 2^31 / 3, and in the pixel form for QuinEngine mode, shard_count > 1
+ * and packed; MCPT_E_INVALID for a host-only scene and for an output that
+ * overlaps an input.  n = 0 is a no-op.  A multi-device scene answers on
+ * devices[0].  Not offered: distance-weighted falloff,
+ * QuinEngine mode, batches sharded over devices.
+ * Counters: the device entries add to the block mcpt_trace_stats_read reports, the
+ * host entries report their own call and leave that block alone; the render stats
+ * are never touched.  paths = samples started, shades = samples that formed an
+ * occlusion ray (point form: all; pixel form: the primary hits), rays = every ray
+ * walked (pixel form: primary and occlusion rays); the traversal counters are the
+ * sum of the walks, and read 0 on a lean call.
+ * Workspace, the scene's, O(n): the renders' stack spill area (run the queries on
+ * the stream of the scene's renders, or synchronize), the ray queries' counter
+ * blocks and 4 B per point or pixel.  After mcpt_scene_reserve_ao(n) or a first
+ * call, a call that needs no more allocates nothing; growth on a capturing
+ * stream is MCPT_E_NOMEM before any launch.                                   */
+typedef struct {
+    uint32_t spp;          /* samples per point this call; >= 1 */
+    uint32_t spp_offset;   /* first global sample index; spp_offset + spp <= 2^32 */
+    float    radius;       /* t_max of every occlusion ray; 0 = FLT_MAX (unbounded); >= 0, not NaN */
+    float    bias;         /* point form: origin = p + bias * dir; 0 = 0.01 (the renders' literal); > 0, finite */
+    uint64_t seed;
+    uint32_t prev_count;   /* running mean over calls; the output is read when > 0 */
+    int32_t  lean;         /* 1: traversal counters compiled out (rays, paths, shades still counted) */
+    int32_t  workgroups;   /* scheduling only, as mcpt_trace_params */
+    int32_t  refill;       /* scheduling only, 0 or 1..64 */
+    int32_t  unit_samples; /* scheduling only: samples of one point a lane takes as one work unit; 0 = automatic */
+} mcpt_ao_params;
+void mcpt_ao_params_default(mcpt_ao_params*);   /* spp 1, the renders' seed, rest 0 */
+
+/* d_p, d_n: n*3 floats each; d_stream: n stream ids or NULL; d_ao: n floats, read first when p->prev_count > 0.
+ * Asynchronous on hip_stream.  p may be NULL (the defaults). */
+int mcpt_ao_device(mcpt_scene*, const mcpt_ao_params* p, int64_t n, const float* d_p, const float* d_n,
+                   const uint32_t* d_stream, float* d_ao, void* hip_stream);
+/* host arrays, synchronous; ao: n floats (read first when p->prev_count > 0); stats may be NULL (the counters of
+ * this call) */
+int mcpt_ao(mcpt_scene*, const mcpt_ao_params* p, int64_t n, const float* p_xyz, const float* nrm,
+            const uint32_t* stream, float* ao, mcpt_render_stats* stats);
+/* d_ao: width*height floats, row-major, read first when rp->prev_count > 0.  Asynchronous on hip_stream.  ap may be
+ * NULL (the defaults); rp may not. */
+int mcpt_render_ao_device(mcpt_scene*, const mcpt_render_params* rp, const mcpt_ao_params* ap, float* d_ao,
+                          void* hip_stream);
+/* host array, synchronous; stats may be NULL (the counters of this call) */
+int mcpt_render_ao(mcpt_scene*, const mcpt_render_params* rp, const mcpt_ao_params* ap, float* ao,
+                   mcpt_render_stats* stats);
+/* allocate what a query of n points, or a frame of n pixels, needs (above) */
+int mcpt_scene_reserve_ao(mcpt_scene*, int64_t n_points_or_pixels);
+
 #ifdef __cplusplus
 }
 #endif

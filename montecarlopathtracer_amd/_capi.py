@@ -124,6 +124,12 @@ class RadianceExParamsC(C.Structure):
                 ("wf_sort", C.c_int32), ("wf_mem_limit", C.c_uint64)]
 
 
+class AoParamsC(C.Structure):
+    _fields_ = [("spp", C.c_uint32), ("spp_offset", C.c_uint32), ("radius", C.c_float), ("bias", C.c_float),
+                ("seed", C.c_uint64), ("prev_count", C.c_uint32), ("lean", C.c_int32), ("workgroups", C.c_int32),
+                ("refill", C.c_int32), ("unit_samples", C.c_int32)]
+
+
 TRACE_CLOSEST = 0
 TRACE_ANY = 1
 OBJ_CVMCTRACER = 0
@@ -239,6 +245,14 @@ _SIGS = {
                                    C.POINTER(RenderStats)]),
     "mcpt_scene_reserve_radiance_ex": (C.c_int, [_vp, C.POINTER(RadianceExParamsC), C.c_int64]),
     "mcpt_scene_query_route_rays": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "mcpt_ao_params_default": (None, [C.POINTER(AoParamsC)]),
+    "mcpt_ao_device": (C.c_int, [_vp, C.POINTER(AoParamsC), C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "mcpt_ao": (C.c_int, [_vp, C.POINTER(AoParamsC), C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                          C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(RenderStats)]),
+    "mcpt_render_ao_device": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(AoParamsC), _vp, _vp]),
+    "mcpt_render_ao": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(AoParamsC), C.POINTER(C.c_float),
+                                 C.POINTER(RenderStats)]),
+    "mcpt_scene_reserve_ao": (C.c_int, [_vp, C.c_int64]),
 }
 
 _lib = None

@@ -243,6 +243,13 @@ void mcpt_radiance_params_default(mcpt_radiance_params* p) {
     p->seed = 0x4D435054ull;                          // mcpt_render_params_default's
 }
 
+void mcpt_ao_params_default(mcpt_ao_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof *p);                     // radius unbounded, bias 0.01, everything else automatic
+    p->spp = 1;
+    p->seed = 0x4D435054ull;                          // mcpt_render_params_default's
+}
+
 void mcpt_radiance_ex_params_default(mcpt_radiance_ex_params* p) {
     if (!p) return;
     std::memset(p, 0, sizeof *p);                     // the megakernel; every wavefront field automatic

@@ -5,7 +5,7 @@
 //   scene_image.cpp   models, the device image, scene creation and teardown
 //   plan.cpp          the render plan, its workspace, mcpt_plan_query, shards
 //   render_host.cpp   renders: one device, several, reserve, variance, adaptive, feature buffers
-//   queries.cpp       ray and radiance queries
+//   queries.cpp       ray, radiance and ambient-occlusion queries
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types and prototypes only: librccl is loaded on first use (render_host.cpp rccl())
@@ -210,13 +210,16 @@ struct mcpt_scene {
     // record as mcpt_trace_stats_read last read it (mcpt_scene_query_route_rays)
     mcpt::host::DevBuf rad_wf_stats;
     uint64_t query_routes[mcpt::kQueryRoutes] = {};
+    // ambient-occlusion queries (mcpt_ao_device, mcpt_render_ao_device): one count of
+    // unoccluded samples per point or pixel (counters: rq_stats; stacks: ws.spill)
+    mcpt::host::DevBuf ao_counts;
 
     // every device buffer of the scene: what the destructor frees (a new buffer
     // is declared above and listed here)
     std::vector<mcpt::host::DevBuf*> buffers() {
         return {&d_image, &d_normals, &ws.partial, &ws.small, &ws.spill, &ws.fb, &ws.wf, &ws.tail, &gather, &gather_send,
                 &ad_list, &ad_flags, &ad_blocks, &rq_order, &rq_stats, &rad_partial, &rad_tail, &rad_small,
-                &rad_wf_stats};
+                &rad_wf_stats, &ao_counts};
     }
     ~mcpt_scene();   // scene_image.cpp
 };

@@ -1,12 +1,14 @@
 // queries.cpp -- the ray entries of the C ABI (include/mcpt.h): closest-hit and
 // any-hit queries over ray buffers (rayquery.hip), path-traced radiance over
 // ray buffers (render.hip radiance_kernel; on the wavefront pipeline as a ray
-// frame, wavefront_rays.hip), and mcpt_intersect on the older
-// closest-hit kernel the ray-query tests compare against.
+// frame, wavefront_rays.hip), ambient occlusion of point buffers and of a frame's
+// first hits (ao.hip), and mcpt_intersect on the older closest-hit kernel the
+// ray-query tests compare against.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 
+#include "ao_launch.hpp"
 #include "capi_internal.hpp"
 #include "rayquery_launch.hpp"
 
@@ -339,9 +341,232 @@ int radiance_device(mcpt_scene* s, const Radiance& R, const RadianceEx* wf, int6
     return MCPT_OK;
 }
 
+// ---- ambient-occlusion queries (ao.hip) ------------------------------------------
+// The checks of an AO query's own params, p resolved (NULL = the defaults) with its
+// zeros for radius and bias replaced
+mcpt_ao_params ao_fields(const mcpt_ao_params* p) {
+    mcpt_ao_params q;
+    mcpt_ao_params_default(&q);
+    if (p) q = *p;
+    if (q.spp == 0) throw mcpt::Error{MCPT_E_INVALID, "spp must be >= 1"};
+    if (uint64_t(q.spp_offset) + uint64_t(q.spp) > (uint64_t(1) << 32))
+        throw mcpt::Error{MCPT_E_INVALID, "spp_offset + spp must not pass 2^32"};
+    if (!(q.radius >= 0.0f)) throw mcpt::Error{MCPT_E_INVALID, "radius must be >= 0 (0 = FLT_MAX)"};
+    if (!(q.bias >= 0.0f) || !std::isfinite(q.bias))
+        throw mcpt::Error{MCPT_E_INVALID, "bias must be > 0 and finite (0 = 0.01)"};
+    if (q.lean != 0 && q.lean != 1) throw mcpt::Error{MCPT_E_INVALID, "lean must be 0 or 1"};
+    if (q.workgroups < 0) throw mcpt::Error{MCPT_E_INVALID, "workgroups must be >= 0"};
+    if (q.refill < 0 || q.refill > 64) throw mcpt::Error{MCPT_E_INVALID, "refill must be 0 (default) or 1..64"};
+    if (q.unit_samples < 0) throw mcpt::Error{MCPT_E_INVALID, "unit_samples must be >= 0"};
+    if (q.radius == 0.0f) q.radius = FLT_MAX;
+    if (q.bias == 0.0f) q.bias = 0.01f;
+    return q;
+}
+// The checks of the point form that need no device, in the header's order
+mcpt_ao_params ao_resolve(const mcpt_scene* s, const mcpt_ao_params* p, int64_t n, bool ptrs) {
+    if (!s) throw mcpt::Error{MCPT_E_INVALID, "NULL scene"};
+    if (n < 0) throw mcpt::Error{MCPT_E_INVALID, "n must be >= 0"};
+    if (n && !ptrs) throw mcpt::Error{MCPT_E_INVALID, "NULL point, normal or result buffer"};
+    const mcpt_ao_params q = ao_fields(p);
+    if (n >= (int64_t(1) << 31) / 3) throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many points for one call"};
+    if (!s->on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
+    return q;
+}
+// ... and of the pixel form: the frame's fields it reads, the AO params, what it does
+// not offer, the host-only scene.  The frame resolved: what make_plan reads of it and
+// no field the query ignores
+struct AoFrame {
+    mcpt_render_params rp;
+    mcpt_ao_params q;
+};
+AoFrame ao_frame_resolve(const mcpt_scene* s, const mcpt_render_params* rp, const mcpt_ao_params* ap, bool ptr) {
+    if (!s) throw mcpt::Error{MCPT_E_INVALID, "NULL scene"};
+    if (!rp) throw mcpt::Error{MCPT_E_INVALID, "render params is NULL"};
+    if (!ptr) throw mcpt::Error{MCPT_E_INVALID, "NULL result buffer"};
+    if (rp->width <= 0 || rp->height <= 0) throw mcpt::Error{MCPT_E_INVALID, "width/height must be positive"};
+    if (rp->spp == 0) throw mcpt::Error{MCPT_E_INVALID, "spp must be >= 1"};
+    if (uint64_t(rp->spp_offset) + uint64_t(rp->spp) > (uint64_t(1) << 32))
+        throw mcpt::Error{MCPT_E_INVALID, "spp_offset + spp must not pass 2^32"};
+    if (rp->tile > 256) throw mcpt::Error{MCPT_E_INVALID, "tile too large"};
+    if (rp->mode != MCPT_MODE_CVMCTRACER && rp->mode != MCPT_MODE_QUINENGINE)
+        throw mcpt::Error{MCPT_E_INVALID, "unknown mode"};
+    AoFrame F;
+    F.q = ao_fields(ap);
+    const uint64_t T = rp->tile > 0 ? rp->tile : 8;
+    const uint64_t padded = ((uint64_t(rp->width) + T - 1) / T) * ((uint64_t(rp->height) + T - 1) / T) * T * T;
+    if (uint64_t(rp->width) * uint64_t(rp->height) >= (uint64_t(1) << 31) / 3 || padded >= (uint64_t(1) << 31))
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many pixels for one call"};
+    if (rp->mode == MCPT_MODE_QUINENGINE)
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "ambient occlusion is not offered in QuinEngine mode"};
+    if (rp->shard_count > 1 || rp->packed)
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "ambient occlusion is not sharded: shard_count <= 1, packed = 0"};
+    if (!s->on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
+    mcpt_render_params_default(&F.rp);
+    F.rp.width = rp->width; F.rp.height = rp->height;
+    F.rp.spp = rp->spp; F.rp.spp_offset = rp->spp_offset;
+    F.rp.seed = rp->seed; F.rp.prev_count = rp->prev_count;
+    F.rp.fov_deg = rp->fov_deg;
+    for (int i = 0; i < 3; ++i) {
+        F.rp.eye[i] = rp->eye[i]; F.rp.dir[i] = rp->dir[i]; F.rp.up[i] = rp->up[i];
+    }
+    F.rp.tile = rp->tile;
+    F.rp.max_depth = 0;
+    F.rp.lean = F.q.lean;
+    return F;
+}
+
+// What the AO queries need on the scene's (current) device for `points` points or
+// pixels: the ray queries' (ensure_rays) and one count each.  Nothing once they exist.
+void ensure_ao(mcpt_scene& s, uint64_t points, bool capturing) {
+    if (capturing && (!s.rq_order.p || !s.rq_stats.p || !s.ao_counts.p))
+        throw mcpt::Error{MCPT_E_NOMEM, "the first ambient-occlusion query of a scene allocates: call "
+                                        "mcpt_scene_reserve_ao before capturing a graph"};
+    ensure_rays(s, capturing);
+    if (!s.ao_counts.p) HIP_TRY(mcpt::prepare_ao(s.gpu));   // (the kernels' code object loaded now)
+    grow_ws(s, s.ao_counts, static_cast<size_t>(std::max<uint64_t>(points, 1)) * 4, capturing);
+}
+
+// One query on st over a filled a.kp (a.p, a.nrm, a.stream, a.out, a.points, a.out_n, a.pixel set)
+void ao_async(mcpt_scene& s, const mcpt_ao_params& q, mcpt::AoParams& a, bool host_block, hipStream_t st) {
+    ensure_ao(s, a.out_n, stream_capturing(st));   // (counts are indexed as the output is)
+    const mcpt::AoUnits u = mcpt::ao_units(a.points, a.kp.spp, static_cast<uint32_t>(q.unit_samples));
+    a.unit = u.unit;
+    a.upp = u.upp;
+    a.div_upp = mcpt::FastDiv::make(u.upp);
+    a.total_units = static_cast<uint32_t>(uint64_t(a.points) * u.upp);
+    a.counts = static_cast<uint32_t*>(s.ao_counts.p);
+    a.spill = static_cast<uint4*>(s.ws.spill.p);
+    a.spill_stride = static_cast<uint32_t>(launched_lanes(s));
+    a.stats = host_block ? query_blocks(s)->host : query_blocks(s)->device;
+    a.refill = q.refill;
+    a.radius = q.radius;
+    a.bias = q.bias;
+    HIP_TRY(mcpt::launch_ao(a, q.lean != 0, s.cus, q.workgroups, st));
+}
+
+void ao_points_async(mcpt_scene& s, const mcpt_ao_params& q, int64_t n, const float* d_p, const float* d_n,
+                     const uint32_t* d_stream, float* d_ao, bool host_block, hipStream_t st) {
+    mcpt::AoParams a{};
+    a.kp.scene = s.gpu;
+    a.kp.spp = q.spp;
+    a.kp.spp_offset = q.spp_offset;
+    a.kp.prev_count = q.prev_count;
+    a.kp.key = tea16(static_cast<uint32_t>(q.seed), static_cast<uint32_t>(q.seed >> 32));
+    a.p = d_p;
+    a.nrm = d_n;
+    a.stream = d_stream;
+    a.out = d_ao;
+    a.points = a.out_n = static_cast<uint32_t>(n);
+    a.pixel = 0;
+    ao_async(s, q, a, host_block, st);
+}
+
+void ao_frame_async(mcpt_scene& s, const AoFrame& F, float* d_ao, bool host_block, hipStream_t st) {
+    mcpt::AoParams a{};
+    a.kp = make_plan(s, &F.rp).kp;        // (one shard, whole tiles, CVMCTracer mode: ao_frame_resolve)
+    a.out = d_ao;
+    a.points = a.kp.npix_local;
+    a.out_n = static_cast<uint32_t>(F.rp.width) * static_cast<uint32_t>(F.rp.height);
+    a.pixel = 1;
+    ao_async(s, F.q, a, host_block, st);
+}
+
 }  // namespace
 
 extern "C" {
+
+int mcpt_ao_device(mcpt_scene* s, const mcpt_ao_params* p, int64_t n, const float* d_p, const float* d_n,
+                   const uint32_t* d_stream, float* d_ao, void* hip_stream) {
+    return guarded([&]() -> int {
+        const mcpt_ao_params q = ao_resolve(s, p, n, d_p && d_n && d_ao);
+        const size_t N = static_cast<size_t>(n);
+        if (ranges_overlap(d_ao, N * 4, d_p, N * 12) || ranges_overlap(d_ao, N * 4, d_n, N * 12) ||
+            ranges_overlap(d_ao, N * 4, d_stream, d_stream ? N * 4 : 0))
+            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+        if (!n) return MCPT_OK;
+        set_device(*s);                   // (a multi-device scene: devices[0], the primary)
+        ao_points_async(*s, q, n, d_p, d_n, d_stream, d_ao, false, static_cast<hipStream_t>(hip_stream));
+        return MCPT_OK;
+    });
+}
+
+// points, normals, stream ids and the result are staged in the scene's host-render buffer
+int mcpt_ao(mcpt_scene* s, const mcpt_ao_params* p, int64_t n, const float* p_xyz, const float* nrm,
+            const uint32_t* stream, float* ao, mcpt_render_stats* stats) {
+    return guarded([&]() -> int {
+        const mcpt_ao_params q = ao_resolve(s, p, n, p_xyz && nrm && ao);
+        const size_t N = static_cast<size_t>(n);
+        if (ranges_overlap(ao, N * 4, p_xyz, N * 12) || ranges_overlap(ao, N * 4, nrm, N * 12) ||
+            ranges_overlap(ao, N * 4, stream, stream ? N * 4 : 0))
+            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (n) {
+            set_device(*s);
+            const auto part = carve({N * 12, N * 12, N * 4, N * 4});
+            ensure_buf(s->ws.fb, part.total);
+            float* d_p = part.at<float>(s->ws.fb.p, 0);
+            float* d_n = part.at<float>(s->ws.fb.p, 1);
+            uint32_t* d_s = part.at<uint32_t>(s->ws.fb.p, 2);
+            float* d_ao = part.at<float>(s->ws.fb.p, 3);
+            HIP_TRY(hipMemcpy(d_p, p_xyz, N * 12, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_n, nrm, N * 12, hipMemcpyHostToDevice));
+            if (stream) HIP_TRY(hipMemcpy(d_s, stream, N * 4, hipMemcpyHostToDevice));
+            if (q.prev_count) HIP_TRY(hipMemcpy(d_ao, ao, N * 4, hipMemcpyHostToDevice));
+            ensure_rays(*s, false);       // (the counter blocks exist before the host entry's is cleared)
+            unsigned long long* blk = clear_host_block(*s);
+            ao_points_async(*s, q, n, d_p, d_n, stream ? d_s : nullptr, d_ao, true, nullptr);
+            HIP_TRY(hipStreamSynchronize(nullptr));
+            HIP_TRY(hipMemcpy(ao, d_ao, N * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(c, blk, sizeof c, hipMemcpyDeviceToHost));
+        }
+        if (stats) stats_from_counters(c, *stats);
+        return MCPT_OK;
+    });
+}
+
+int mcpt_render_ao_device(mcpt_scene* s, const mcpt_render_params* rp, const mcpt_ao_params* ap, float* d_ao,
+                          void* hip_stream) {
+    return guarded([&]() -> int {
+        const AoFrame F = ao_frame_resolve(s, rp, ap, d_ao != nullptr);
+        set_device(*s);                   // (a multi-device scene: devices[0], the primary)
+        ao_frame_async(*s, F, d_ao, false, static_cast<hipStream_t>(hip_stream));
+        return MCPT_OK;
+    });
+}
+
+// the result is staged in the scene's host-render buffer
+int mcpt_render_ao(mcpt_scene* s, const mcpt_render_params* rp, const mcpt_ao_params* ap, float* ao,
+                   mcpt_render_stats* stats) {
+    return guarded([&]() -> int {
+        const AoFrame F = ao_frame_resolve(s, rp, ap, ao != nullptr);
+        set_device(*s);
+        const size_t bytes = size_t(F.rp.width) * size_t(F.rp.height) * 4;
+        ensure_buf(s->ws.fb, bytes);
+        float* d_ao = static_cast<float*>(s->ws.fb.p);
+        if (F.rp.prev_count) HIP_TRY(hipMemcpy(d_ao, ao, bytes, hipMemcpyHostToDevice));
+        ensure_rays(*s, false);
+        unsigned long long* blk = clear_host_block(*s);
+        ao_frame_async(*s, F, d_ao, true, nullptr);
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        HIP_TRY(hipMemcpy(ao, d_ao, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c, blk, sizeof c, hipMemcpyDeviceToHost));
+        if (stats) stats_from_counters(c, *stats);
+        return MCPT_OK;
+    });
+}
+
+int mcpt_scene_reserve_ao(mcpt_scene* s, int64_t n) {
+    return guarded([&]() -> int {
+        if (!s || !s->on_device) return fail(MCPT_E_INVALID, "scene is not on a device");
+        if (n < 0) return fail(MCPT_E_INVALID, "n must be >= 0");
+        if (n >= (int64_t(1) << 31) / 3) return fail(MCPT_E_UNSUPPORTED, "too many points for one call");
+        DeviceGuard guard;
+        set_device(*s);
+        ensure_ao(*s, static_cast<uint64_t>(n), false);
+        return MCPT_OK;
+    });
+}
 
 int mcpt_intersect(mcpt_scene* s, int64_t n, const float* o, const float* d, float t_max, int32_t* tri_out,
                    float* hit_out, mcpt_render_stats* stats) {

@@ -549,6 +549,65 @@ class Scene:
         check(lib().mcpt_scene_query_route_rays(self.handle, out))
         return tuple(int(v) for v in out)
 
+    def ao_device(self, n: int, p_ptr: int, n_ptr: int, out_ptr: int, stream_ids_ptr: int = 0,
+                  stream_ptr: int = 0, **params):
+        """Ambient occlusion of n points in device memory (mcpt_ao_device), asynchronous on the
+        stream: p / normals (n, 3) float32, the normals unit length and used as given; out (n,)
+        float32 = the share of spp cosine-hemisphere rays of length ``radius`` from p + bias * dir
+        that reach nothing (1 = open), read first when prev_count > 0; stream ids (n,) uint32,
+        optional (the point's index), as ``radiance_device``.  Counted in integers: scheduling
+        never changes a bit.  params: the fields of ``ao_params``.  Counted in ``trace_stats``.
+        Run it on the stream of the scene's renders, or synchronize."""
+        check(lib().mcpt_ao_device(self.handle, C.byref(ao_params(**params)), int(n), C.c_void_p(p_ptr),
+                                   C.c_void_p(n_ptr), C.c_void_p(stream_ids_ptr), C.c_void_p(out_ptr),
+                                   C.c_void_p(stream_ptr)))
+
+    def ao(self, p: np.ndarray, normals: np.ndarray, stream_ids=None, prev=None, **params):
+        """Ambient occlusion of host points (mcpt_ao), synchronous: ((n,) float32, counters of this
+        call).  prev: the earlier mean the running mean continues (with prev_count > 0)."""
+        p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+        normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if p.shape != normals.shape:
+            raise McptError(-1, "p and normals must have the same shape")
+        n = p.shape[0]
+        ids = None
+        if stream_ids is not None:
+            ids = np.ascontiguousarray(stream_ids, np.uint32).reshape(-1)
+            if ids.shape[0] != n:
+                raise McptError(-1, "stream_ids must hold one value per point")
+        out = np.zeros(n, np.float32)
+        if prev is not None:
+            out[...] = np.asarray(prev, np.float32).reshape(n)
+        st = RenderStats()
+        check(lib().mcpt_ao(self.handle, C.byref(ao_params(**params)), n, _fptr(p), _fptr(normals),
+                            ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None, _fptr(out),
+                            C.byref(st)))
+        return out, st.as_dict()
+
+    def render_ao_device(self, params: RenderParams, out_ptr: int, stream_ptr: int = 0, **ao):
+        """Ambient occlusion at the first hits of a frame's own primary rays
+        (mcpt_render_ao_device), asynchronous: out (H, W) float32, 1 where a pixel's samples miss
+        the scene or see nothing within ``radius`` of their hits.  The frame, its samples, seed
+        and prev_count come from ``params``; ao: radius, lean, workgroups, refill, unit_samples."""
+        check(lib().mcpt_render_ao_device(self.handle, C.byref(params.to_c()), C.byref(ao_params(**ao)),
+                                          C.c_void_p(out_ptr), C.c_void_p(stream_ptr)))
+
+    def render_ao(self, params: RenderParams, prev: Optional[np.ndarray] = None, **ao):
+        """``render_ao_device`` into a host array (mcpt_render_ao), synchronous: ((H, W) float32,
+        counters of this call).  prev: the earlier mean (with ``params.prev_count > 0``)."""
+        out = np.zeros((int(params.height), int(params.width)), np.float32)
+        if prev is not None:
+            out[...] = np.asarray(prev, np.float32).reshape(out.shape)
+        st = RenderStats()
+        check(lib().mcpt_render_ao(self.handle, C.byref(params.to_c()), C.byref(ao_params(**ao)), _fptr(out),
+                                   C.byref(st)))
+        return out, st.as_dict()
+
+    def reserve_ao(self, n: int):
+        """Allocate what an ambient-occlusion query of n points, or of a frame of n pixels, needs
+        (mcpt_scene_reserve_ao): a later query that needs no more allocates nothing."""
+        check(lib().mcpt_scene_reserve_ao(self.handle, int(n)))
+
     def render_unit_counters(self, params: RenderParams):
         """Synchronous render returning (fb, per-unit counters (units, 4): rays, inner, leaf, tests)."""
         n = params.output_pixels()
@@ -763,6 +822,19 @@ def radiance_ex_params(**kw) -> "_capi.RadianceExParamsC":
             setattr(p, k, int(v))
         else:
             raise McptError(-1, f"unknown radiance parameter {k!r}")
+    return p
+
+
+def ao_params(**kw) -> "_capi.AoParamsC":
+    """mcpt_ao_params: the library's defaults (spp 1, the renders' seed, radius 0 = unbounded,
+    bias 0 = 0.01, everything else 0 = automatic), then the fields given by name."""
+    p = _capi.AoParamsC()
+    lib().mcpt_ao_params_default(C.byref(p))
+    names = {n for n, _ in _capi.AoParamsC._fields_}
+    for k, v in kw.items():
+        if k not in names:
+            raise McptError(-1, f"unknown ambient-occlusion parameter {k!r}")
+        setattr(p, k, float(v) if k in ("radius", "bias") else int(v))
     return p
 
 
