@@ -871,6 +871,109 @@ int mcpt_render_ao(mcpt_scene*, const mcpt_render_params* rp, const mcpt_ao_para
 /* allocate what a query of n points, or a frame of n pixels, needs (above) */
 int mcpt_scene_reserve_ao(mcpt_scene*, int64_t n_points_or_pixels);
 
+/* ---- direct-lighting queries: emitter light at points and at pixels ---- */
+/* The fourth query kind: for every point x with unit normal n, the cosine-weighted
+ * mean of the emitter radiance over the hemisphere about n (E / pi), estimated by
+ * area sampling of the scene's emitters.  A diffuse surface's direct radiance is Kd
+ * times the value (mcpt_render_aov's albedo); a render's diffuse scatter followed by a
+ * terminal query converges to the same quantity.  All device arithmetic is fp32, one
+ * rounding per operation, no contraction.  CVMCTracer mode.
+ * Light table, built by mcpt_scene_create* (host-only scenes too): a light triangle
+ * is a kd triangle id k whose geometry is an emitter (some Ka > 0) and whose area is
+ * above 0, in ascending kd id; v0, v1, v2 its fp32 vertices (mcpt_scene_copy_kd's).
+ * In double, no fused multiply-add: e1 = v1 - v0, e2 = v2 - v0, c = e1 x e2, len =
+ * sqrt((c.x*c.x + c.y*c.y) + c.z*c.z), a_k = 0.5 * len, ng_k = (float)(c / len);
+ * S_k = S_(k-1) + a_k in table order, A_tot = (float)S_last, cdf_k = (float)(S_k /
+ * S_last): the last entry is 1.0f exactly.  A uniform u selects j = min(#{k : cdf_k <=
+ * u}, L - 1): the first entry with u < cdf_j, or the last.
+ * One sample, from x, n, bias and an RNG state sd that has spent two draws:
+ * u0, u1, u2 = rng_next(sd); j from u0; su = sqrt(u1), beta = su * (1 - u2), gamma =
+ * su * u2; y = (v0 * (1 - beta - gamma) + v1 * beta) + v2 * gamma; w = y - x, r2 =
+ * dot(w, w), r = sqrt(r2), dir = w / r; cx = dot(n, dir), cy = |dot(ng_j, dir)|
+ * (emitters radiate from both sides, as in the renders).  Unless cx > 0, cy > 0 and
+ * r > 2 * bias the sample adds (0, 0, 0) and walks nothing.  Else the shadow ray has
+ * origin x + dir * bias, direction dir and t_max = r - 2 * bias, and is occluded iff
+ * mcpt_occluded_device answers 1 for it; an unoccluded sample adds g * (Ka[c] *
+ * illum) per channel c, Ka of triangle j's geometry, g = ((cx * cy) * A_tot) /
+ * (kPwPi * r2), kPwPi = 3.14159265359f.
+ * Accumulation (as the radiance queries): the samples are added in sample order
+ * inside chunks of spp_chunk (0 = spp), the chunk sums in chunk order from 0, the
+ * total divided by (float)spp; with prev_count > 0 the output is read first and (old *
+ * (float)prev_count + v) / (float)(prev_count + 1) written.  spp_chunk is part of the
+ * result's definition; workgroups, refill and the scene's layout never change a bit.
+ * Point form (mcpt_direct[_device]): points p_i, unit normals n_i (used as given),
+ * stream id id_i = d_stream[i], or i without d_stream.  Sample s: sd = rng_init(id_i,
+ * TEA16(seed), spp_offset + s), two uniforms drawn and dropped (a render's jitter, as
+ * mcpt_ao_device), then the sample above at x = p_i, n = n_i.
+ * Pixel form (mcpt_render_direct[_device]): sample s of pixel (px, py) is the render's
+ * primary ray of sample spp_offset + s (mcpt_render_aov's and mcpt_render_ao's) and
+ * its closest hit.  A miss adds zeros.  At a hit, whatever the material (emitters,
+ * glass and Phong alike; the material is not read): nrm the normalized shading
+ * normal, n = dot(d, nrm) > 0 ? -nrm : nrm, x = o + t * d, bias the literal 0.01, and
+ * the stream's next three draws go to the sample above.  The render params give the
+ * fields mcpt_render_ao_device reads; the direct params give spp_chunk, illum, lean,
+ * workgroups and refill: their spp, spp_offset, bias, seed and prev_count are checked
+ * and otherwise ignored.
+ * Checks, before anything is launched or allocated and in this order: MCPT_E_INVALID
+ * for a NULL scene, n < 0, a NULL required pointer with n > 0, a field out of range
+ * (the message names it; illum not finite, bias negative, NaN or infinite);
+ * MCPT_E_UNSUPPORTED for n (or width x height) >= 2^31 / 3, for n x chunks >= 2^31,
+ * and in the pixel form for QuinEngine mode, shard_count > 1 and packed;
+ * MCPT_E_INVALID for a host-only scene and for an output that overlaps an input.
+ * n = 0 is a no-op.  A scene without a light triangle launches no walk: zeros, or the
+ * running mean of zeros, are written.  A multi-device scene answers on devices[0].
+ * Not offered: QuinEngine mode, batches sharded over devices,
+ * multiple importance sampling with the BSDF, power- or distance-weighted light
+ * selection, use inside the renders' path loop.
+ * Counters (as the ambient-occlusion queries): the device entries add to the block
+ * mcpt_trace_stats_read reports, the host entries report their own call; the render
+ * stats are never touched.  paths = samples started, shades = samples that formed a
+ * shadow ray, rays = every ray walked (pixel form: primary and shadow rays); the
+ * traversal counters are the sum of the walks, and read 0 on a lean call.
+ * Workspace, the scene's: the renders' stack spill area (run the queries on the
+ * stream of the scene's renders, or synchronize), the ray queries' counter blocks,
+ * the light table (64 B and a cdf entry per light, uploaded with the scene) and, with
+ * more than one chunk, 16 B per (point or pixel, chunk).  After
+ * mcpt_scene_reserve_direct or a first call, a call that needs no more allocates
+ * nothing; growth on a capturing stream is MCPT_E_NOMEM before any launch.        */
+typedef struct {
+    uint32_t spp;          /* samples per point this call; >= 1 */
+    uint32_t spp_offset;   /* first global sample index; spp_offset + spp <= 2^32 */
+    uint32_t spp_chunk;    /* samples per partial sum; 0 = spp (one chunk); part of the result */
+    float    illum;        /* the emitters' scale (a render's illum); finite */
+    float    bias;         /* point form: shadow rays start at x + bias * dir; 0 = 0.01; >= 0, finite */
+    uint64_t seed;
+    uint32_t prev_count;   /* running mean over calls; the output is read when > 0 */
+    int32_t  lean;         /* 1: traversal counters compiled out (rays, paths, shades still counted) */
+    int32_t  workgroups;   /* scheduling only, as mcpt_trace_params */
+    int32_t  refill;       /* scheduling only, 0 or 1..64 */
+} mcpt_direct_params;
+void mcpt_direct_params_default(mcpt_direct_params*);   /* spp 1, illum 10, the renders' seed, rest 0 */
+
+/* The light table: returns the number of lights L; each pointer may be NULL.  kd_ids: L
+ * kd triangle ids, ascending; cdf: L floats; normals: L*3 floats; area_total: A_tot.
+ * Works on host-only scenes; 0 for a NULL scene. */
+int mcpt_scene_lights(const mcpt_scene*, int32_t* kd_ids, float* cdf, float* normals, float* area_total);
+
+/* d_p, d_n: n*3 floats each; d_stream: n stream ids or NULL; d_out: n*4 floats (r, g, b, 0), read first when
+ * p->prev_count > 0.  Asynchronous on hip_stream.  p may be NULL (the defaults). */
+int mcpt_direct_device(mcpt_scene*, const mcpt_direct_params* p, int64_t n, const float* d_p, const float* d_n,
+                       const uint32_t* d_stream, float* d_out, void* hip_stream);
+/* host arrays, synchronous; out: n*3 floats (read first when p->prev_count > 0); stats may be NULL (the counters
+ * of this call) */
+int mcpt_direct(mcpt_scene*, const mcpt_direct_params* p, int64_t n, const float* p_xyz, const float* nrm,
+                const uint32_t* stream, float* out, mcpt_render_stats* stats);
+/* d_out_rgba: width*height*4 floats (r, g, b, 0), row-major, read first when rp->prev_count > 0.  Asynchronous on
+ * hip_stream.  dp may be NULL (the defaults); rp may not. */
+int mcpt_render_direct_device(mcpt_scene*, const mcpt_render_params* rp, const mcpt_direct_params* dp,
+                              float* d_out_rgba, void* hip_stream);
+/* host array of width*height*3 floats, synchronous; stats may be NULL (the counters of this call) */
+int mcpt_render_direct(mcpt_scene*, const mcpt_render_params* rp, const mcpt_direct_params* dp, float* out,
+                       mcpt_render_stats* stats);
+/* allocate what a query of n points, or a frame of n pixels, with p's spp and spp_chunk needs (above); p may be
+ * NULL (one chunk) */
+int mcpt_scene_reserve_direct(mcpt_scene*, const mcpt_direct_params* p, int64_t n_points_or_pixels);
+
 #ifdef __cplusplus
 }
 #endif

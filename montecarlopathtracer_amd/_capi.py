@@ -130,6 +130,12 @@ class AoParamsC(C.Structure):
                 ("refill", C.c_int32), ("unit_samples", C.c_int32)]
 
 
+class DirectParamsC(C.Structure):
+    _fields_ = [("spp", C.c_uint32), ("spp_offset", C.c_uint32), ("spp_chunk", C.c_uint32), ("illum", C.c_float),
+                ("bias", C.c_float), ("seed", C.c_uint64), ("prev_count", C.c_uint32), ("lean", C.c_int32),
+                ("workgroups", C.c_int32), ("refill", C.c_int32)]
+
+
 TRACE_CLOSEST = 0
 TRACE_ANY = 1
 OBJ_CVMCTRACER = 0
@@ -253,6 +259,16 @@ _SIGS = {
     "mcpt_render_ao": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(AoParamsC), C.POINTER(C.c_float),
                                  C.POINTER(RenderStats)]),
     "mcpt_scene_reserve_ao": (C.c_int, [_vp, C.c_int64]),
+    "mcpt_direct_params_default": (None, [C.POINTER(DirectParamsC)]),
+    "mcpt_scene_lights": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_float)]),
+    "mcpt_direct_device": (C.c_int, [_vp, C.POINTER(DirectParamsC), C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "mcpt_direct": (C.c_int, [_vp, C.POINTER(DirectParamsC), C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                              C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(RenderStats)]),
+    "mcpt_render_direct_device": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(DirectParamsC), _vp, _vp]),
+    "mcpt_render_direct": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(DirectParamsC), C.POINTER(C.c_float),
+                                     C.POINTER(RenderStats)]),
+    "mcpt_scene_reserve_direct": (C.c_int, [_vp, C.POINTER(DirectParamsC), C.c_int64]),
 }
 
 _lib = None

@@ -250,6 +250,26 @@ void mcpt_ao_params_default(mcpt_ao_params* p) {
     p->seed = 0x4D435054ull;                          // mcpt_render_params_default's
 }
 
+void mcpt_direct_params_default(mcpt_direct_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof *p);                     // one chunk, bias 0.01, everything else automatic
+    p->spp = 1;
+    p->illum = 10.0f;                                 // mcpt_render_params_default's
+    p->seed = 0x4D435054ull;
+}
+
+// the scene's light table (built at creation, host-only scenes too)
+int mcpt_scene_lights(const mcpt_scene* s, int32_t* kd_ids, float* cdf, float* normals, float* area_total) {
+    if (!s) return 0;
+    const mcpt::LightTable& t = s->lights;
+    const size_t L = t.kd_ids.size();
+    if (kd_ids && L) std::memcpy(kd_ids, t.kd_ids.data(), L * 4);
+    if (cdf && L) std::memcpy(cdf, t.cdf.data(), L * 4);
+    if (normals && L) std::memcpy(normals, t.normals.data(), L * 12);
+    if (area_total) *area_total = t.area_total;
+    return static_cast<int>(L);
+}
+
 void mcpt_radiance_ex_params_default(mcpt_radiance_ex_params* p) {
     if (!p) return;
     std::memset(p, 0, sizeof *p);                     // the megakernel; every wavefront field automatic

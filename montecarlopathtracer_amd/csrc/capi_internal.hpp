@@ -5,7 +5,7 @@
 //   scene_image.cpp   models, the device image, scene creation and teardown
 //   plan.cpp          the render plan, its workspace, mcpt_plan_query, shards
 //   render_host.cpp   renders: one device, several, reserve, variance, adaptive, feature buffers
-//   queries.cpp       ray, radiance and ambient-occlusion queries
+//   queries.cpp       ray, radiance, ambient-occlusion and direct-lighting queries
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types and prototypes only: librccl is loaded on first use (render_host.cpp rccl())
@@ -213,13 +213,20 @@ struct mcpt_scene {
     // ambient-occlusion queries (mcpt_ao_device, mcpt_render_ao_device): one count of
     // unoccluded samples per point or pixel (counters: rq_stats; stacks: ws.spill)
     mcpt::host::DevBuf ao_counts;
+    // direct-lighting queries (mcpt_direct_device, mcpt_render_direct_device): the
+    // scene's light table (host_model.hpp; built for host-only scenes too), its device
+    // copy -- the records of direct_launch.hpp, then the cdf; null without lights --
+    // and one float4 per (point or pixel, chunk) of partial sums
+    mcpt::LightTable lights;
+    mcpt::host::DevBuf d_lights, dl_partial;
+    bool dl_prepared = false;           // the kernels' code object is loaded (ensure_direct)
 
     // every device buffer of the scene: what the destructor frees (a new buffer
     // is declared above and listed here)
     std::vector<mcpt::host::DevBuf*> buffers() {
         return {&d_image, &d_normals, &ws.partial, &ws.small, &ws.spill, &ws.fb, &ws.wf, &ws.tail, &gather, &gather_send,
                 &ad_list, &ad_flags, &ad_blocks, &rq_order, &rq_stats, &rad_partial, &rad_tail, &rad_small,
-                &rad_wf_stats, &ao_counts};
+                &rad_wf_stats, &ao_counts, &d_lights, &dl_partial};
     }
     ~mcpt_scene();   // scene_image.cpp
 };

@@ -499,6 +499,39 @@ int terminal_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes) {
 }
 
 // ---------------------------------------------------------------------------
+// Light table: the emitters' triangles as the direct-lighting queries sample them,
+// uniformly by area (host_model.hpp).  Every product and sum below is one double
+// operation (the build contracts nothing), so a restatement in double reproduces
+// the table bit for bit.
+void light_table(const HostScene& hs, LightTable& out) {
+    out = LightTable{};
+    std::vector<double> running;
+    double S = 0.0;
+    for (size_t k = 0; k < hs.kd_geom.size(); ++k) {
+        const Geometry& ge = hs.geoms[hs.kd_geom[k]];
+        if (!(ge.Ka.x > 0 || ge.Ka.y > 0 || ge.Ka.z > 0)) continue;
+        const float* v = &hs.kd_verts[9 * k];
+        double e1[3], e2[3];
+        for (int a = 0; a < 3; ++a) {
+            e1[a] = double(v[3 + a]) - double(v[a]);
+            e2[a] = double(v[6 + a]) - double(v[a]);
+        }
+        const double c[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
+                             e1[0] * e2[1] - e1[1] * e2[0]};
+        const double len = std::sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
+        const double area = 0.5 * len;
+        if (!(area > 0.0)) continue;
+        S = S + area;
+        running.push_back(S);
+        out.kd_ids.push_back(static_cast<int32_t>(k));
+        for (int a = 0; a < 3; ++a) out.normals.push_back(static_cast<float>(c[a] / len));
+    }
+    out.cdf.reserve(running.size());
+    for (double s : running) out.cdf.push_back(static_cast<float>(s / S));
+    out.area_total = static_cast<float>(S);
+}
+
+// ---------------------------------------------------------------------------
 // Miss cull: occluder boxes.  A secondary ray whose segment misses the box of
 // every triangle has no hit, so the shade that creates it may end the path at
 // once (trace_device.hpp scene_box_hits).  The boxes need no material

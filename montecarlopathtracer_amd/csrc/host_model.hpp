@@ -85,6 +85,20 @@ void build_host_scene(const ObjModel& m, HostScene& out, const char* kd_cache_di
 // every non-emitter has Ka == 0 exactly, every Kd and Ks is finite, and there
 // are 1..max_boxes emitter geometries -- else 0.
 int terminal_cull_boxes(const HostScene& hs, float (*boxes)[6], int max_boxes);
+// Light table (include/mcpt.h "direct-lighting queries"): the kd triangles of emitter
+// geometries (some Ka > 0) with an area above 0, in ascending kd id -- what the
+// direct-lighting queries sample.  Areas and normals are formed in double from the
+// fp32 vertices, e1 = v1 - v0, e2 = v2 - v0, c = e1 x e2, len = sqrt((c.x c.x + c.y c.y)
+// + c.z c.z), area = 0.5 len, normal = (float)(c / len); cdf[k] = (float)(S_k / S_last)
+// over the running sums S of the areas, so the last entry is 1.0f exactly;
+// area_total = (float)S_last.  A scene without emitters has an empty table.
+struct LightTable {
+    std::vector<int32_t> kd_ids;
+    std::vector<float> cdf;
+    std::vector<float> normals;       // 3 per light
+    float area_total = 0.0f;
+};
+void light_table(const HostScene& hs, LightTable& out);
 // Miss cull (render_launch.hpp "Miss cull"): at most max_boxes fp32 AABBs
 // (min xyz, max xyz; bounds are vertex coordinates, unrounded) such that every
 // KD triangle lies inside at least one of them, clustered bottom-up from one

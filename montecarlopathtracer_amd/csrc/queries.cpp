@@ -2,7 +2,8 @@
 // any-hit queries over ray buffers (rayquery.hip), path-traced radiance over
 // ray buffers (render.hip radiance_kernel; on the wavefront pipeline as a ray
 // frame, wavefront_rays.hip), ambient occlusion of point buffers and of a frame's
-// first hits (ao.hip), and mcpt_intersect on the older closest-hit kernel the
+// first hits (ao.hip), direct lighting of the same by area sampling of the scene's
+// light table (direct.hip), and mcpt_intersect on the older closest-hit kernel the
 // ray-query tests compare against.
 #include <algorithm>
 #include <cfloat>
@@ -10,6 +11,7 @@
 
 #include "ao_launch.hpp"
 #include "capi_internal.hpp"
+#include "direct_launch.hpp"
 #include "rayquery_launch.hpp"
 
 using namespace mcpt::host;
@@ -372,14 +374,18 @@ mcpt_ao_params ao_resolve(const mcpt_scene* s, const mcpt_ao_params* p, int64_t 
     if (!s->on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
     return q;
 }
-// ... and of the pixel form: the frame's fields it reads, the AO params, what it does
-// not offer, the host-only scene.  The frame resolved: what make_plan reads of it and
-// no field the query ignores
-struct AoFrame {
-    mcpt_render_params rp;
-    mcpt_ao_params q;
+// The checks of a pixel form (ambient occlusion, direct lighting), in the header's
+// order: the frame's fields it reads, the query's own params (fields(): they throw;
+// returns the query's lean flag and its chunks per pixel), what it does not offer
+// (`what` names the query), the host-only scene.  Returns the frame resolved: what
+// make_plan reads of it and no field the query ignores
+struct FrameQuery {
+    int32_t lean;
+    uint64_t chunks;
 };
-AoFrame ao_frame_resolve(const mcpt_scene* s, const mcpt_render_params* rp, const mcpt_ao_params* ap, bool ptr) {
+template <typename Fields>
+mcpt_render_params frame_resolve(const mcpt_scene* s, const mcpt_render_params* rp, bool ptr, const std::string& what,
+                                 Fields&& fields) {
     if (!s) throw mcpt::Error{MCPT_E_INVALID, "NULL scene"};
     if (!rp) throw mcpt::Error{MCPT_E_INVALID, "render params is NULL"};
     if (!ptr) throw mcpt::Error{MCPT_E_INVALID, "NULL result buffer"};
@@ -390,28 +396,42 @@ AoFrame ao_frame_resolve(const mcpt_scene* s, const mcpt_render_params* rp, cons
     if (rp->tile > 256) throw mcpt::Error{MCPT_E_INVALID, "tile too large"};
     if (rp->mode != MCPT_MODE_CVMCTRACER && rp->mode != MCPT_MODE_QUINENGINE)
         throw mcpt::Error{MCPT_E_INVALID, "unknown mode"};
-    AoFrame F;
-    F.q = ao_fields(ap);
+    const FrameQuery fq = fields();
     const uint64_t T = rp->tile > 0 ? rp->tile : 8;
     const uint64_t padded = ((uint64_t(rp->width) + T - 1) / T) * ((uint64_t(rp->height) + T - 1) / T) * T * T;
     if (uint64_t(rp->width) * uint64_t(rp->height) >= (uint64_t(1) << 31) / 3 || padded >= (uint64_t(1) << 31))
         throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many pixels for one call"};
+    if (padded * fq.chunks >= (uint64_t(1) << 31))
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many work units (pixels x chunks) for one call"};
     if (rp->mode == MCPT_MODE_QUINENGINE)
-        throw mcpt::Error{MCPT_E_UNSUPPORTED, "ambient occlusion is not offered in QuinEngine mode"};
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, what + " is not offered in QuinEngine mode"};
     if (rp->shard_count > 1 || rp->packed)
-        throw mcpt::Error{MCPT_E_UNSUPPORTED, "ambient occlusion is not sharded: shard_count <= 1, packed = 0"};
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, what + " is not sharded: shard_count <= 1, packed = 0"};
     if (!s->on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
-    mcpt_render_params_default(&F.rp);
-    F.rp.width = rp->width; F.rp.height = rp->height;
-    F.rp.spp = rp->spp; F.rp.spp_offset = rp->spp_offset;
-    F.rp.seed = rp->seed; F.rp.prev_count = rp->prev_count;
-    F.rp.fov_deg = rp->fov_deg;
+    mcpt_render_params F;
+    mcpt_render_params_default(&F);
+    F.width = rp->width; F.height = rp->height;
+    F.spp = rp->spp; F.spp_offset = rp->spp_offset;
+    F.seed = rp->seed; F.prev_count = rp->prev_count;
+    F.fov_deg = rp->fov_deg;
     for (int i = 0; i < 3; ++i) {
-        F.rp.eye[i] = rp->eye[i]; F.rp.dir[i] = rp->dir[i]; F.rp.up[i] = rp->up[i];
+        F.eye[i] = rp->eye[i]; F.dir[i] = rp->dir[i]; F.up[i] = rp->up[i];
     }
-    F.rp.tile = rp->tile;
-    F.rp.max_depth = 0;
-    F.rp.lean = F.q.lean;
+    F.tile = rp->tile;
+    F.max_depth = 0;
+    F.lean = fq.lean;
+    return F;
+}
+struct AoFrame {
+    mcpt_render_params rp;
+    mcpt_ao_params q;
+};
+AoFrame ao_frame_resolve(const mcpt_scene* s, const mcpt_render_params* rp, const mcpt_ao_params* ap, bool ptr) {
+    AoFrame F;
+    F.rp = frame_resolve(s, rp, ptr, "ambient occlusion", [&] {
+        F.q = ao_fields(ap);
+        return FrameQuery{F.q.lean, 1};
+    });
     return F;
 }
 
@@ -471,9 +491,240 @@ void ao_frame_async(mcpt_scene& s, const AoFrame& F, float* d_ao, bool host_bloc
     ao_async(s, F.q, a, host_block, st);
 }
 
+// ---- direct-lighting queries (direct.hip) -----------------------------------------
+// The checks of a direct-lighting query's own params, p resolved (NULL = the
+// defaults) with its zero bias replaced
+mcpt_direct_params direct_fields(const mcpt_direct_params* p) {
+    mcpt_direct_params q;
+    mcpt_direct_params_default(&q);
+    if (p) q = *p;
+    if (q.spp == 0) throw mcpt::Error{MCPT_E_INVALID, "spp must be >= 1"};
+    if (uint64_t(q.spp_offset) + uint64_t(q.spp) > (uint64_t(1) << 32))
+        throw mcpt::Error{MCPT_E_INVALID, "spp_offset + spp must not pass 2^32"};
+    if (!std::isfinite(q.illum)) throw mcpt::Error{MCPT_E_INVALID, "illum must be finite"};
+    if (!(q.bias >= 0.0f) || !std::isfinite(q.bias))
+        throw mcpt::Error{MCPT_E_INVALID, "bias must be > 0 and finite (0 = 0.01)"};
+    if (q.lean != 0 && q.lean != 1) throw mcpt::Error{MCPT_E_INVALID, "lean must be 0 or 1"};
+    if (q.workgroups < 0) throw mcpt::Error{MCPT_E_INVALID, "workgroups must be >= 0"};
+    if (q.refill < 0 || q.refill > 64) throw mcpt::Error{MCPT_E_INVALID, "refill must be 0 (default) or 1..64"};
+    if (q.bias == 0.0f) q.bias = 0.01f;
+    return q;
+}
+// samples per chunk and chunks per point of spp samples in chunks of spp_chunk (0 = spp)
+struct DirectChunks {
+    uint32_t chunk;
+    uint64_t chunks;
+};
+DirectChunks direct_chunks(uint32_t spp, uint32_t spp_chunk) {
+    const uint32_t chunk = spp_chunk ? (spp_chunk < spp ? spp_chunk : spp) : spp;
+    return DirectChunks{chunk, (uint64_t(spp) + chunk - 1) / chunk};
+}
+// The checks of the point form that need no device, in the header's order
+mcpt_direct_params direct_resolve(const mcpt_scene* s, const mcpt_direct_params* p, int64_t n, bool ptrs) {
+    if (!s) throw mcpt::Error{MCPT_E_INVALID, "NULL scene"};
+    if (n < 0) throw mcpt::Error{MCPT_E_INVALID, "n must be >= 0"};
+    if (n && !ptrs) throw mcpt::Error{MCPT_E_INVALID, "NULL point, normal or result buffer"};
+    const mcpt_direct_params q = direct_fields(p);
+    if (n >= (int64_t(1) << 31) / 3) throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many points for one call"};
+    if (uint64_t(n) * direct_chunks(q.spp, q.spp_chunk).chunks >= (uint64_t(1) << 31))
+        throw mcpt::Error{MCPT_E_UNSUPPORTED, "too many work units (points x chunks) for one call"};
+    if (!s->on_device) throw mcpt::Error{MCPT_E_INVALID, "scene was created host-only"};
+    return q;
+}
+// ... and of the pixel form (frame_resolve): the frame's samples in the direct params' chunks
+struct DirectFrame {
+    mcpt_render_params rp;
+    mcpt_direct_params q;
+};
+DirectFrame direct_frame_resolve(const mcpt_scene* s, const mcpt_render_params* rp, const mcpt_direct_params* dp,
+                                 bool ptr) {
+    DirectFrame F;
+    F.rp = frame_resolve(s, rp, ptr, "direct lighting", [&] {
+        F.q = direct_fields(dp);
+        return FrameQuery{F.q.lean, direct_chunks(rp->spp, F.q.spp_chunk).chunks};
+    });
+    return F;
+}
+
+// What the direct-lighting queries need on the scene's (current) device for `units`
+// (point or pixel, chunk) units of a query in `chunks` chunks: the ray queries'
+// (ensure_rays), the kernels, and with more than one chunk a partial sum per unit.
+// The light table came with the scene.  Nothing once they exist.
+void ensure_direct(mcpt_scene& s, uint64_t units, uint64_t chunks, bool capturing) {
+    if (capturing && (!s.rq_order.p || !s.rq_stats.p || !s.dl_prepared))
+        throw mcpt::Error{MCPT_E_NOMEM, "the first direct-lighting query of a scene allocates: call "
+                                        "mcpt_scene_reserve_direct before capturing a graph"};
+    ensure_rays(s, capturing);
+    if (!s.dl_prepared) {
+        HIP_TRY(mcpt::prepare_direct(s.gpu));         // (the kernels' code object loaded now)
+        s.dl_prepared = true;
+    }
+    if (chunks > 1) grow_ws(s, s.dl_partial, static_cast<size_t>(units) * 16, capturing);
+}
+
+// One query on st over a filled d.kp (d.p, d.nrm, d.stream, d.out, d.points, d.out_n, d.pixel, d.bias set)
+void direct_async(mcpt_scene& s, const mcpt_direct_params& q, mcpt::DirectParams& d, bool host_block,
+                  hipStream_t st) {
+    const DirectChunks ch = direct_chunks(d.kp.spp, q.spp_chunk);
+    // (partial sums are indexed as the output is: chunk x out_n + point)
+    ensure_direct(s, uint64_t(d.out_n) * ch.chunks, ch.chunks, stream_capturing(st));
+    d.chunk = ch.chunk;
+    d.chunks = static_cast<uint32_t>(ch.chunks);
+    d.div_chunks = mcpt::FastDiv::make(d.chunks);
+    d.total_units = static_cast<uint32_t>(uint64_t(d.points) * ch.chunks);
+    d.partial = static_cast<float4*>(s.dl_partial.p);
+    const size_t L = s.lights.kd_ids.size();
+    d.n_lights = static_cast<uint32_t>(L);
+    d.lights = static_cast<const float4*>(s.d_lights.p);
+    d.cdf = L ? static_cast<const float*>(s.d_lights.p) + L * (mcpt::kLightRecordBytes / 4) : nullptr;
+    d.area_total = s.lights.area_total;
+    d.illum = q.illum;
+    d.spill = static_cast<uint4*>(s.ws.spill.p);
+    d.spill_stride = static_cast<uint32_t>(launched_lanes(s));
+    d.stats = host_block ? query_blocks(s)->host : query_blocks(s)->device;
+    d.refill = q.refill;
+    HIP_TRY(mcpt::launch_direct(d, q.lean != 0, s.cus, q.workgroups, st));
+}
+
+void direct_points_async(mcpt_scene& s, const mcpt_direct_params& q, int64_t n, const float* d_p, const float* d_n,
+                         const uint32_t* d_stream, float* d_out, bool host_block, hipStream_t st) {
+    mcpt::DirectParams d{};
+    d.kp.scene = s.gpu;
+    d.kp.spp = q.spp;
+    d.kp.spp_offset = q.spp_offset;
+    d.kp.prev_count = q.prev_count;
+    d.kp.key = tea16(static_cast<uint32_t>(q.seed), static_cast<uint32_t>(q.seed >> 32));
+    d.p = d_p;
+    d.nrm = d_n;
+    d.stream = d_stream;
+    d.out = reinterpret_cast<float4*>(d_out);
+    d.points = d.out_n = static_cast<uint32_t>(n);
+    d.bias = q.bias;
+    d.pixel = 0;
+    direct_async(s, q, d, host_block, st);
+}
+
+void direct_frame_async(mcpt_scene& s, const DirectFrame& F, float* d_out, bool host_block, hipStream_t st) {
+    mcpt::DirectParams d{};
+    d.kp = make_plan(s, &F.rp).kp;        // (one shard, whole tiles, CVMCTracer mode: frame_resolve)
+    d.out = reinterpret_cast<float4*>(d_out);
+    d.points = d.kp.npix_local;
+    d.out_n = static_cast<uint32_t>(F.rp.width) * static_cast<uint32_t>(F.rp.height);
+    d.bias = 0.01f;                       // (the renders' literal)
+    d.pixel = 1;
+    direct_async(s, F.q, d, host_block, st);
+}
+
 }  // namespace
 
 extern "C" {
+
+int mcpt_direct_device(mcpt_scene* s, const mcpt_direct_params* p, int64_t n, const float* d_p, const float* d_n,
+                       const uint32_t* d_stream, float* d_out, void* hip_stream) {
+    return guarded([&]() -> int {
+        const mcpt_direct_params q = direct_resolve(s, p, n, d_p && d_n && d_out);
+        const size_t N = static_cast<size_t>(n);
+        if (ranges_overlap(d_out, N * 16, d_p, N * 12) || ranges_overlap(d_out, N * 16, d_n, N * 12) ||
+            ranges_overlap(d_out, N * 16, d_stream, d_stream ? N * 4 : 0))
+            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+        if (!n) return MCPT_OK;
+        set_device(*s);                   // (a multi-device scene: devices[0], the primary)
+        direct_points_async(*s, q, n, d_p, d_n, d_stream, d_out, false, static_cast<hipStream_t>(hip_stream));
+        return MCPT_OK;
+    });
+}
+
+// points, normals, stream ids and the result are staged in the scene's host-render buffer
+int mcpt_direct(mcpt_scene* s, const mcpt_direct_params* p, int64_t n, const float* p_xyz, const float* nrm,
+                const uint32_t* stream, float* out, mcpt_render_stats* stats) {
+    return guarded([&]() -> int {
+        const mcpt_direct_params q = direct_resolve(s, p, n, p_xyz && nrm && out);
+        const size_t N = static_cast<size_t>(n);
+        if (ranges_overlap(out, N * 12, p_xyz, N * 12) || ranges_overlap(out, N * 12, nrm, N * 12) ||
+            ranges_overlap(out, N * 12, stream, stream ? N * 4 : 0))
+            return fail(MCPT_E_INVALID, "the output buffer overlaps an input of the call");
+        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (n) {
+            set_device(*s);
+            const auto part = carve({N * 16, N * 12, N * 12, N * 4});
+            ensure_buf(s->ws.fb, part.total);
+            float* d_out = part.at<float>(s->ws.fb.p, 0);
+            float* d_p = part.at<float>(s->ws.fb.p, 1);
+            float* d_n = part.at<float>(s->ws.fb.p, 2);
+            uint32_t* d_s = part.at<uint32_t>(s->ws.fb.p, 3);
+            HIP_TRY(hipMemcpy(d_p, p_xyz, N * 12, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_n, nrm, N * 12, hipMemcpyHostToDevice));
+            if (stream) HIP_TRY(hipMemcpy(d_s, stream, N * 4, hipMemcpyHostToDevice));
+            std::vector<float> rgba(N * 4, 0.0f);
+            if (q.prev_count) {
+                rgb_to_rgba(out, N, rgba.data());
+                HIP_TRY(hipMemcpy(d_out, rgba.data(), N * 16, hipMemcpyHostToDevice));
+            }
+            ensure_rays(*s, false);       // (the counter blocks exist before the host entry's is cleared)
+            unsigned long long* blk = clear_host_block(*s);
+            direct_points_async(*s, q, n, d_p, d_n, stream ? d_s : nullptr, d_out, true, nullptr);
+            HIP_TRY(hipStreamSynchronize(nullptr));
+            HIP_TRY(hipMemcpy(rgba.data(), d_out, N * 16, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(c, blk, sizeof c, hipMemcpyDeviceToHost));
+            rgba_to_rgb(rgba.data(), N, out);
+        }
+        if (stats) stats_from_counters(c, *stats);
+        return MCPT_OK;
+    });
+}
+
+int mcpt_render_direct_device(mcpt_scene* s, const mcpt_render_params* rp, const mcpt_direct_params* dp,
+                              float* d_out_rgba, void* hip_stream) {
+    return guarded([&]() -> int {
+        const DirectFrame F = direct_frame_resolve(s, rp, dp, d_out_rgba != nullptr);
+        set_device(*s);                   // (a multi-device scene: devices[0], the primary)
+        direct_frame_async(*s, F, d_out_rgba, false, static_cast<hipStream_t>(hip_stream));
+        return MCPT_OK;
+    });
+}
+
+// the result is staged in the scene's host-render buffer
+int mcpt_render_direct(mcpt_scene* s, const mcpt_render_params* rp, const mcpt_direct_params* dp, float* out,
+                       mcpt_render_stats* stats) {
+    return guarded([&]() -> int {
+        const DirectFrame F = direct_frame_resolve(s, rp, dp, out != nullptr);
+        set_device(*s);
+        const size_t N = size_t(F.rp.width) * size_t(F.rp.height);
+        ensure_buf(s->ws.fb, N * 16);
+        float* d_out = static_cast<float*>(s->ws.fb.p);
+        std::vector<float> rgba(N * 4, 0.0f);
+        if (F.rp.prev_count) {
+            rgb_to_rgba(out, N, rgba.data());
+            HIP_TRY(hipMemcpy(d_out, rgba.data(), N * 16, hipMemcpyHostToDevice));
+        }
+        ensure_rays(*s, false);
+        unsigned long long* blk = clear_host_block(*s);
+        direct_frame_async(*s, F, d_out, true, nullptr);
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        HIP_TRY(hipMemcpy(rgba.data(), d_out, N * 16, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c, blk, sizeof c, hipMemcpyDeviceToHost));
+        rgba_to_rgb(rgba.data(), N, out);
+        if (stats) stats_from_counters(c, *stats);
+        return MCPT_OK;
+    });
+}
+
+int mcpt_scene_reserve_direct(mcpt_scene* s, const mcpt_direct_params* p, int64_t n) {
+    return guarded([&]() -> int {
+        if (!s || !s->on_device) return fail(MCPT_E_INVALID, "scene is not on a device");
+        if (n < 0) return fail(MCPT_E_INVALID, "n must be >= 0");
+        const mcpt_direct_params q = direct_fields(p);
+        const uint64_t chunks = direct_chunks(q.spp, q.spp_chunk).chunks;
+        if (n >= (int64_t(1) << 31) / 3) return fail(MCPT_E_UNSUPPORTED, "too many points for one call");
+        if (uint64_t(n) * chunks >= (uint64_t(1) << 31))
+            return fail(MCPT_E_UNSUPPORTED, "too many work units (points x chunks) for one call");
+        DeviceGuard guard;
+        set_device(*s);
+        ensure_direct(*s, std::max<uint64_t>(uint64_t(n), 1) * chunks, chunks, false);
+        return MCPT_OK;
+    });
+}
 
 int mcpt_ao_device(mcpt_scene* s, const mcpt_ao_params* p, int64_t n, const float* d_p, const float* d_n,
                    const uint32_t* d_stream, float* d_ao, void* hip_stream) {

@@ -290,8 +290,30 @@ void route_tables(const mcpt::HostScene& hs, const std::vector<uint32_t>& tri_or
             if (std::fabs(k) > t.cull_gain) t.cull_gain = std::fabs(k);
 }
 
-// device copies of the scene image and the shading normals on `device`
-void upload(mcpt_scene& s, int device, const std::vector<unsigned char>& image, const std::vector<float>& nrm) {
+// The light table as the direct-lighting kernels read it (direct_launch.hpp): one
+// 64-B record per light -- the kd triangle's vertices with the normal's components in
+// the fourth words, then the geometry's Ka -- and the cdf behind the records
+std::vector<float> light_image(const mcpt::HostScene& hs, const mcpt::LightTable& t) {
+    const size_t L = t.kd_ids.size();
+    std::vector<float> img(L * 16 + L, 0.0f);
+    for (size_t i = 0; i < L; ++i) {
+        const size_t k = static_cast<size_t>(t.kd_ids[i]);
+        const float* v = &hs.kd_verts[9 * k];
+        const mcpt::Geometry& ge = hs.geoms[hs.kd_geom[k]];
+        float* rec = &img[16 * i];
+        for (int j = 0; j < 3; ++j) {
+            for (int a = 0; a < 3; ++a) rec[4 * j + a] = v[3 * j + a];
+            rec[4 * j + 3] = t.normals[3 * i + j];
+        }
+        rec[12] = ge.Ka.x; rec[13] = ge.Ka.y; rec[14] = ge.Ka.z;
+        img[L * 16 + i] = t.cdf[i];
+    }
+    return img;
+}
+
+// device copies of the scene image, the shading normals and the light table on `device`
+void upload(mcpt_scene& s, int device, const std::vector<unsigned char>& image, const std::vector<float>& nrm,
+            const std::vector<float>& lights) {
     HIP_TRY(hipSetDevice(device));
     s.device = device;
     HIP_TRY(hipDeviceGetAttribute(&s.cus, hipDeviceAttributeMultiprocessorCount, s.device));
@@ -302,6 +324,11 @@ void upload(mcpt_scene& s, int device, const std::vector<unsigned char>& image, 
     HIP_TRY(hipMemcpy(s.d_normals.p, nrm.data(), nrm.size() * 4, hipMemcpyHostToDevice));
     s.gpu.image = static_cast<const unsigned char*>(s.d_image.p);
     s.gpu.normals = static_cast<const float4*>(s.d_normals.p);
+    if (!lights.empty()) {
+        HIP_TRY(hipMalloc(&s.d_lights.p, lights.size() * 4));
+        s.d_lights.bytes = lights.size() * 4;
+        HIP_TRY(hipMemcpy(s.d_lights.p, lights.data(), lights.size() * 4, hipMemcpyHostToDevice));
+    }
 }
 
 int scene_create_impl(const mcpt_model* m, mcpt_scene** out, bool device, const char* kd_cache_dir = nullptr,
@@ -319,7 +346,9 @@ int scene_create_impl(const mcpt_model* m, mcpt_scene** out, bool device, const 
         if (layout != MCPT_LAYOUT_AUTO && layout != MCPT_LAYOUT_GLOBAL) return fail(MCPT_E_INVALID, "unknown layout");
         build_image(*s, layout == MCPT_LAYOUT_GLOBAL);
         route_tables(s->hs, s->tri_order, s->tables);
+        mcpt::light_table(s->hs, s->lights);
         if (device) {
+            const std::vector<float> lights = light_image(s->hs, s->lights);
             const size_t nt = s->hs.kd_tris.size();
             std::vector<float> nrm(nt * 12, 0.0f);
             for (size_t k = 0; k < nt; ++k)          // image triangle order
@@ -329,13 +358,14 @@ int scene_create_impl(const mcpt_model* m, mcpt_scene** out, bool device, const 
             int cur = 0;
             HIP_TRY(hipGetDevice(&cur));
             const std::vector<int> devs = g_devices.empty() ? std::vector<int>{cur} : g_devices;
-            upload(*s, devs[0], s->image, nrm);
+            upload(*s, devs[0], s->image, nrm, lights);
             // replicas for the further devices: same image, own workspace and stream
             for (size_t i = 1; i < devs.size(); ++i) {
                 auto R = std::make_unique<mcpt_scene>();
                 R->gpu = s->gpu;
                 R->tables = s->tables;
-                upload(*R, devs[i], s->image, nrm);
+                R->lights = s->lights;
+                upload(*R, devs[i], s->image, nrm, lights);
                 HIP_TRY(hipStreamCreateWithFlags(&R->stream, hipStreamNonBlocking));
                 HIP_TRY(hipEventCreateWithFlags(&R->done, hipEventDisableTiming));
                 s->replicas.push_back(std::move(R));

@@ -608,6 +608,81 @@ class Scene:
         (mcpt_scene_reserve_ao): a later query that needs no more allocates nothing."""
         check(lib().mcpt_scene_reserve_ao(self.handle, int(n)))
 
+    def lights(self):
+        """The scene's light table (mcpt_scene_lights): the emitters' triangles the direct-lighting
+        queries sample, as a dict -- ``kd_ids`` (L,) int32 ascending, ``cdf`` (L,) float32 ending at
+        1.0, ``normals`` (L, 3) float32, ``area_total`` float.  Works on host-only scenes."""
+        n = lib().mcpt_scene_lights(self.handle, None, None, None, None)
+        ids = np.zeros(n, np.int32)
+        cdf = np.zeros(n, np.float32)
+        nrm = np.zeros((n, 3), np.float32)
+        area = C.c_float(0.0)
+        lib().mcpt_scene_lights(self.handle, ids.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(cdf), _fptr(nrm),
+                                C.byref(area))
+        return {"kd_ids": ids, "cdf": cdf, "normals": nrm, "area_total": np.float32(area.value)}
+
+    def direct_device(self, n: int, p_ptr: int, n_ptr: int, out_ptr: int, stream_ids_ptr: int = 0,
+                      stream_ptr: int = 0, **params):
+        """Direct lighting of n points in device memory (mcpt_direct_device), asynchronous on the
+        stream: p / normals (n, 3) float32, the normals unit length and used as given; out (n, 4)
+        float32 = (r, g, b, 0), the cosine-weighted mean of the emitter radiance over the point's
+        hemisphere (E / pi) from spp area samples of the scene's lights, read first when
+        prev_count > 0; stream ids (n,) uint32, optional (the point's index), as ``ao_device``.
+        ``spp_chunk`` is part of the result (the summation order); the scheduling fields never
+        change a bit.  params: the fields of ``direct_params``.  Counted in ``trace_stats``.  Run
+        it on the stream of the scene's renders, or synchronize."""
+        check(lib().mcpt_direct_device(self.handle, C.byref(direct_params(**params)), int(n), C.c_void_p(p_ptr),
+                                       C.c_void_p(n_ptr), C.c_void_p(stream_ids_ptr), C.c_void_p(out_ptr),
+                                       C.c_void_p(stream_ptr)))
+
+    def direct(self, p: np.ndarray, normals: np.ndarray, stream_ids=None, prev=None, **params):
+        """Direct lighting of host points (mcpt_direct), synchronous: ((n, 3) float32, counters of
+        this call).  prev: the earlier mean the running mean continues (with prev_count > 0)."""
+        p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+        normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if p.shape != normals.shape:
+            raise McptError(-1, "p and normals must have the same shape")
+        n = p.shape[0]
+        ids = None
+        if stream_ids is not None:
+            ids = np.ascontiguousarray(stream_ids, np.uint32).reshape(-1)
+            if ids.shape[0] != n:
+                raise McptError(-1, "stream_ids must hold one value per point")
+        out = np.zeros((n, 3), np.float32)
+        if prev is not None:
+            out[...] = np.asarray(prev, np.float32).reshape(n, 3)
+        st = RenderStats()
+        check(lib().mcpt_direct(self.handle, C.byref(direct_params(**params)), n, _fptr(p), _fptr(normals),
+                                ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None, _fptr(out),
+                                C.byref(st)))
+        return out, st.as_dict()
+
+    def render_direct_device(self, params: RenderParams, out_ptr: int, stream_ptr: int = 0, **direct):
+        """Direct lighting at the first hits of a frame's own primary rays
+        (mcpt_render_direct_device), asynchronous: out (H, W, 4) float32 = (r, g, b, 0), zeros
+        where a pixel's samples miss the scene; times ``render_aov``'s albedo it is a diffuse
+        surface's direct radiance.  The frame, its samples, seed and prev_count come from
+        ``params``; direct: spp_chunk, illum, lean, workgroups, refill."""
+        check(lib().mcpt_render_direct_device(self.handle, C.byref(params.to_c()), C.byref(direct_params(**direct)),
+                                              C.c_void_p(out_ptr), C.c_void_p(stream_ptr)))
+
+    def render_direct(self, params: RenderParams, prev: Optional[np.ndarray] = None, **direct):
+        """``render_direct_device`` into a host array (mcpt_render_direct), synchronous: ((H, W, 3)
+        float32, counters of this call).  prev: the earlier mean (with ``params.prev_count > 0``)."""
+        out = np.zeros((int(params.height), int(params.width), 3), np.float32)
+        if prev is not None:
+            out[...] = np.asarray(prev, np.float32).reshape(out.shape)
+        st = RenderStats()
+        check(lib().mcpt_render_direct(self.handle, C.byref(params.to_c()), C.byref(direct_params(**direct)),
+                                       _fptr(out), C.byref(st)))
+        return out, st.as_dict()
+
+    def reserve_direct(self, n: int, **params):
+        """Allocate what a direct-lighting query of n points, or of a frame of n pixels, with these
+        params' spp and spp_chunk needs (mcpt_scene_reserve_direct): a later query that needs no
+        more allocates nothing."""
+        check(lib().mcpt_scene_reserve_direct(self.handle, C.byref(direct_params(**params)), int(n)))
+
     def render_unit_counters(self, params: RenderParams):
         """Synchronous render returning (fb, per-unit counters (units, 4): rays, inner, leaf, tests)."""
         n = params.output_pixels()
@@ -835,6 +910,19 @@ def ao_params(**kw) -> "_capi.AoParamsC":
         if k not in names:
             raise McptError(-1, f"unknown ambient-occlusion parameter {k!r}")
         setattr(p, k, float(v) if k in ("radius", "bias") else int(v))
+    return p
+
+
+def direct_params(**kw) -> "_capi.DirectParamsC":
+    """mcpt_direct_params: the library's defaults (spp 1, illum 10, the renders' seed, spp_chunk 0 =
+    one chunk, bias 0 = 0.01, everything else 0 = automatic), then the fields given by name."""
+    p = _capi.DirectParamsC()
+    lib().mcpt_direct_params_default(C.byref(p))
+    names = {n for n, _ in _capi.DirectParamsC._fields_}
+    for k, v in kw.items():
+        if k not in names:
+            raise McptError(-1, f"unknown direct-lighting parameter {k!r}")
+        setattr(p, k, float(v) if k in ("illum", "bias") else int(v))
     return p
 
 
