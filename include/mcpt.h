@@ -533,6 +533,63 @@ int mcpt_denoise_var_device(const mcpt_denoise_var_params* p, const float* d_col
                             const float* d_albedo_cov, const float* d_normal_depth, float* d_out_rgba,
                             float* d_scratch_rgba, void* hip_stream);
 
+/* ---- temporal accumulation --------------------------------------------------- */
+/* The temporal half of that filter, between "render" and "denoise": a frame's
+ * history reprojected onto a new camera.  (Additions; the ABI stays 9.)  For
+ * every pixel of the new frame (camera cur) the surface point its features
+ * give -- the pixel centre's ray at the mean hit distance normal_depth.w /
+ * coverage -- is projected into the previous frame (camera prev); the
+ * accumulated colour, history length N and variance are fetched there
+ * bilinearly from the taps that show the same surface (the previous frame's
+ * features: coverage > 0, normals and depth within the two tolerances below),
+ * from the valid pixels of the 3x3 block around the nearest pixel if no
+ * bilinear tap is one, and blended with this frame:
+ *   Ne = min(N, max_history - 1)
+ *   out     = ((hist Ne + colour) / (Ne + 1), Ne + 1)
+ *   out_var = ((hist_var Ne Ne + var) / (Ne + 1)^2, 0)
+ * the renders' running mean and mcpt_render_var's merge.  A pixel that hit
+ * nothing, whose point lies behind or outside the previous frame or finds no
+ * valid tap is reset: out = (colour, 1), out_var = (var, 0); out.w == 1 marks
+ * it.  fp32 in a fixed operation order.  Static
+ * geometry only; the caller ping-pongs: this call's outputs and this frame's
+ * feature buffers are the next call's history.  0 in a field = its default.   */
+typedef struct {
+    int32_t max_history;      /* cap on a pixel's history length; 0 = 32; 1..65536.  1 = no accumulation */
+    float   normal_threshold; /* a tap is the same surface if dot(n_p, n_q) >= thr * (cov_p * cov_q); 0 = 0.9; (0, 1] */
+    float   sigma_z;          /* ... and |e - z_q| <= sigma_z * max(e, z_q), e the depth expected there;
+                                 0 = 0.1 (mcpt_denoise's default); > 0, finite */
+    int32_t gamma_space;      /* 1: d_color is gamma-2.2 encoded (a QuinEngine-mode framebuffer): decoded on read.
+                                 History and outputs are always linear */
+} mcpt_temporal_params;
+/* the defaults spelled out: 32, 0.9, 0.1, 0 */
+void mcpt_temporal_params_default(mcpt_temporal_params*);
+/* Device buffers, row-major, 4 floats per pixel, asynchronous on hip_stream, no
+ * allocation (capturable in a graph, as mcpt_denoise_device).  This frame:
+ * d_color_rgba (alpha ignored), d_var_rgba (of mcpt_render_var), d_albedo_cov
+ * and d_normal_depth (of mcpt_render_aov).  History: d_hist_color_n (r g b N),
+ * d_hist_var and the previous frame's two feature buffers.  d_var_rgba,
+ * d_hist_var and d_out_var are given together or all NULL (no variance is
+ * carried); tp may be NULL (the defaults).  Of cur and prev only width,
+ * height, fov_deg, eye, dir, up and mode are read; width, height and mode must
+ * be equal in both.  Checks, before any launch and in this order:
+ * MCPT_E_INVALID for a NULL required pointer, a field of tp out of range (the
+ * message names it), width or height <= 0, an unknown mode, cur and prev
+ * mismatched (the message names the field), the variance pointers given
+ * partially; MCPT_E_UNSUPPORTED for width x height >= 2^31 / 3; MCPT_E_INVALID
+ * for an output that overlaps an input or the other output.                  */
+int mcpt_temporal_device(const mcpt_temporal_params* tp, const mcpt_render_params* cur, const mcpt_render_params* prev,
+                         const float* d_color_rgba, const float* d_var_rgba, const float* d_albedo_cov,
+                         const float* d_normal_depth, const float* d_hist_color_n, const float* d_hist_var,
+                         const float* d_hist_albedo_cov, const float* d_hist_normal_depth, float* d_out_color_n,
+                         float* d_out_var, void* hip_stream);
+/* The same on host arrays, synchronous, on the current device; colour in and
+ * out 4 floats per pixel here too (the alpha of hist_color_n and out_color_n
+ * carries N).  Every check comes before anything is staged.                   */
+int mcpt_temporal(const mcpt_temporal_params* tp, const mcpt_render_params* cur, const mcpt_render_params* prev,
+                  const float* color_rgba, const float* var_rgba, const float* albedo_cov, const float* normal_depth,
+                  const float* hist_color_n, const float* hist_var, const float* hist_albedo_cov,
+                  const float* hist_normal_depth, float* out_color_n, float* out_var);
+
 /* ---- variance-driven adaptive sampling -------------------------------------- */
 /* Passes of p->spp samples, each pass only over the pixels that are still
  * noisy.  Pass 0 is mcpt_render_var of p for every pixel.  Before pass j >= 1

@@ -14,7 +14,8 @@ from .tracer import (ILLUM, IMG_HEIGHT, IMG_WIDTH, NUM_KERNELS, NUM_SAMPLES_PER_
                      DestroyGeometry, Initialize, ObjModel, RenderParams, RenderScene, Scene, Tracer,
                      adaptive_params, ao_params, denoise,
                      denoise_device, denoise_params, denoise_var, denoise_var_device, denoise_var_params,
-                     direct_params, encode_8bit, radiance_ex_params, radiance_params, trace_params)
+                     direct_params, encode_8bit, radiance_ex_params, radiance_params, temporal, temporal_device,
+                     temporal_params, trace_params)
 
 lib()
 
@@ -22,4 +23,5 @@ __all__ = ["McptError", "ObjModel", "RenderParams", "Scene", "Tracer", "Initiali
            "DestroyGeometry", "RenderScene", "encode_8bit", "scene_path", "IMG_WIDTH", "IMG_HEIGHT",
            "NUM_KERNELS", "NUM_SAMPLES_PER_KERNEL", "ILLUM", "write_png", "read_png", "write_pfm", "read_pfm",
            "denoise", "denoise_device", "denoise_params", "denoise_var", "denoise_var_device", "denoise_var_params",
-           "adaptive_params", "ao_params", "direct_params", "trace_params", "radiance_params", "radiance_ex_params"]
+           "adaptive_params", "ao_params", "direct_params", "trace_params", "radiance_params", "radiance_ex_params",
+           "temporal", "temporal_device", "temporal_params"]

@@ -19,7 +19,7 @@ LIB = os.path.join(LIBDIR, os.environ.get("MCPT_LIB_NAME", "libmcpt.so"))
 SOURCES = ["host_model.cpp", "kd_cache.cpp", "capi.cpp", "scene_image.cpp", "plan.cpp", "render_host.cpp", "queries.cpp",
            "render.hip", "wavefront.hip", "wavefront_primary.hip", "wavefront_primary_shade.hip",
            "wavefront_sphere.hip", "wavefront_rays.hip", "aov.hip", "denoise.hip", "variance.hip", "denoise_var.hip", "adaptive.hip", "rayquery.hip", "ao.hip",
-           "direct.hip"]
+           "direct.hip", "temporal.hip"]
 # per-source code generation (wavefront_primary.hip: the bounce-0 packet extend's
 # wave-uniform control flow as scalar branches; render.hip: GVN hoisting,
 # megakernel +1.4%, no effect on the wavefront kernels, and the global-memory
@@ -49,7 +49,7 @@ SOURCE_FLAGS = {"wavefront_primary.hip": ["-mllvm", "-structurizecfg-skip-unifor
 # A/B variable, does not reach such a source -- any other scheduler gives it scratch)
 SOURCE_SCHED = {"wavefront_primary_shade.hip": "iterative-minreg"}
 HEADERS = ["capi_internal.hpp", "staging.hpp", "host_model.hpp", "mcpt_device.hpp", "render_launch.hpp", "stat_blocks.hpp", "wf_route.hpp", "trace_device.hpp", "half_box.hpp",
-           "aov_device.hpp", "aov_launch.hpp", "variance_launch.hpp", "adaptive_launch.hpp", "partial_sum.hpp", "rayquery_launch.hpp", "ao_launch.hpp", "direct_launch.hpp",
+           "aov_device.hpp", "aov_launch.hpp", "variance_launch.hpp", "adaptive_launch.hpp", "partial_sum.hpp", "rayquery_launch.hpp", "ao_launch.hpp", "direct_launch.hpp", "temporal_launch.hpp",
            "wf_device.hpp", "wf_extend_body.hpp", "wf_primary_body.hpp", "wf_primary_walk.hpp", "wf_primary_pairs.hpp", "wf_primary_shade_body.hpp", "wf_shade_item.hpp"]
 ARCH = os.environ.get("MCPT_OFFLOAD_ARCH", "gfx950")
 

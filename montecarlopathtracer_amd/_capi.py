@@ -101,6 +101,11 @@ class DenoiseVarParamsC(C.Structure):
     _fields_ = [("base", DenoiseParamsC), ("sigma_l", C.c_float)]
 
 
+class TemporalParamsC(C.Structure):
+    _fields_ = [("max_history", C.c_int32), ("normal_threshold", C.c_float), ("sigma_z", C.c_float),
+                ("gamma_space", C.c_int32)]
+
+
 class AdaptiveParamsC(C.Structure):
     _fields_ = [("max_passes", C.c_int32), ("min_passes", C.c_int32), ("threshold", C.c_float),
                 ("lum_floor", C.c_float), ("dilate", C.c_int32), ("force_list", C.c_int32)]
@@ -220,6 +225,11 @@ _SIGS = {
     "mcpt_denoise_var": (C.c_int, [C.POINTER(DenoiseVarParamsC), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                    C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mcpt_denoise_var_device": (C.c_int, [C.POINTER(DenoiseVarParamsC), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcpt_temporal_params_default": (None, [C.POINTER(TemporalParamsC)]),
+    "mcpt_temporal": (C.c_int, [C.POINTER(TemporalParamsC), C.POINTER(RenderParamsC), C.POINTER(RenderParamsC)]
+                      + [C.POINTER(C.c_float)] * 10),
+    "mcpt_temporal_device": (C.c_int, [C.POINTER(TemporalParamsC), C.POINTER(RenderParamsC), C.POINTER(RenderParamsC)]
+                             + [_vp] * 11),
     "mcpt_adaptive_params_default": (None, [C.POINTER(AdaptiveParamsC)]),
     "mcpt_render_adaptive": (C.c_int, [_vp, C.POINTER(RenderParamsC), C.POINTER(AdaptiveParamsC),
                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),

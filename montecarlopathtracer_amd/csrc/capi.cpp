@@ -1,7 +1,8 @@
 // capi.cpp -- what the C ABI declared in include/mcpt.h keeps per thread and
 // per call rather than per scene: the last error, device selection (the
 // reference's Initialize(), CVMCTracer/CUDA/CUTracer.cu:220-223), the parameter
-// defaults and the two denoisers.  Unlike the reference, no module globals hold
+// defaults, the two denoisers and the temporal accumulation in front of them.
+// Unlike the reference, no module globals hold
 // a scene: every call takes the opaque handle it works on (capi_internal.hpp
 // lists the units that implement the rest).
 #include <algorithm>
@@ -9,6 +10,7 @@
 
 #include "aov_launch.hpp"
 #include "capi_internal.hpp"
+#include "temporal_launch.hpp"
 #include "variance_launch.hpp"
 
 namespace mcpt::host {
@@ -109,6 +111,82 @@ int denoise_on_host(const mcpt::DenoiseVarParams& d, const float* color_rgb, con
     HIP_TRY(hipMemcpy(rgba.data(), c.at<float>(buf.p, 4), bytes, hipMemcpyDeviceToHost));
     rgba_to_rgb(rgba.data(), npx, out_rgb);
     return MCPT_OK;
+}
+
+// The buffers of a temporal accumulation, device or host: 4 floats per pixel each
+struct TemporalBufs {
+    const float *color, *var, *albedo_cov, *normal_depth;
+    const float *hist_color_n, *hist_var, *hist_albedo_cov, *hist_normal_depth;
+    float *out_color_n, *out_var;
+};
+
+// Every check of mcpt_temporal / mcpt_temporal_device in the header's order (nothing
+// is launched, staged or allocated before it returns); then the kernel's parameters,
+// mcpt_temporal_params' zeros replaced by the defaults.  Throws on a failed check
+mcpt::TemporalParams temporal_resolve(const mcpt_temporal_params* tp, const mcpt_render_params* cur,
+                                      const mcpt_render_params* prev, const TemporalBufs& b) {
+    using mcpt::Error;
+    if (!cur || !prev || !b.color || !b.albedo_cov || !b.normal_depth || !b.hist_color_n || !b.hist_albedo_cov ||
+        !b.hist_normal_depth || !b.out_color_n)
+        throw Error{MCPT_E_INVALID, "NULL argument"};
+    mcpt_temporal_params t;
+    mcpt_temporal_params_default(&t);
+    if (tp) {
+        if (tp->max_history < 0 || tp->max_history > 65536)
+            throw Error{MCPT_E_INVALID, "max_history must be 0 (default 32) or 1..65536"};
+        if (!(tp->normal_threshold >= 0.0f && tp->normal_threshold <= 1.0f))
+            throw Error{MCPT_E_INVALID, "normal_threshold must be 0 (default 0.9) or in (0, 1]"};
+        if (!(tp->sigma_z >= 0.0f) || !std::isfinite(tp->sigma_z))
+            throw Error{MCPT_E_INVALID, "sigma_z must be finite and >= 0 (0 = default 0.1)"};
+        if (tp->gamma_space != 0 && tp->gamma_space != 1) throw Error{MCPT_E_INVALID, "gamma_space must be 0 or 1"};
+        if (tp->max_history) t.max_history = tp->max_history;
+        if (tp->normal_threshold != 0.0f) t.normal_threshold = tp->normal_threshold;
+        if (tp->sigma_z != 0.0f) t.sigma_z = tp->sigma_z;
+        t.gamma_space = tp->gamma_space;
+    }
+    if (cur->width <= 0 || cur->height <= 0) throw Error{MCPT_E_INVALID, "width/height must be positive"};
+    if (cur->mode != MCPT_MODE_CVMCTRACER && cur->mode != MCPT_MODE_QUINENGINE)
+        throw Error{MCPT_E_INVALID, "unknown mode"};
+    if (prev->width != cur->width) throw Error{MCPT_E_INVALID, "cur and prev differ in width"};
+    if (prev->height != cur->height) throw Error{MCPT_E_INVALID, "cur and prev differ in height"};
+    if (prev->mode != cur->mode) throw Error{MCPT_E_INVALID, "cur and prev differ in mode"};
+    const int nvar = (b.var != nullptr) + (b.hist_var != nullptr) + (b.out_var != nullptr);
+    if (nvar != 0 && nvar != 3)
+        throw Error{MCPT_E_INVALID, "var, hist_var and out_var must be given together or all be NULL"};
+    const uint64_t npx = uint64_t(cur->width) * uint64_t(cur->height);
+    if (npx >= (uint64_t(1) << 31) / 3) throw Error{MCPT_E_UNSUPPORTED, "width x height must be below 2^31 / 3"};
+    const size_t bytes = size_t(npx) * 16;
+    const void* ins[] = {b.color, b.var, b.albedo_cov, b.normal_depth, b.hist_color_n, b.hist_var, b.hist_albedo_cov,
+                         b.hist_normal_depth};
+    for (const void* out : {static_cast<const void*>(b.out_color_n), static_cast<const void*>(b.out_var)}) {
+        if (!out) continue;
+        for (const void* in : ins)
+            if (in && ranges_overlap(out, bytes, in, bytes))
+                throw Error{MCPT_E_INVALID, "an output overlaps an input"};
+    }
+    if (b.out_var && ranges_overlap(b.out_color_n, bytes, b.out_var, bytes))
+        throw Error{MCPT_E_INVALID, "the two outputs overlap"};
+
+    mcpt::TemporalParams k{};
+    k.width = cur->width; k.height = cur->height;
+    k.mode = cur->mode;
+    k.gamma_space = t.gamma_space;
+    k.max_n = static_cast<float>(t.max_history - 1);
+    k.normal_threshold = t.normal_threshold;
+    k.sigma_z = t.sigma_z;
+    k.Wf = static_cast<float>(cur->width);
+    k.Hf = static_cast<float>(cur->height);
+    k.hw = k.Hf / k.Wf;
+    k.cur = camera_consts(*cur);
+    k.prev = camera_consts(*prev);
+    return k;
+}
+
+hipError_t temporal_launch(const mcpt::TemporalParams& k, const TemporalBufs& b, hipStream_t st) {
+    auto f4 = [](const float* p) { return reinterpret_cast<const float4*>(p); };
+    return mcpt::launch_temporal(k, f4(b.color), f4(b.var), f4(b.albedo_cov), f4(b.normal_depth), f4(b.hist_color_n),
+                                 f4(b.hist_var), f4(b.hist_albedo_cov), f4(b.hist_normal_depth),
+                                 reinterpret_cast<float4*>(b.out_color_n), reinterpret_cast<float4*>(b.out_var), st);
 }
 
 }  // namespace
@@ -214,6 +292,14 @@ void mcpt_denoise_var_params_default(mcpt_denoise_var_params* p) {
     p->sigma_l = 4.0f;
 }
 
+void mcpt_temporal_params_default(mcpt_temporal_params* p) {
+    if (!p) return;
+    p->max_history = 32;
+    p->normal_threshold = 0.9f;
+    p->sigma_z = 0.1f;
+    p->gamma_space = 0;
+}
+
 void mcpt_adaptive_params_default(mcpt_adaptive_params* p) {
     if (!p) return;
     p->max_passes = 8;
@@ -315,6 +401,48 @@ int mcpt_denoise_var(const mcpt_denoise_var_params* p, const float* color_rgb, c
         if (!p || !color_rgb || !var_rgba || !albedo_cov || !normal_depth || !out_rgb)
             return fail(MCPT_E_INVALID, "NULL argument");
         return denoise_on_host(denoise_var_resolve(p), color_rgb, var_rgba, albedo_cov, normal_depth, out_rgb);
+    });
+}
+
+int mcpt_temporal_device(const mcpt_temporal_params* tp, const mcpt_render_params* cur, const mcpt_render_params* prev,
+                         const float* d_color_rgba, const float* d_var_rgba, const float* d_albedo_cov,
+                         const float* d_normal_depth, const float* d_hist_color_n, const float* d_hist_var,
+                         const float* d_hist_albedo_cov, const float* d_hist_normal_depth, float* d_out_color_n,
+                         float* d_out_var, void* hip_stream) {
+    return guarded([&]() -> int {
+        const TemporalBufs b{d_color_rgba, d_var_rgba, d_albedo_cov, d_normal_depth, d_hist_color_n, d_hist_var,
+                             d_hist_albedo_cov, d_hist_normal_depth, d_out_color_n, d_out_var};
+        const mcpt::TemporalParams k = temporal_resolve(tp, cur, prev, b);
+        HIP_TRY(temporal_launch(k, b, static_cast<hipStream_t>(hip_stream)));
+        return MCPT_OK;
+    });
+}
+
+int mcpt_temporal(const mcpt_temporal_params* tp, const mcpt_render_params* cur, const mcpt_render_params* prev,
+                  const float* color_rgba, const float* var_rgba, const float* albedo_cov, const float* normal_depth,
+                  const float* hist_color_n, const float* hist_var, const float* hist_albedo_cov,
+                  const float* hist_normal_depth, float* out_color_n, float* out_var) {
+    return guarded([&]() -> int {
+        const TemporalBufs h{color_rgba, var_rgba, albedo_cov, normal_depth, hist_color_n, hist_var, hist_albedo_cov,
+                             hist_normal_depth, out_color_n, out_var};
+        const mcpt::TemporalParams k = temporal_resolve(tp, cur, prev, h);
+        const size_t bytes = size_t(k.width) * size_t(k.height) * 16, vbytes = var_rgba ? bytes : size_t(0);
+        // one allocation: the eight inputs in TemporalBufs' order, then the two outputs
+        const auto c = carve({bytes, vbytes, bytes, bytes, bytes, vbytes, bytes, bytes, bytes, vbytes});
+        TempDev buf(c.total);
+        const float* in[8] = {color_rgba, var_rgba, albedo_cov, normal_depth, hist_color_n, hist_var, hist_albedo_cov,
+                              hist_normal_depth};
+        for (size_t i = 0; i < 8; ++i)
+            if (in[i]) HIP_TRY(hipMemcpy(c.at<float>(buf.p, i), in[i], bytes, hipMemcpyHostToDevice));
+        auto dv = [&](size_t i) { return var_rgba ? c.at<float>(buf.p, i) : nullptr; };
+        const TemporalBufs d{c.at<float>(buf.p, 0), dv(1), c.at<float>(buf.p, 2), c.at<float>(buf.p, 3),
+                             c.at<float>(buf.p, 4), dv(5), c.at<float>(buf.p, 6), c.at<float>(buf.p, 7),
+                             c.at<float>(buf.p, 8), dv(9)};
+        HIP_TRY(temporal_launch(k, d, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        HIP_TRY(hipMemcpy(out_color_n, d.out_color_n, bytes, hipMemcpyDeviceToHost));
+        if (out_var) HIP_TRY(hipMemcpy(out_var, d.out_var, bytes, hipMemcpyDeviceToHost));
+        return MCPT_OK;
     });
 }
 

@@ -1,7 +1,7 @@
 // capi_internal.hpp -- what the host translation units of the C ABI share
 // (include/mcpt.h): the opaque handles, the render plan and workspace, the error
 // plumbing and the functions one unit defines and another calls.
-//   capi.cpp          init, errors, parameter defaults, the denoisers
+//   capi.cpp          init, errors, parameter defaults, the denoisers, temporal accumulation
 //   scene_image.cpp   models, the device image, scene creation and teardown
 //   plan.cpp          the render plan, its workspace, mcpt_plan_query, shards
 //   render_host.cpp   renders: one device, several, reserve, variance, adaptive, feature buffers
@@ -288,6 +288,8 @@ size_t spill_bytes(const mcpt_scene& s, int sets);
 void grow_spill(mcpt_scene& s, int sets, bool capturing);
 uint64_t tail_split(uint64_t lanes, int64_t per_lane, int64_t exact, uint32_t total_units, uint32_t chunk);
 uint64_t tail_units_for(const mcpt_scene& s, const Plan& pl);
+// the camera of p's eye / dir / up / fov_deg / width / height / mode (render_launch.hpp)
+mcpt::CameraConsts camera_consts(const mcpt_render_params& p);
 Plan make_plan(const mcpt_scene& s, const mcpt_render_params* p);
 void plan_wavefront(const mcpt_scene& s, Plan& pl, const mcpt_render_params* p, bool listed);
 uint32_t wf_batch_capacity(const mcpt_scene& s, const mcpt_render_params* p, uint64_t work, uint32_t chunk, int nstr);

@@ -231,6 +231,29 @@ mcpt::WfFacts scene_facts(const mcpt_scene& s) {   // (the render's facts: false
 size_t spill_bytes(const mcpt_scene& s, int sets) { return size_t(sets) * kSpillEntries * launched_lanes(s) * 16; }
 void grow_spill(mcpt_scene& s, int sets, bool capturing) { grow_ws(s, s.ws.spill, spill_bytes(s, sets), capturing); }
 
+// The camera of p as the kernels take it: make_plan's, and the temporal
+// accumulation's for both of its frames (capi.cpp)
+mcpt::CameraConsts camera_consts(const mcpt_render_params& p) {
+    mcpt::CameraConsts c{};
+    const float a = p.fov_deg * 3.14159265359f / 360;   // CUTracer.cu:189,202
+    c.tan_half_fov = static_cast<float>(std::tan(static_cast<double>(a)));
+    // camera basis (CUTracer.cu:349-359)
+    Vf d = normal_of(Vf{p.dir[0], p.dir[1], p.dir[2]});
+    Vf r = normal_of(cross_of(d, Vf{p.up[0], p.up[1], p.up[2]}));
+    Vf u = normal_of(cross_of(r, d));
+    for (int i = 0; i < 3; ++i) c.eye[i] = p.eye[i];
+    c.fwd[0] = d.x; c.fwd[1] = d.y; c.fwd[2] = d.z;
+    c.up[0] = u.x; c.up[1] = u.y; c.up[2] = u.z;
+    c.right[0] = r.x; c.right[1] = r.y; c.right[2] = r.z;
+    if (p.mode == MCPT_MODE_QUINENGINE) {
+        // camera GraphicsRTX.cpp:173-184 (PerspectiveFovRH: fov_deg is the vertical FOV)
+        const float ys = static_cast<float>(1.0 / std::tan(static_cast<double>(a)));
+        c.proj22 = ys;
+        c.proj11 = ys / (static_cast<float>(p.width) / static_cast<float>(p.height));
+    }
+    return c;
+}
+
 Plan make_plan(const mcpt_scene& s, const mcpt_render_params* p) {
     if (!p) throw mcpt::Error{MCPT_E_INVALID, "params is NULL"};
     if (p->width <= 0 || p->height <= 0) throw mcpt::Error{MCPT_E_INVALID, "width/height must be positive"};
@@ -281,33 +304,29 @@ Plan make_plan(const mcpt_scene& s, const mcpt_render_params* p) {
     k.max_depth = p->max_depth;
     k.lean = p->lean ? 1 : 0;
     k.illum = p->illum;
-    const float a = p->fov_deg * 3.14159265359f / 360;   // CUTracer.cu:189,202
-    k.tan_half_fov = static_cast<float>(std::tan(static_cast<double>(a)));
+    const mcpt::CameraConsts cam = camera_consts(*p);
+    k.tan_half_fov = cam.tan_half_fov;
     k.h_over_w = 1.0 * static_cast<double>(static_cast<uint32_t>(p->height)) / static_cast<double>(static_cast<uint32_t>(p->width));
     k.inv_w_pow2 = (p->width > 0 && (p->width & (p->width - 1)) == 0) ? 1.0 / static_cast<double>(p->width) : 0.0;
     k.fresnel_kd = p->fresnel_kd ? 1 : 0;
     k.prev_count = p->prev_count;
-    // camera basis (CUTracer.cu:349-359)
-    Vf d = normal_of(Vf{p->dir[0], p->dir[1], p->dir[2]});
-    Vf r = normal_of(cross_of(d, Vf{p->up[0], p->up[1], p->up[2]}));
-    Vf u = normal_of(cross_of(r, d));
-    for (int i = 0; i < 3; ++i) k.eye[i] = p->eye[i];
-    k.fwd[0] = d.x; k.fwd[1] = d.y; k.fwd[2] = d.z;
-    k.up[0] = u.x; k.up[1] = u.y; k.up[2] = u.z;
-    k.right[0] = r.x; k.right[1] = r.y; k.right[2] = r.z;
+    for (int i = 0; i < 3; ++i) {
+        k.eye[i] = cam.eye[i];
+        k.fwd[i] = cam.fwd[i];
+        k.up[i] = cam.up[i];
+        k.right[i] = cam.right[i];
+    }
     if (p->mode != MCPT_MODE_CVMCTRACER && p->mode != MCPT_MODE_QUINENGINE)
         throw mcpt::Error{MCPT_E_INVALID, "unknown mode"};
     k.mode = p->mode;
     k.best_init = FLT_MAX;
     if (p->mode == MCPT_MODE_QUINENGINE) {
         // rtx.hlsl:380 seeds TEA-16 with the 32-bit frame seed itself; t_best 10000 (:88);
-        // camera GraphicsRTX.cpp:173-184 (PerspectiveFovRH: fov_deg is the vertical FOV)
+        // the camera's projection: camera_consts
         k.key = static_cast<uint32_t>(p->seed);
         k.best_init = 10000.0f;
-        const float a = p->fov_deg * 3.14159265359f / 360;
-        const float ys = static_cast<float>(1.0 / std::tan(static_cast<double>(a)));
-        k.proj22 = ys;
-        k.proj11 = ys / (static_cast<float>(p->width) / static_cast<float>(p->height));
+        k.proj22 = cam.proj22;
+        k.proj11 = cam.proj11;
     } else {
         k.key = tea16(static_cast<uint32_t>(p->seed), static_cast<uint32_t>(p->seed >> 32));
     }

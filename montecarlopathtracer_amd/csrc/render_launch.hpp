@@ -232,6 +232,14 @@ struct FastDiv {
     }
 };
 
+// One frame's camera as the kernels take it (capi_internal.hpp camera_consts): eye,
+// the normalized basis, tan(fov / 2) and -- QuinEngine mode only, else 0 -- the
+// projection's two scales
+struct CameraConsts {
+    float eye[3], fwd[3], up[3], right[3];
+    float tan_half_fov, proj11, proj22;
+};
+
 struct KernelParams {
     GpuScene scene;
     int32_t width, height;

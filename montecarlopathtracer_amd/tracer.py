@@ -968,6 +968,58 @@ def denoise_var_device(width: int, height: int, color_ptr: int, var_ptr: int, al
                                         C.c_void_p(out_ptr), C.c_void_p(scratch_ptr), C.c_void_p(stream_ptr)))
 
 
+def temporal_params(max_history: int = 0, normal_threshold: float = 0.0, sigma_z: float = 0.0,
+                    gamma_space: bool = False) -> "_capi.TemporalParamsC":
+    """mcpt_temporal_params; 0 = the default (history capped at 32 frames, normal threshold 0.9,
+    sigma_z 0.1)."""
+    return _capi.TemporalParamsC(int(max_history), float(normal_threshold), float(sigma_z), 1 if gamma_space else 0)
+
+
+def temporal(cur: RenderParams, prev: RenderParams, color: np.ndarray, variance, albedo_cov: np.ndarray,
+             normal_depth: np.ndarray, hist_color_n: np.ndarray, hist_var, hist_albedo_cov: np.ndarray,
+             hist_normal_depth: np.ndarray, **params):
+    """Temporal accumulation of host images on the current device (mcpt_temporal): the history
+    (hist_color_n (H, W, 4) r g b N, hist_var, the previous frame's feature buffers, camera
+    ``prev``) reprojected onto camera ``cur`` and blended with this frame (color (H, W, 3) or
+    (H, W, 4), variance of Scene.render_var, the feature buffers of Scene.render_aov).
+    variance and hist_var are given together or both None.  Returns (color_n, var), each
+    (H, W, 4) -- var None without variance; they and this frame's features are the next
+    call's history.  params: the fields of temporal_params."""
+    color = np.ascontiguousarray(color, np.float32)
+    if color.ndim != 3 or color.shape[2] not in (3, 4):
+        raise McptError(-1, "color must be (H, W, 3) or (H, W, 4)")
+    H, W = color.shape[:2]
+    if color.shape[2] == 3:
+        color = np.ascontiguousarray(np.concatenate([color, np.zeros((H, W, 1), np.float32)], axis=-1))
+    if (variance is None) != (hist_var is None):
+        raise McptError(-1, "variance and hist_var must be given together or both be None")
+    bufs = [None if a is None else np.ascontiguousarray(a, np.float32)
+            for a in (variance, albedo_cov, normal_depth, hist_color_n, hist_var, hist_albedo_cov, hist_normal_depth)]
+    if any(a is not None and a.size != H * W * 4 for a in bufs):
+        raise McptError(-1, "every buffer must hold 4 floats per pixel of color")
+    v, a, n, hc, hv, ha, hn = bufs
+    out = np.zeros((H, W, 4), np.float32)
+    out_var = None if v is None else np.zeros((H, W, 4), np.float32)
+    opt = lambda x: None if x is None else _fptr(x)   # noqa: E731
+    check(lib().mcpt_temporal(C.byref(temporal_params(**params)), C.byref(cur.to_c()), C.byref(prev.to_c()),
+                              _fptr(color), opt(v), _fptr(a), _fptr(n), _fptr(hc), opt(hv), _fptr(ha), _fptr(hn),
+                              _fptr(out), opt(out_var)))
+    return out, out_var
+
+
+def temporal_device(cur: RenderParams, prev: RenderParams, color_ptr: int, var_ptr: int, albedo_ptr: int, nd_ptr: int,
+                    hist_color_ptr: int, hist_var_ptr: int, hist_albedo_ptr: int, hist_nd_ptr: int, out_color_ptr: int,
+                    out_var_ptr: int, stream_ptr: int = 0, **params) -> None:
+    """Asynchronous temporal accumulation of device RGBA float buffers (mcpt_temporal_device):
+    the eight inputs are only read, out_color and out_var receive the result; the three variance
+    pointers are given together or all 0 (no variance carried)."""
+    check(lib().mcpt_temporal_device(C.byref(temporal_params(**params)), C.byref(cur.to_c()), C.byref(prev.to_c()),
+                                     *[C.c_void_p(int(p) or None) for p in
+                                       (color_ptr, var_ptr, albedo_ptr, nd_ptr, hist_color_ptr, hist_var_ptr,
+                                        hist_albedo_ptr, hist_nd_ptr, out_color_ptr, out_var_ptr)],
+                                     C.c_void_p(stream_ptr)))
+
+
 class Tracer:
     """PW::Tracer as an object: Initialize / CreateGeometry / DestroyGeometry / RenderScene."""
 
