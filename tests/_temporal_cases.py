@@ -22,6 +22,7 @@ def yaw(deg):
 
 
 DEFAULT = dict(eye=(0.0, 5.0, 17.0), direction=(0.0, 0.0, -1.0))
+ORBIT = dict(eye=(2.0, 6.5, 15.0), direction=(-0.1, -0.15, -1.0), up=(0.1, 1.0, 0.0))
 # name: (mode, W, H, cur camera, prev camera, the classes the reference must populate)
 SCENE_CASES = {
     "equal": ("cv", W0, H0, DEFAULT, DEFAULT, (T.MISS, T.REJECTED, T.BILINEAR)),
@@ -37,6 +38,9 @@ SCENE_CASES = {
     "aspect-fov": ("cv", 64, 48, dict(eye=(0.0, 5.0, 17.0), direction=yaw(2.0), fov=50.0),
                    dict(eye=(0.0, 5.0, 17.0), direction=(0.0, 0.0, -1.0), fov=45.0),
                    (T.MISS, T.BEHIND, T.REJECTED, T.BILINEAR, T.FALLBACK)),
+    # pitch, roll and an up that is not (0, 1, 0): camera_consts' basis with every input in play
+    "orbit": ("cv", W0, H0, ORBIT, DEFAULT, (T.MISS, T.REJECTED, T.BILINEAR, T.FALLBACK)),
+    "qe-orbit": ("qe", W0, H0, ORBIT, DEFAULT, (T.MISS, T.REJECTED, T.BILINEAR, T.FALLBACK)),
 }
 
 
